@@ -4,8 +4,9 @@
 Headline metric (BASELINE.json): raster fwd+bwd Mpix/s at 1M Gaussians, 1920x1080 (SURVEY.md §8d
 Metric 1); the same run also reports SDF Msamples/s (Metric 2) once the SDF kernels exist.
 
-  python bench.py --gpus N --steps K --warmup W
-  (N > 1: launched by torch.distributed.run, one rank per GPU; every rank renders its own camera
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  (--dump-outputs: the last timed step's outputs as DIR/<name>.npy, for comparing two builds output for output;
+   N > 1: launched by torch.distributed.run, one rank per GPU; every rank renders its own camera
    view of the same Gaussian cloud and the parameter gradients are all-reduced over RCCL, as a
    multi-view training step would; weak scaling.)
 
@@ -563,6 +564,39 @@ def _prof_run(L, fn, steps):
     buf = C.create_string_buffer(16384)
     L.pings_prof_report(buf, len(buf))
     return {k: v[1] / steps for k, v in parse_prof(buf.value.decode()).items()}
+
+
+DUMP_BUDGET_BYTES = 60_000_000   # --dump-outputs: all arrays together stay under 64 MB
+DUMP_SEED = 0
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: write every tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy, float64 if the tensor is
+    float64 or an integer type (exact), float32 otherwise.  The budget is split evenly between the arrays; an array over
+    its share keeps a fixed sample of its items, as [k, values per item].  Items are the rows of a [P, ...] array and
+    the pixels of a [C, H, W] image.  The sample is the first k of a permutation seeded with DUMP_SEED, in ascending
+    order: two runs (or two builds) with the same arguments write the same items, and arrays with the same item count
+    share the items the smaller sample keeps.  Returns {name: {"shape": full shape, "items_kept": k or None when whole}}."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BUDGET_BYTES // len(arrays)
+    perms = {}
+    written = {}
+    for name, t in arrays.items():
+        t = t.detach()
+        exact64 = t.dtype == torch.float64 or not t.is_floating_point()
+        a = t.to(torch.float64 if exact64 else torch.float32).cpu().numpy()
+        kept = None
+        if a.nbytes > share:
+            rows = a.reshape(a.shape[0], -1).T if a.ndim == 3 else a.reshape(a.shape[0], -1)
+            kept = max(1, share // rows[0].nbytes)
+            if rows.shape[0] not in perms:
+                perms[rows.shape[0]] = np.random.default_rng(DUMP_SEED).permutation(rows.shape[0])
+            a = np.ascontiguousarray(rows[np.sort(perms[rows.shape[0]][:kept])])
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+        written[name] = {"shape": list(t.shape), "items_kept": kept}
+    return written
 
 
 def bench_sdf_sweep(dev, steps, warmup, sizes=(200_000, 1_000_000, 5_000_000), with_cpu=True):
@@ -1157,7 +1191,12 @@ def main():
                     help="N > 1: run the render_step_exchange leg even with --no-sdf (rehearsals)")
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal only: put every rank on cuda:0 (use with --backend gloo)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (rasteriser outputs and parameter "
+                         "gradients of rank 0) as DIR/<name>.npy, under 64 MB in all (see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # backward passes run on the calling thread: the hand-off to autograd's per-device worker thread and back costs
     # 40-300 us per backward() depending on the box (measured: a two-operator graph 40 vs 73 us, the fused SDF step 178
@@ -1318,10 +1357,12 @@ def main():
     report()
     host_ms = []
     t0 = time.perf_counter()
-    for _ in range(args.steps):
+    for i in range(args.steps):
         ts = time.perf_counter()
-        step()
+        out = step()
         host_ms.append((time.perf_counter() - ts) * 1e3)  # host-side issue time only (no sync)
+        if i < args.steps - 1:
+            del out  # released before the next step allocates, as when the result was discarded; the last one is dumped
     sync()
     elapsed = time.perf_counter() - t0
     L.pings_prof_enable(0)
@@ -1335,6 +1376,19 @@ def main():
     elapsed = t.item()
     ms_per_step = elapsed / args.steps * 1e3
     value = world * W * H / (elapsed / args.steps) / 1e6
+
+    # what the last timed step handed its caller: the rasteriser's outputs and the gradients of its inputs
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        names = (("image", "normal", "depth", "alpha", "radii", "contributions") if surfel
+                 else ("image", "radii", "depth", "alpha", "n_touched"))
+        arrays = dict(zip(names, out))
+        for n, p_ in zip(("means3D", "colors", "opacities", "scales", "rotations", "theta", "rho"), params + [theta, rho]):
+            if p_.grad is not None:
+                arrays[f"grad_{n}"] = p_.grad
+        dumped = {"dir": args.dump_outputs, "arrays": dump_outputs(args.dump_outputs, arrays)}
+        del arrays
+    del out
 
     # N > 1: the real multi-view mapping step (every rank takes part: collectives inside), VERDICT r3 #7
     rse = None
@@ -1516,6 +1570,8 @@ def main():
             "roofline": roofline, "kernels": kernels, "cpu_baseline": cpu, "sdf": sdf, "decoder": decoder,
             "map_maintenance": map_maint, "image_losses": img_losses, **extras,
         }
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         print(json.dumps(line), flush=True)
     if world > 1:
         dist.destroy_process_group()

@@ -48,3 +48,50 @@ def test_headline_pmc_summary_is_found_next_to_the_other_summaries():
 
     traffic, src, valu = bench.pmc_traffic("blend_bwd", dict(gaussians=1_000_000, width=1920, height=1080, mode="surfel"))
     assert traffic and valu and src.endswith("pmc_traffic.json") and "ssim" not in src and "sdf" not in src
+
+
+def test_dump_outputs_is_bounded_repeatable_and_keeps_small_arrays_whole(tmp_path):
+    """--dump-outputs at the headline shapes (1M Gaussians, 1080p): under 64 MB in all, the same arrays on a second
+    run, float32 / float64 only, image samples are pixels of the image, and arrays within budget keep their layout."""
+    import sys
+
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, str(PROFILES.parent))
+    import bench
+
+    P, H, W = 1_000_000, 1080, 1920
+    g = torch.Generator().manual_seed(0)
+    arrays = {"image": torch.rand(3, H, W, generator=g), "depth": torch.rand(1, H, W, generator=g),
+              "radii": torch.randint(0, 50, (P,), dtype=torch.int32, generator=g),
+              "grad_means3D": torch.rand(P, 3, generator=g), "grad_rotations": torch.rand(P, 4, generator=g),
+              "grad_theta": torch.rand(3, generator=g)}
+    a = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    b = bench.dump_outputs(str(tmp_path / "b"), arrays)
+    assert a == b and set(a) == set(arrays)
+    assert sum(f.stat().st_size for f in (tmp_path / "a").iterdir()) <= 64_000_000
+    for name in arrays:
+        x, y = np.load(tmp_path / "a" / f"{name}.npy"), np.load(tmp_path / "b" / f"{name}.npy")
+        assert x.dtype in (np.float32, np.float64) and np.array_equal(x, y), name
+    assert np.load(tmp_path / "a" / "radii.npy").dtype == np.float64          # integers travel exactly
+    assert a["grad_theta"] == {"shape": [3], "items_kept": None}
+    assert np.array_equal(np.load(tmp_path / "a" / "grad_theta.npy"), arrays["grad_theta"].numpy())
+    img, k = np.load(tmp_path / "a" / "image.npy"), a["image"]["items_kept"]
+    assert a["image"]["shape"] == [3, H, W] and img.shape == (k, 3) and 0 < k < H * W
+    px = np.sort(np.random.default_rng(bench.DUMP_SEED).permutation(H * W)[:k])
+    assert np.array_equal(img, arrays["image"].numpy().reshape(3, -1).T[px])
+
+
+def test_bench_refuses_zero_steps(monkeypatch):
+    import sys
+
+    import pytest
+
+    sys.path.insert(0, str(PROFILES.parent))
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "0", "--warmup", "1"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
