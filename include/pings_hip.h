@@ -35,7 +35,7 @@
 
 /* ABI version of this header (bumped on any signature change).  A binding compares pings_abi_version() of the
  * library it loaded with the PINGS_ABI_VERSION of the header it was written against (pings_amd/_lib.py does). */
-#define PINGS_ABI_VERSION 8
+#define PINGS_ABI_VERSION 9
 PINGS_API int pings_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). Host string. */
 PINGS_API const char* pings_last_error(void);
@@ -92,10 +92,11 @@ PINGS_API int pings_ssim_backward(const float* img1, const float* img2, int plan
  */
 #define PINGS_RASTER_SURFEL 0
 #define PINGS_RASTER_3DGS 1
+#define PINGS_RASTER_2DGS 2   /* only the pings_raster2d_* entry points below accept it */
 
 typedef struct pings_raster_settings {
   int32_t image_height, image_width;
-  int32_t mode;           /* PINGS_RASTER_SURFEL | PINGS_RASTER_3DGS                     */
+  int32_t mode;           /* PINGS_RASTER_SURFEL | PINGS_RASTER_3DGS | PINGS_RASTER_2DGS  */
   int32_t front_only;     /* config[4] of the surfel settings (surfel mode only)          */
   double tanfovx, tanfovy;
   double scale_modifier;
@@ -185,6 +186,56 @@ PINGS_API int pings_raster_debug_lists(const void* binning_blob, int64_t num_ins
 PINGS_API int pings_raster_debug_image(const void* image_blob, int image_height, int image_width,
                                        float* final_T, uint32_t* n_contrib, void* stream);
 
+
+/* ------------------------------------------- 2D Gaussian splatting rasteriser
+ * Replaces the `diff_surfel_rasterization` torch extension (gaussian_renderer/__init__.py:88-89; settings :167-181;
+ * outputs consumed :349-409): ray-splat intersection of Huang et al. 2024, restated in tests/raster2d_ref.py
+ * (assumptions in DESIGN.md §3).  A parallel set of entry points with its own blobs: the settings struct is the one
+ * above with mode = PINGS_RASTER_2DGS (projmatrix = full_proj_transform is what it reads; projmatrix_raw, prcppoint
+ * and front_only are ignored); modes 0 / 1 are unchanged and the pings_raster_* entries reject mode 2.
+ * Scales are [P,2] (two tangent axes).  Same memory protocol: geom / binning / image blobs sized by the queries,
+ * handed unchanged to pings_raster2d_backward. */
+PINGS_API size_t pings_raster2d_geom_bytes(int P, int image_height, int image_width);
+PINGS_API size_t pings_raster2d_binning_bytes(int64_t num_instances, int image_height, int image_width);
+PINGS_API size_t pings_raster2d_image_bytes(int image_height, int image_width);
+
+/* Stage 1: per-Gaussian splat-to-pixel matrix, screen centre, radius (radii[P], 0 = culled), published tile square,
+ * camera-frame normal, depth key, tiles-per-Gaussian scan.  Synchronises `stream` once: *num_instances (HOST, summed
+ * in 64 bits; 2^31 - 1 pairs or more return PINGS_ERR_CAPACITY) and, in the same read-back, up to 6 device int32
+ * words aux_dev[i] -> aux_host[i] (HOST arrays; aux_words = 0: unused).
+ * live_rows_dev (nullable): of the first dyn_rows Gaussians only rows [0, *live_rows_dev) exist (as in
+ * pings_raster_preprocess_dyn). */
+PINGS_API int pings_raster2d_preprocess(const pings_raster_settings* s, int P, const float* means3D,
+                                        const float* colors, const float* opacities, const float* scales,
+                                        const float* rotations, void* geom_blob, int32_t* radii,
+                                        const int32_t* live_rows_dev, int dyn_rows, const int32_t* const* aux_dev,
+                                        int aux_words, int32_t* aux_host, int64_t* num_instances, void* stream);
+
+/* Stage 2: binning (stable sort by tile, then depth, then Gaussian index) and front-to-back blending.
+ * out_color [3,H,W] = C + T bg;  out_allmap [7,H,W] = {expected depth (not normalised), 1 - T, normal xyz,
+ * median depth (0 = none), depth distortion}. */
+PINGS_API int pings_raster2d_render(const pings_raster_settings* s, int P, int64_t num_instances, void* geom_blob,
+                                    void* binning_blob, void* image_blob, float* out_color, float* out_allmap,
+                                    void* stream);
+
+PINGS_API size_t pings_raster2d_backward_bytes(int P, int64_t num_instances);
+
+/* Backward of stage 1+2 w.r.t. means3D [P,3], colours [P,3], opacities [P,1], scales [P,2], rotations [P,4]
+ * (overwritten).  dL_dcolor [3,H,W] / dL_dallmap [7,H,W] may be NULL (zero).  dL_dmeans2D [P,3] receives the
+ * gradient w.r.t. the screen centre through the low-pass branch (xy, z = 0).  Deterministic: no float atomics. */
+PINGS_API int pings_raster2d_backward(const pings_raster_settings* s, int P, int64_t num_instances,
+                                      const float* scales, const float* rotations, const void* geom_blob,
+                                      const void* binning_blob, const void* image_blob, const float* dL_dcolor,
+                                      const float* dL_dallmap, void* bwd_blob, float* dL_dmeans3D,
+                                      float* dL_dmeans2D, float* dL_dcolors, float* dL_dopacities,
+                                      float* dL_dscales, float* dL_drotations, void* stream);
+
+/* Parity taps (tests only): sorted Gaussian ids and tile ranges; final T, last contributor (list position + 1,
+ * relative to the tile's range) and median contributor (list position, -1 = none) per pixel. */
+PINGS_API int pings_raster2d_debug_lists(const void* binning_blob, int64_t num_instances, int image_height,
+                                         int image_width, uint32_t* point_list, uint32_t* ranges_xy, void* stream);
+PINGS_API int pings_raster2d_debug_image(const void* image_blob, int image_height, int image_width, float* final_T,
+                                         uint32_t* n_contrib, int32_t* median, void* stream);
 
 /* -------------------------------------------- neural-point kNN + SDF decode
  * Replaces, for the query path, `NeuralPoints.radius_neighborhood_search`

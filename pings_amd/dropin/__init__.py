@@ -2,7 +2,7 @@
 
 Put this directory on `sys.path` (see `path()` / `activate()`), or install it, and the
 reference's `from diff_gaussian_surfel_rasterization import GaussianRasterizationSettings,
-GaussianRasterizer`, `from diff_gaussian_rasterization import ...` and
+GaussianRasterizer`, `from diff_gaussian_rasterization import ...`, `from diff_surfel_rasterization import ...` and
 `from fused_ssim import fused_ssim` resolve to the HIP implementations."""
 import os
 import sys

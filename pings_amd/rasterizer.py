@@ -8,6 +8,9 @@ Mirrors the two modules the reference imports
   returns `(image, normal, depth, alpha, radii, contributions)` (:318-326).
 * `diff_gaussian_rasterization.{...}` (MonoGS-style 3DGS with pose) — settings at :185-199,
   `__call__` returns `(image, radii, depth, alpha, n_touched)` (:415-423).
+* `diff_surfel_rasterization.{...}` (2D Gaussian splatting) — settings at :167-181, `__call__`
+  returns `(image, radii, allmap)` (:351-358), allmap = [depth, alpha, normal xyz, median depth,
+  distortion] (:366-404); restated in tests/raster2d_ref.py.
 
 Both expose `markVisible(positions) -> BoolTensor[N]` (:215).  The absent CUDA
 extensions' semantics are restated in oracle/raster_cpu.py; see DESIGN.md.
@@ -24,6 +27,7 @@ from . import _lib
 
 MODE_SURFEL = 0
 MODE_3DGS = 1
+MODE_2DGS = 2
 
 
 class _CSettings(C.Structure):
@@ -73,6 +77,22 @@ class GS3DRasterizationSettings(NamedTuple):
     debug: bool
 
 
+class Surfel2DRasterizationSettings(NamedTuple):
+    """Field-for-field the record built at gaussian_renderer/__init__.py:167-181 (2d_gs)."""
+    image_height: int
+    image_width: int
+    tanfovx: float
+    tanfovy: float
+    bg: torch.Tensor
+    scale_modifier: float
+    viewmatrix: torch.Tensor
+    projmatrix: torch.Tensor
+    sh_degree: int
+    campos: torch.Tensor
+    prefiltered: bool
+    debug: bool
+
+
 def _f32c(t: torch.Tensor) -> torch.Tensor:
     return t.detach().to(torch.float32).contiguous()
 
@@ -86,7 +106,14 @@ class _Prepared:
         self.bg = _f32c(rs.bg).reshape(-1)
         self.view = _f32c(rs.viewmatrix)
         self.proj = _f32c(rs.projmatrix)
-        self.proj_raw = _f32c(rs.projmatrix_raw)
+        if mode == MODE_2DGS:
+            # the 2d_gs record carries no projection_matrix; markVisible's frustum test (shared with the other modes)
+            # wants it: P^T = viewmatrix^-1 @ full_proj_transform (cameras.py:214-216), fp64, on the device
+            v64 = rs.viewmatrix.detach().to(torch.float64)
+            self.proj_raw = (torch.linalg.inv_ex(v64)[0] @ rs.projmatrix.detach().to(torch.float64)).to(
+                torch.float32).contiguous()
+        else:
+            self.proj_raw = _f32c(rs.projmatrix_raw)
         dev = self.view.device
         if not self.view.is_cuda:
             raise _lib.PingsHipError("rasteriser settings must live on the HIP device (no CPU fallback)")
@@ -357,3 +384,175 @@ class GS3DGaussianRasterizer(_RasterizerBase):
     """`diff_gaussian_rasterization.GaussianRasterizer` (MonoGS-style, with pose): returns
     (image[3,H,W], radii[P], depth[1,H,W] un-normalised, alpha[1,H,W], n_touched[P] int32)."""
     MODE = MODE_3DGS
+
+
+# ------------------------------------------------------------------ 2D Gaussian splatting (diff_surfel_rasterization)
+def _declare2d(L):
+    if getattr(L, "_raster2d_declared", False):
+        return
+    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
+    L.pings_raster2d_geom_bytes.restype = C.c_size_t
+    L.pings_raster2d_geom_bytes.argtypes = [i32, i32, i32]
+    L.pings_raster2d_binning_bytes.restype = C.c_size_t
+    L.pings_raster2d_binning_bytes.argtypes = [i64, i32, i32]
+    L.pings_raster2d_image_bytes.restype = C.c_size_t
+    L.pings_raster2d_image_bytes.argtypes = [i32, i32]
+    L.pings_raster2d_preprocess.restype = C.c_int
+    L.pings_raster2d_preprocess.argtypes = [C.POINTER(_CSettings), i32, vp, vp, vp, vp, vp, vp, vp, vp, i32,
+                                            C.POINTER(C.c_void_p), i32, C.POINTER(C.c_int32),
+                                            C.POINTER(C.c_int64), vp]
+    L.pings_raster2d_render.restype = C.c_int
+    L.pings_raster2d_render.argtypes = [C.POINTER(_CSettings), i32, i64, vp, vp, vp, vp, vp, vp]
+    L.pings_raster2d_backward_bytes.restype = C.c_size_t
+    L.pings_raster2d_backward_bytes.argtypes = [i32, i64]
+    L.pings_raster2d_backward.restype = C.c_int
+    L.pings_raster2d_backward.argtypes = [C.POINTER(_CSettings), i32, i64] + [vp] * 14 + [vp]
+    L.pings_raster2d_debug_lists.restype = C.c_int
+    L.pings_raster2d_debug_lists.argtypes = [vp, i64, i32, i32, vp, vp, vp]
+    L.pings_raster2d_debug_image.restype = C.c_int
+    L.pings_raster2d_debug_image.argtypes = [vp, i32, i32, vp, vp, vp, vp]
+    L._raster2d_declared = True
+
+
+def _lib_raster2d():
+    L = _lib.lib()
+    _declare(L)
+    _declare2d(L)
+    return L
+
+
+class _Forward2DState:
+    """What the 2DGS backward pass reads: the three blobs, the inputs it differentiates through, the sizes."""
+    __slots__ = ("prep", "P", "I", "geom", "binning", "image", "scales", "rotations", "color", "allmap")
+
+
+def _forward2d(prep: _Prepared, means3D, colors, opacities, scales, rotations):
+    L = _lib_raster2d()
+    dev = means3D.device
+    P = means3D.shape[0]
+    H, W = prep.H, prep.W
+    u8 = dict(dtype=torch.uint8, device=dev)
+    stream = _lib.stream_ptr(dev)
+    geom = torch.empty(L.pings_raster2d_geom_bytes(P, H, W), **u8)
+    radii = torch.empty(P, dtype=torch.int32, device=dev)
+    image = torch.empty(L.pings_raster2d_image_bytes(H, W), **u8)
+    color = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+    allmap = torch.empty(7, H, W, dtype=torch.float32, device=dev)
+    n_inst = C.c_int64(0)
+    _lib.check(L.pings_raster2d_preprocess(prep.ref(), P, _lib.ptr(means3D), _lib.ptr(colors), _lib.ptr(opacities),
+                                           _lib.ptr(scales), _lib.ptr(rotations), _lib.ptr(geom), _lib.ptr(radii),
+                                           None, 0, None, 0, None, C.byref(n_inst), stream),
+               "pings_raster2d_preprocess")
+    _lib.note_sync("raster_instance_count")
+    I = n_inst.value
+    binning = torch.empty(L.pings_raster2d_binning_bytes(I, H, W), **u8)
+    _lib.check(L.pings_raster2d_render(prep.ref(), P, I, _lib.ptr(geom), _lib.ptr(binning), _lib.ptr(image),
+                                       _lib.ptr(color), _lib.ptr(allmap), stream), "pings_raster2d_render")
+    fs = _Forward2DState()
+    fs.prep, fs.P, fs.I = prep, P, I
+    fs.geom, fs.binning, fs.image = geom, binning, image
+    fs.scales, fs.rotations = scales, rotations
+    fs.color, fs.allmap = color, allmap
+    return fs, radii
+
+
+def debug_lists2d(fs: _Forward2DState):
+    """(point_list[I] int64 Gaussian ids, ranges[num_tiles,2] int64, final_T[H,W], last[H,W], median[H,W])."""
+    L = _lib_raster2d()
+    dev = fs.geom.device
+    H, W = fs.prep.H, fs.prep.W
+    nt = ((W + 15) // 16) * ((H + 15) // 16)
+    pl = torch.empty(max(fs.I, 1), dtype=torch.int32, device=dev)
+    rg = torch.empty(nt * 2, dtype=torch.int32, device=dev)
+    stream = _lib.stream_ptr(dev)
+    _lib.check(L.pings_raster2d_debug_lists(_lib.ptr(fs.binning), fs.I, H, W, _lib.ptr(pl), _lib.ptr(rg), stream),
+               "pings_raster2d_debug_lists")
+    fT = torch.empty(H, W, dtype=torch.float32, device=dev)
+    nc = torch.empty(H, W, dtype=torch.int32, device=dev)
+    med = torch.empty(H, W, dtype=torch.int32, device=dev)
+    _lib.check(L.pings_raster2d_debug_image(_lib.ptr(fs.image), H, W, _lib.ptr(fT), _lib.ptr(nc), _lib.ptr(med),
+                                            stream), "pings_raster2d_debug_image")
+    return pl[:fs.I].long(), rg.view(nt, 2).long(), fT, nc, med
+
+
+def backward2d(fs: _Forward2DState, g_color, g_allmap):
+    """(d_means3D[P,3], d_means2D[P,3], d_colors[P,3], d_opacities[P,1], d_scales[P,2], d_rotations[P,4])."""
+    L = _lib_raster2d()
+    dev = fs.geom.device
+    P, I = fs.P, fs.I
+    f32 = dict(dtype=torch.float32, device=dev)
+
+    def gc(g):
+        return None if g is None else g.detach().to(torch.float32).contiguous()
+
+    g_color, g_allmap = gc(g_color), gc(g_allmap)
+    scratch = torch.empty(L.pings_raster2d_backward_bytes(P, I), dtype=torch.uint8, device=dev)
+    outs = (torch.empty(P, 3, **f32), torch.empty(P, 3, **f32), torch.empty(P, 3, **f32), torch.empty(P, 1, **f32),
+            torch.empty(P, 2, **f32), torch.empty(P, 4, **f32))
+    _lib.check(L.pings_raster2d_backward(
+        fs.prep.ref(), P, I, _lib.ptr(fs.scales), _lib.ptr(fs.rotations), _lib.ptr(fs.geom), _lib.ptr(fs.binning),
+        _lib.ptr(fs.image), _lib.ptr(g_color), _lib.ptr(g_allmap), _lib.ptr(scratch),
+        *[_lib.ptr(o) for o in outs], _lib.stream_ptr(dev)), "pings_raster2d_backward")
+    return outs
+
+
+class _RasterizeSurfels2D(torch.autograd.Function):
+    """autograd.Function over pings_raster2d_{preprocess,render,backward}: inputs means3D, means2D (gradient sink,
+    never read), colors_precomp, opacities, scales [P,2], rotations, prepared settings."""
+
+    @staticmethod
+    def forward(ctx, means3D, means2D, colors, opacities, scales, rotations, prep):
+        for name, t in (("means3D", means3D), ("colors_precomp", colors), ("opacities", opacities),
+                        ("scales", scales), ("rotations", rotations)):
+            if not t.is_cuda:
+                raise _lib.PingsHipError(f"{name} must be on the HIP device (no CPU fallback)")
+        P = means3D.shape[0]
+        if colors.shape != (P, 3) or rotations.shape != (P, 4) or opacities.numel() != P or means3D.shape != (P, 3):
+            raise ValueError("rasterizer: inconsistent Gaussian attribute shapes")
+        fs, radii = _forward2d(prep, _f32c(means3D), _f32c(colors), _f32c(opacities).reshape(P, 1), _f32c(scales),
+                               _f32c(rotations))
+        ctx.fs = fs
+        ctx.opac_shape = opacities.shape
+        ctx.mark_non_differentiable(radii)
+        # aliases, not fs's own tensor objects: no output -> grad_fn -> ctx -> output cycle (see _RasterizeGaussians)
+        return fs.color.detach(), radii, fs.allmap.detach()
+
+    @staticmethod
+    def backward(ctx, g_color, _g_radii, g_allmap):
+        d_m3, d_m2, d_c, d_o, d_s, d_r = backward2d(ctx.fs, g_color, g_allmap)
+        return d_m3, d_m2, d_c, d_o.reshape(ctx.opac_shape), d_s, d_r, None
+
+
+class Surfel2DGaussianRasterizer(nn.Module):
+    """`diff_surfel_rasterization.GaussianRasterizer` (2D Gaussian splatting): returns
+    (image[3,H,W], radii[P] int32, allmap[7,H,W]); allmap = [expected depth (not normalised), alpha, normal xyz
+    (camera frame), median depth, depth distortion].  The gradient reaching `means2D` is dL/d(screen centre) of the
+    low-pass branch (xy, z = 0)."""
+    MODE = MODE_2DGS
+
+    def __init__(self, raster_settings):
+        super().__init__()
+        self.raster_settings = raster_settings
+        self._prep: Optional[_Prepared] = None
+
+    def _prepared(self) -> _Prepared:
+        if self._prep is None:
+            self._prep = _Prepared(self.raster_settings, self.MODE)
+        return self._prep
+
+    def markVisible(self, positions: torch.Tensor) -> torch.Tensor:
+        """Frustum test of point centres -> BoolTensor[N] (gaussian_renderer/__init__.py:215), the rule of the other
+        two backends."""
+        with torch.no_grad():
+            return mark_visible(positions, self._prepared())
+
+    def forward(self, means3D, means2D, opacities, shs=None, colors_precomp=None, scales=None, rotations=None,
+                cov3D_precomp=None):
+        if shs is not None or colors_precomp is None:
+            raise NotImplementedError("only colors_precomp is supported (the PINGS path never evaluates SH)")
+        if cov3D_precomp is not None or scales is None or rotations is None:
+            raise NotImplementedError("only scales + rotations are supported (no cov3D_precomp)")
+        if scales.dim() != 2 or scales.shape[1] != 2:
+            raise ValueError(f"2D Gaussian splatting takes scales [P,2], got {tuple(scales.shape)}")
+        return _RasterizeSurfels2D.apply(means3D, means2D, colors_precomp, opacities, scales, rotations,
+                                         self._prepared())

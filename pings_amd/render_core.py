@@ -16,6 +16,10 @@ reference's early-outs and narrows the returned tensors to their exact shapes (v
 `_SpawnRaster` = `_Activate` + `_RasterizeGaussians` of the legacy path in one node (one Python round trip each way
 instead of two, and no slice nodes between them); `spawn.gather` and `mlp.fused_mlp_group` run on the capacity-sized
 buffers with the device count forward and the (by then host-known) exact count backward.
+
+The 2DGS mode (`gs_type="2d_gs"`) goes through the same node: the spawn block is the 3d_gs activation ([P,3] scales),
+the rasteriser reads its first two columns (`pings_raster2d_*`), and the returned `gaussian_scale` is the [:, :2] view
+the legacy path returns; its outputs are (image, allmap) instead of the four surfel / 3DGS images.
 """
 from __future__ import annotations
 
@@ -52,6 +56,7 @@ def _declare(L):
         return
     vp, i32 = C.c_void_p, C.c_int
     _rast._declare(L)
+    _rast._declare2d(L)
     _spawn._declare(L)
     L.pings_spawn_plan_dyn.restype = C.c_int
     L.pings_spawn_plan_dyn.argtypes = [C.POINTER(_spawn.SpawnParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -101,19 +106,22 @@ class _SpawnRaster(torch.autograd.Function):
         f32 = dict(dtype=torch.float32, device=dev)
         u8 = dict(dtype=torch.uint8, device=dev)
         surfel = prep.mode == _rast.MODE_SURFEL
+        two_d = prep.mode == _rast.MODE_2DGS
         sdim = 3 if p.surfel else p.scale_dim
         if sdim != 3:
             raise ValueError("rasteriser needs three scale columns per Gaussian")
         # ---- one allocation for everything only kernels see: [words | dest | plan scratch | geom | image]
         H, W = prep.H, prep.W
         al = lambda v: (v + 255) & ~255
-        key = (nk, P, H, W)
+        key = (nk, P, H, W, two_d)
         sizes = _BLOB_SIZES.get(key)
         if sizes is None:
             if len(_BLOB_SIZES) > 64:      # a new (n_all * k, P) nearly every mapped frame: keep the cache small
                 _BLOB_SIZES.clear()
-            sizes = _BLOB_SIZES[key] = (al(4 * max(nk, 1)), al(L.pings_spawn_plan_scratch_bytes(nk)),
-                                        al(L.pings_raster_geom_bytes(P, H, W)), al(L.pings_raster_image_bytes(H, W)))
+            geom_b = L.pings_raster2d_geom_bytes(P, H, W) if two_d else L.pings_raster_geom_bytes(P, H, W)
+            image_b = L.pings_raster2d_image_bytes(H, W) if two_d else L.pings_raster_image_bytes(H, W)
+            sizes = _BLOB_SIZES[key] = (al(4 * max(nk, 1)), al(L.pings_spawn_plan_scratch_bytes(nk)), al(geom_b),
+                                        al(image_b))
         blob = torch.empty(256 + sum(sizes), **u8)
         words_ptr = blob.data_ptr()                                              # [kept count, NaN-rotation flag]
         dest_ptr = words_ptr + 256
@@ -138,23 +146,38 @@ class _SpawnRaster(torch.autograd.Function):
         if M:                                               # frozen surrounding map behind the block (:267-281)
             xyz[nk:] = fz_xyz.detach()
             alpha[nk:] = fz_alpha.detach().reshape(M, 1)
-            scale[nk:] = fz_scale.detach()
+            if two_d:                                       # the frozen 2d_gs map keeps two scale columns
+                scale[nk:, :2] = fz_scale.detach()
+            else:
+                scale[nk:] = fz_scale.detach()
             rot[nk:] = fz_rot.detach()
             color[nk:] = fz_color.detach()
         # ---- rasteriser stage 1; its read-back is the frame's one synchronisation
         radii = torch.empty(P, dtype=torch.int32, device=dev)
-        o_color, o_depth, o_alpha = torch.empty(3, H, W, **f32), torch.empty(1, H, W, **f32), torch.empty(1, H, W, **f32)
-        o_normal = torch.empty(3, H, W, **f32) if surfel else None
-        per_g = torch.empty(P, **f32) if surfel else torch.empty(P, dtype=torch.int32, device=dev)
         aux_ptrs = (C.c_void_p * 5)(fc.n_vis_dev.data_ptr(), n_dev_ptr, words_ptr, words_ptr + 4,
                                     st.frozen_nan.data_ptr() if st.frozen_nan is not None else None)
         aux = (C.c_int32 * 5)()
         n_inst, fclass = C.c_int64(0), C.c_int32(1)
         ref = prep.ref()
-        _lib.check(L.pings_raster_preprocess_dyn(
-            ref, P, _lib.ptr(xyz), _lib.ptr(color), _lib.ptr(alpha), _lib.ptr(scale), _lib.ptr(rot), geom_ptr,
-            _lib.ptr(radii), words_ptr, nk, aux_ptrs, 5, aux, C.byref(n_inst), C.byref(fclass), stream),
-            "pings_raster_preprocess_dyn")
+        if two_d:
+            # the 2DGS kernels read [P,2] scales: the first two columns of the 3d_gs activation (:672-673)
+            scale2 = scale[:, :2].contiguous()
+            o_color, o_allmap = torch.empty(3, H, W, **f32), torch.empty(7, H, W, **f32)
+            o_normal = o_depth = o_alpha = per_g = None
+            _lib.check(L.pings_raster2d_preprocess(
+                ref, P, _lib.ptr(xyz), _lib.ptr(color), _lib.ptr(alpha), _lib.ptr(scale2), _lib.ptr(rot), geom_ptr,
+                _lib.ptr(radii), words_ptr, nk, aux_ptrs, 5, aux, C.byref(n_inst), stream),
+                "pings_raster2d_preprocess")
+        else:
+            scale2 = o_allmap = None
+            o_color, o_depth, o_alpha = torch.empty(3, H, W, **f32), torch.empty(1, H, W, **f32), \
+                torch.empty(1, H, W, **f32)
+            o_normal = torch.empty(3, H, W, **f32) if surfel else None
+            per_g = torch.empty(P, **f32) if surfel else torch.empty(P, dtype=torch.int32, device=dev)
+            _lib.check(L.pings_raster_preprocess_dyn(
+                ref, P, _lib.ptr(xyz), _lib.ptr(color), _lib.ptr(alpha), _lib.ptr(scale), _lib.ptr(rot), geom_ptr,
+                _lib.ptr(radii), words_ptr, nk, aux_ptrs, 5, aux, C.byref(n_inst), C.byref(fclass), stream),
+                "pings_raster_preprocess_dyn")
         _lib.note_sync("raster_instance_count")
         n_vis, n_sel, count, nan_spawn, nan_frozen = (int(v) for v in aux)
         fc.n_vis, fc.n_sel, fc.count, fc.k = n_vis, n_sel, count, k
@@ -170,26 +193,33 @@ class _SpawnRaster(torch.autograd.Function):
             raise SkipFrame("too few Gaussians")
         assert not (nan_spawn or nan_frozen), "NaN in rotation"     # :305-306
         # ---- rasteriser stage 2
-        binning = torch.empty(L.pings_raster_binning_bytes(I, H, W), **u8)
-        _lib.check(L.pings_raster_render(ref, P, I, geom_ptr, _lib.ptr(binning), image_ptr, _lib.ptr(o_color),
-                                         _lib.ptr(o_normal), _lib.ptr(o_depth), _lib.ptr(o_alpha), _lib.ptr(per_g),
-                                         fclass.value, stream), "pings_raster_render")
+        if two_d:
+            binning = torch.empty(L.pings_raster2d_binning_bytes(I, H, W), **u8)
+            _lib.check(L.pings_raster2d_render(ref, P, I, geom_ptr, _lib.ptr(binning), image_ptr, _lib.ptr(o_color),
+                                               _lib.ptr(o_allmap), stream), "pings_raster2d_render")
+        else:
+            binning = torch.empty(L.pings_raster_binning_bytes(I, H, W), **u8)
+            _lib.check(L.pings_raster_render(ref, P, I, geom_ptr, _lib.ptr(binning), image_ptr, _lib.ptr(o_color),
+                                             _lib.ptr(o_normal), _lib.ptr(o_depth), _lib.ptr(o_alpha),
+                                             _lib.ptr(per_g), fclass.value, stream), "pings_raster_render")
         ctx.st = st
         ctx.keep = (raws, quat, base, dist_ratio, blob, (dest_ptr, geom_ptr, image_ptr), xyz, color, alpha, scale, rot,
-                    binning, o_color, o_normal, o_depth, o_alpha)
+                    binning, o_color, o_normal, o_depth, o_alpha, scale2, o_allmap)
         ctx.dims = (P, I, nk, M, int(fclass.value), n_sel, count)
         ctx.has_pose = (theta is not None, rho is not None)
         ctx.prm = prm
         if M:
             radii_o = torch.cat((radii[:count], radii[nk:]))
-            per_g_o = torch.cat((per_g[:count], per_g[nk:]))
+            per_g_o = torch.cat((per_g[:count], per_g[nk:])) if per_g is not None else None
         else:
-            radii_o, per_g_o = radii[:count], per_g[:count]
+            radii_o, per_g_o = radii[:count], (per_g[:count] if per_g is not None else None)
         nsk = n_sel * k
         # the four images are returned as ALIASES of the tensors ctx.keep holds (see rasterizer._RasterizeGaussians:
         # output -> grad_fn -> ctx -> the same output object is a reference cycle only the cycle collector frees)
         alias = lambda t: None if t is None else t.detach()
-        outs = (alias(o_color), alias(o_normal), alias(o_depth), alias(o_alpha), radii_o, per_g_o, xyz[:count], scale[:count], rot[:count],
+        # 2DGS: the allmap takes the normal's place; `gaussian_scale` is the [:, :2] view of the activation block
+        outs = (alias(o_color), alias(o_allmap if two_d else o_normal), alias(o_depth), alias(o_alpha), radii_o,
+                per_g_o, xyz[:count], scale[:count, :2] if two_d else scale[:count], rot[:count],
                 alpha[:count], color[:count], alpha_all[:nsk], gfree[:count] if gfree is not None else None)
         ctx.mark_non_differentiable(*[o for o in (radii_o, per_g_o, outs[12]) if o is not None])
         ctx.set_materialize_grads(False)
@@ -203,7 +233,8 @@ class _SpawnRaster(torch.autograd.Function):
         st = ctx.st
         prep = st.prep
         (raws, quat, base, dist_ratio, _blob, (dest_ptr, geom_ptr, image_ptr), xyz, color, alpha, scale, rot,
-         binning, o_color, o_normal, o_depth, o_alpha) = ctx.keep
+         binning, o_color, o_normal, o_depth, o_alpha, scale2, o_allmap) = ctx.keep
+        two_d = prep.mode == _rast.MODE_2DGS
         P, I, nk, M, fclass, n_sel, count = ctx.dims
         dev = xyz.device
         stream = _lib.stream_ptr(dev)
@@ -220,7 +251,21 @@ class _SpawnRaster(torch.autograd.Function):
         base_ptr = gb.data_ptr()
         ptr_of = [base_ptr + 4 * o for o in offs]
         d_tau = gb[offs[6]:offs[6] + 6]
-        if any(g is not None for g in (g_color, g_normal, g_depth, g_alpha)):
+        if two_d and (g_color is not None or g_normal is not None):
+            # g_normal is the allmap's gradient here (see forward); scales [P,2] -> the block's first two columns
+            scratch = torch.empty(L.pings_raster2d_backward_bytes(P, I), dtype=torch.uint8, device=dev)
+            d_s2 = torch.empty(P, 2, **f32)
+            _lib.check(L.pings_raster2d_backward(
+                prep.ref(), P, I, _lib.ptr(scale2), _lib.ptr(rot), geom_ptr, _lib.ptr(binning), image_ptr,
+                _lib.ptr(g_color), _lib.ptr(g_normal), _lib.ptr(scratch), ptr_of[0], ptr_of[1], ptr_of[2], ptr_of[3],
+                _lib.ptr(d_s2), ptr_of[5], stream), "pings_raster2d_backward")
+            sc_g = view(4)
+            sc_g[:, :2] = d_s2
+            sc_g[:, 2] = 0.0
+            d_tau.zero_()
+        elif two_d:
+            gb.zero_()
+        elif any(g is not None for g in (g_color, g_normal, g_depth, g_alpha)):
             key = (P, I)
             nb = _BWD_BYTES.get(key)
             if nb is None:
@@ -239,7 +284,10 @@ class _SpawnRaster(torch.autograd.Function):
         # losses on the returned Gaussian tensors themselves (the mapper's regularisers) join the rasteriser's gradients
         for j, g in ((0, g_xyz), (4, g_scale), (5, g_rot), (3, g_galpha), (2, g_gcolor)):
             if g is not None:
-                view(j)[:count].add_(g.reshape(count, -1))
+                if j == 4 and two_d:
+                    view(j)[:count, :2].add_(g.reshape(count, 2))
+                else:
+                    view(j)[:count].add_(g.reshape(count, -1))
         vsp = st.viewspace
         if vsp is not None:                                 # gradient sink of the reference's API (:295-301)
             d_m2d = view(1)
@@ -263,7 +311,7 @@ class _SpawnRaster(torch.autograd.Function):
         if M:
             for j, col in enumerate((0, 3, 4, 5, 2)):
                 if need[7 + j]:
-                    fz[j] = view(col)[nk:]
+                    fz[j] = view(col)[nk:, :2] if (two_d and col == 4) else view(col)[nk:]
         return (*outs, d_theta, d_rho, *fz, None)
 
 

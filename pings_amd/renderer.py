@@ -71,8 +71,6 @@ def spawn_gaussians(neural_points_data: Dict,
     if not pos_all.is_cuda:
         raise _lib.PingsHipError("spawn_gaussians runs on the HIP device only (got CPU tensors); there is no CPU "
                                  "fallback — the CPU restatement lives in oracle/spawn_cpu.py (tests only)")
-    if gs_type == "2d_gs":
-        raise NotImplementedError("gs_type='2d_gs' is outside the PINGS hot path (gaussian_renderer/__init__.py:350)")
     base_all = d.get("color", None)
     geo_feat, col_feat = d["geo_feature"], d["color_feature"]
     res = float(d["resolution"])
@@ -131,9 +129,10 @@ def spawn_gaussians(neural_points_data: Dict,
             far = mag > 2.0 * res
             shifted_position = pos[far] + pick[far]
 
+    # 2d_gs keeps the first two columns of the 3d_gs activation (:672-673); the slice is differentiable
     return {
         "gaussian_xyz": sp.xyz,
-        "gaussian_scale": sp.scale,
+        "gaussian_scale": sp.scale[:, :2] if gs_type == "2d_gs" else sp.scale,
         "gaussian_rot": sp.rot,
         "gaussian_alpha": sp.alpha,
         "gaussian_color": sp.color,
@@ -175,6 +174,9 @@ def _settings(viewpoint_camera, gs_type, height, width, tanfovx, tanfovy, bg_col
                 torch.tensor(patch, dtype=torch.float32, device=device), patch)
         return _rast.SurfelGaussianRasterizer(_rast.SurfelRasterizationSettings(
             patch_bbox=pb, prcppoint=viewpoint_camera.prcppoint, config=cfg, **common))
+    if gs_type == "2d_gs":                                   # :167-181: no projmatrix_raw in this record
+        common.pop("projmatrix_raw")
+        return _rast.Surfel2DGaussianRasterizer(_rast.Surfel2DRasterizationSettings(**common))
     return _rast.GS3DGaussianRasterizer(_rast.GS3DRasterizationSettings(**common))
 
 
@@ -204,10 +206,7 @@ def render(viewpoint_camera,
            unit_scale_ratio: float = 0.2,
            ):
     """Render one view of the neural-point map (gaussian_renderer/__init__.py:27-466)."""
-    if gs_type == "2d_gs":
-        raise NotImplementedError("gs_type='2d_gs' is outside the PINGS hot path (no shipped config uses it; "
-                                  "gaussian_renderer/__init__.py:350)")
-    if gs_type not in ("gaussian_surfel", "3d_gs"):
+    if gs_type not in ("gaussian_surfel", "3d_gs", "2d_gs"):
         print("wrong gs type selected, use the default one 3d gs")  # :97
         gs_type = "3d_gs"
 
@@ -242,7 +241,7 @@ def render(viewpoint_camera,
                                     dtype, device, img_scale, z_far, min_visible_neural_point_ratio, verbose,
                                     replay_mode, dist_concat_on, view_concat_on, correct_exposure,
                                     correct_exposure_affine, learn_color_residual, d2n_on, gs_type, min_alpha,
-                                    displacement_range_ratio, max_scale_ratio, unit_scale_ratio)
+                                    displacement_range_ratio, max_scale_ratio, unit_scale_ratio, use_median_depth)
         except _core.LegacyFrame:
             pass                        # fewer than 10 selected neural points (:572): the path below handles it
     # ONE read-back for both counts the control flow needs: visible points (reference: `.item()` at :219) and rows
@@ -297,19 +296,42 @@ def render(viewpoint_camera,
     # one-synchronisation path folds the flag into the rasteriser's read-back; here it is a wait for the blend kernels)
     nan_flag = torch.isnan(rotations).any()
 
-    out = rasterizer(means3D=means3D, means2D=screenspace_points, colors_precomp=colors, opacities=opacity,
-                     scales=scales, rotations=rotations, theta=viewpoint_camera.cam_rot_delta,
-                     rho=viewpoint_camera.cam_trans_delta)
+    if gs_type == "2d_gs":             # the reference passes no pose tangent here (:351-358)
+        out = rasterizer(means3D=means3D, means2D=screenspace_points, colors_precomp=colors, opacities=opacity,
+                         scales=scales, rotations=rotations)
+    else:
+        out = rasterizer(means3D=means3D, means2D=screenspace_points, colors_precomp=colors, opacities=opacity,
+                         scales=scales, rotations=rotations, theta=viewpoint_camera.cam_rot_delta,
+                         rho=viewpoint_camera.cam_trans_delta)
     _lib.note_sync("nan_rotation_assert")
     assert not bool(nan_flag), "NaN in rotation"
     return _finish(results, out, screenspace_points, viewpoint_camera, gs_type, d2n_on, img_scale, min_alpha,
-                   correct_exposure, correct_exposure_affine)
+                   correct_exposure, correct_exposure_affine, use_median_depth)
 
 
 def _finish(results, out, screenspace_points, viewpoint_camera, gs_type, d2n_on, img_scale, min_alpha,
-            correct_exposure, correct_exposure_affine):
+            correct_exposure, correct_exposure_affine, use_median_depth=False):
     """Image-space tail of `render` (:318-466), shared by both paths."""
-    if gs_type == "gaussian_surfel":
+    if gs_type == "2d_gs":             # :360-409
+        rendered_image, radii, allmap = out
+        rendered_image = torch.nan_to_num(rendered_image, 0, 0)
+        rendered_alpha = allmap[1:2]
+        alpha_detached = rendered_alpha.detach()
+        mask_vis = alpha_detached > min_alpha
+        rendered_normal = torch.nan_to_num(allmap[2:5], 0, 0)
+        depth_median = torch.nan_to_num(allmap[5:6], 0, 0)
+        depth_expected = torch.nan_to_num(allmap[0:1], 0, 0)
+        # :384 divides in place through boolean-mask indexing (host synchronisations); the same values and gradients
+        # without leaving the stream: depth / alpha where the mask holds, the map as it is elsewhere
+        depth_expected = torch.where(mask_vis, depth_expected / alpha_detached.clamp_min(1e-30), depth_expected)
+        rendered_depth = depth_median if use_median_depth else depth_expected
+        d2n = None
+        if d2n_on:
+            d2n = depth2normal(rendered_depth, mask_vis, viewpoint_camera, img_scale=img_scale, weight=alpha_detached)
+        results.update({"rend_alpha": rendered_alpha, "rend_normal": rendered_normal, "rend_dist": allmap[6:7],
+                        "surf_depth": rendered_depth, "surf_normal": d2n, "viewspace_points": screenspace_points,
+                        "visibility_filter": radii > 0, "radii": radii})
+    elif gs_type == "gaussian_surfel":
         rendered_image, rendered_normal, rendered_depth, rendered_alpha, radii, contributions = out
         alpha_detached = rendered_alpha.detach()
         mask_vis = alpha_detached > min_alpha
@@ -369,7 +391,7 @@ def _one_sync_supported(decoders, gs_type) -> bool:
 def _render_one_sync(cam, rasterizer, d, decoders, gaussians, visible, dtype, device, img_scale, z_far, min_ratio,
                      verbose, replay_mode, dist_concat_on, view_concat_on, correct_exposure, correct_exposure_affine,
                      learn_color_residual, d2n_on, gs_type, min_alpha, displacement_range_ratio, max_scale_ratio,
-                     unit_scale_ratio):
+                     unit_scale_ratio, use_median_depth=False):
     """`render` from `markVisible` on with every count left on the device until the rasteriser's read-back
     (render_core.py).  Same results as the legacy path bit for bit (tests/test_render.py)."""
     pos_all, quat_all = d["position"], d["orientation"]
@@ -412,7 +434,8 @@ def _render_one_sync(cam, rasterizer, d, decoders, gaussians, visible, dtype, de
         st.frozen_nan = torch.isnan(frozen[3]).any().to(torch.int32).reshape(1)
     st.viewspace = None
     try:
-        out = _core.spawn_and_rasterise(raws, cam.cam_rot_delta, cam.cam_trans_delta, frozen, st)
+        pose = (None, None) if gs_type == "2d_gs" else (cam.cam_rot_delta, cam.cam_trans_delta)   # :351-358: no pose
+        out = _core.spawn_and_rasterise(raws, pose[0], pose[1], frozen, st)
     except _core.SkipFrame as e:
         if verbose:
             print("[Render] {}, skip this frame {}".format(e, cam.uid))
@@ -428,7 +451,9 @@ def _render_one_sync(cam, rasterizer, d, decoders, gaussians, visible, dtype, de
                "visible_neural_point_ratio": 1.0 * fc.n_vis / n_all}
     if gs_type == "gaussian_surfel":
         raster_out = (o_color, o_normal, o_depth, o_alpha, radii, per_g)
+    elif gs_type == "2d_gs":
+        raster_out = (o_color, radii, o_normal)     # the node returns the allmap in the normal's place
     else:
         raster_out = (o_color, radii, o_depth, o_alpha, per_g)
     return _finish(results, raster_out, screenspace_points, cam, gs_type, d2n_on, img_scale, min_alpha,
-                   correct_exposure, correct_exposure_affine)
+                   correct_exposure, correct_exposure_affine, use_median_depth)
