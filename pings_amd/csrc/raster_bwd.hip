@@ -160,6 +160,9 @@ __global__ __launch_bounds__(BLOCK / PPL, PPL == 4 ? 3 : 4) void blend_bwd_kerne
   }
   __syncthreads();
   const int max_last = (int)sMax;
+  // the 0.5 of the cov2D xx / yy gradient terms, applied to the reduced sums (lane < 16 holds slot red_slot)
+  const int red_slot = ((lane & 1) << 3) | ((lane & 2) << 1) | (lane >> 2);
+  const float red_scale = (red_slot == G_CONX || red_slot == G_CONZ) ? 0.5f : 1.0f;
 
   const int nbatch = ceil_div(max_last, BATCH);
   for (int b = nbatch - 1; b >= 0; --b) {
@@ -246,10 +249,21 @@ __global__ __launch_bounds__(BLOCK / PPL, PPL == 4 ? 3 : 4) void blend_bwd_kerne
       }
       if (!__any(any_v)) continue;
 
+      // The first pixel set assigns the 16 accumulators, the others add to them (no zeroing, no 0 + x per record).
+      // Changes against the forward-identical decisions below affect only the gradient sums, by rounding.
       float v[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) v[q] = 0.f;
+      if (MODE != MODE_SURFEL) v[G_NX] = v[G_NY] = v[G_NZ] = v[G_Q] = v[G_ZLO] = v[G_ZHI] = 0.f;   // no surfel terms
       const float zlo = ca.w - cb.w, zhi = ca.w + cb.w;
+      const float zlo_m = fminf(zlo, zhi);   // med3(d, min(lo, hi), hi) == fminf(fmaxf(d, lo), hi) for non-NaN d
+      // per-record products shared by the pixel sets of an x half / a row: q = conic . (dx, dy) as two adds
+      float cxdx[NXH], cydy[PPL], czdy[PPL];
+#pragma unroll
+      for (int h = 0; h < NXH; ++h) cxdx[h] = cb.x * dxv[h];
+#pragma unroll
+      for (int k = 0; k < PPL; ++k) {
+        cydy[k] = cb.y * dyv[k];
+        czdy[k] = cb.z * dyv[k];
+      }
 #pragma unroll
       for (int k = 0; k < PPL; ++k) {
         // gradient accumulation only (the alpha / validity decisions were taken above, un-contracted, exactly as in
@@ -257,20 +271,24 @@ __global__ __launch_bounds__(BLOCK / PPL, PPL == 4 ? 3 : 4) void blend_bwd_kerne
 #pragma clang fp contract(fast)
         // (a uniform `if (!__any(valid[k])) continue;` per pixel set here: 0.346 -> 0.399 ms — four more branches per
         // record cost more than the skipped sets save)
-        const float dy = dyv[k];
-        const float dx = dxv[PPL == 4 ? (k & 1) : 0], rx = rxv[PPL == 4 ? (k & 1) : 0];
-        const float one_m = 1.0f - alpha[k];
+        const bool first = k == 0;
+        auto acc = [&](int q, float x) { v[q] = first ? x : v[q] + x; };
+        const int h = PPL == 4 ? (k & 1) : 0;
+        const float rx = rxv[h];
+        // Validity folded into alpha: an invalid pixel blends av = 0, so 1 - av = 1, rcp(1) = 1 exactly and Tn == T
+        // bit for bit; w = av * Tn and T = Tn need no select.  Valid pixels see the same operations as before.
+        const float av = valid[k] ? alpha[k] : 0.f;
+        const float one_m = 1.0f - av;
         const float inv_one_m = __builtin_amdgcn_rcpf(one_m);  // 1-ulp reciprocal: alpha <= 0.99
         const float Tn = T[k] * inv_one_m;
-        const float w = valid[k] ? alpha[k] * Tn : 0.f;
+        const float w = av * Tn;
         // dL/dalpha needs sum_ch (feature_ch - B_ch) g_ch with B the normalised blend of the records behind.  Both
         // the blend recurrence and the dot product are linear, so ONE scalar per pixel is tracked instead of the
         // eight channels:  s = g . feature,  dLda = s - Bs,  Bs <- Bs + alpha (s - Bs).
         float sdot = (cc.x * gC0[k] + cc.y * gC1[k]) + cc.z * gC2[k];
-        const float av = valid[k] ? alpha[k] : 0.f;  // only contributing lanes enter the blend
-        v[G_R] = fmaf(gC0[k], w, v[G_R]);
-        v[G_G] = fmaf(gC1[k], w, v[G_G]);
-        v[G_B] = fmaf(gC2[k], w, v[G_B]);
+        acc(G_R, gC0[k] * w);
+        acc(G_G, gC1[k] * w);
+        acc(G_B, gC2[k] * w);
         if (MODE == MODE_SURFEL) {
           sdot += (cn.x * gN0[k] + cn.y * gN1[k]) + cn.z * gN2[k];
           // per-pixel depth of this surfel
@@ -278,48 +296,51 @@ __global__ __launch_bounds__(BLOCK / PPL, PPL == 4 ? 3 : 4) void blend_bwd_kerne
           const bool hit = den < -DEN_EPS;
           const float inv_den = __builtin_amdgcn_rcpf(den);
           const float d0 = hit ? cc.w * inv_den : ca.w;
-          const float d = fminf(fmaxf(d0, zlo), zhi);
+          const float d = __builtin_amdgcn_fmed3f(d0, zlo_m, zhi);
           sdot = fmaf(d, gD[k], sdot);
           const float gd = gD[k] * w;
           const bool lo = d0 < zlo, hi = d0 > zhi;
           const bool mid = !lo && !hi;
-          v[G_ZLO] += lo ? gd : 0.f;
-          v[G_ZHI] += hi ? gd : 0.f;
+          acc(G_ZLO, lo ? gd : 0.f);
+          acc(G_ZHI, hi ? gd : 0.f);
           const float gq = (mid && hit) ? gd * inv_den : 0.f;
-          v[G_Q] += gq;
-          v[G_PZ] += (mid && !hit) ? gd : 0.f;
+          acc(G_Q, gq);
+          acc(G_PZ, (mid && !hit) ? gd : 0.f);
           const float gden = -gq * d0;  // = -gd * d0 / den on the unclamped ray hit, else 0
-          v[G_NX] += fmaf(gden, rx, gN0[k] * w);
-          v[G_NY] += fmaf(gden, ry[k], gN1[k] * w);
-          v[G_NZ] += gN2[k] * w + gden;
+          // two multiply-adds per normal component instead of multiply, multiply-add and add
+          v[G_NX] = fmaf(gden, rx, first ? gN0[k] * w : fmaf(gN0[k], w, v[G_NX]));
+          v[G_NY] = fmaf(gden, ry[k], first ? gN1[k] * w : fmaf(gN1[k], w, v[G_NY]));
+          v[G_NZ] = fmaf(gN2[k], w, first ? gden : v[G_NZ] + gden);
         } else {
           sdot = fmaf(ca.w, gD[k], sdot);
-          v[G_PZ] = fmaf(gD[k], w, v[G_PZ]);
+          acc(G_PZ, gD[k] * w);
         }
         float dLda = sdot - Bs[k];
         Bs[k] = fmaf(av, dLda, Bs[k]);
         dLda = fmaf(dLda, Tn, coefT[k] * inv_one_m);
         // alpha = min(0.99, opacity * G): no gradient through the clamp when it is active
         dLda = (valid[k] && raw[k] <= ALPHA_MAX) ? dLda : 0.f;
-        v[G_OPAC] = fmaf(Gs[k], dLda, v[G_OPAC]);
+        acc(G_OPAC, Gs[k] * dLda);
         const float dLp = raw[k] * dLda;  // dL/dpower = G * (opacity * dL/dalpha)
         // q = conic . d.  d power / d mean = -q, and d power / d cov2D = 0.5 q q^T: accumulating the
         // gradient w.r.t. the 2-D COVARIANCE here (instead of w.r.t. the conic, to be pushed through
         // -conic G conic afterwards) keeps every per-pixel term O(1); the conic form sums d d^T terms
         // of order 1e6 that must cancel to O(1) for large anisotropic footprints, which fp32 cannot do.
-        const float qx = cb.x * dx + cb.y * dy, qy = cb.y * dx + cb.z * dy;
-        v[G_MX] -= dLp * qx;
-        v[G_MY] -= dLp * qy;
-        v[G_CONX] += 0.5f * qx * qx * dLp;
-        v[G_CONY] += qx * qy * dLp;
-        v[G_CONZ] += 0.5f * qy * qy * dLp;
-        T[k] = valid[k] ? Tn : T[k];
+        // The 0.5 of the xx / yy terms is applied once to the reduced sums (exact: a power of two).
+        const float qx = cxdx[h] + cydy[k], qy = pxyv[h] + czdy[k];
+        const float ux = dLp * qx, uy = dLp * qy;
+        acc(G_MX, -ux);
+        acc(G_MY, -uy);
+        acc(G_CONX, ux * qx);
+        acc(G_CONY, ux * qy);
+        acc(G_CONZ, uy * qy);
+        T[k] = Tn;
       }
-      const float tot = wave_reduce16(v, lane);
+      const float tot = wave_reduce16(v, lane) * red_scale;
       // (one-wave kernel, PPL 4: storing the 64-byte row straight to global memory from here instead of through the
       // LDS batch below was measured 5 % SLOWER: a scattered 16-lane store per record in the hot loop)
       if (lane < 16)
-        reinterpret_cast<float*>(&sG[wave][j][0])[((lane & 1) << 3) | ((lane & 2) << 1) | (lane >> 2)] = tot;
+        reinterpret_cast<float*>(&sG[wave][j][0])[red_slot] = tot;
     }
     __syncthreads();
     for (int e = tid; e < n * 4; e += NT) {

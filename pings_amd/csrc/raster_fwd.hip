@@ -1804,16 +1804,23 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
   const int todo = (int)(range.y - range.x);
   float T[PPL], C0[PPL], C1[PPL], C2[PPL], N0[PPL], N1[PPL], N2[PPL], D[PPL];
   uint32_t last[PPL];
-  bool done[PPL], inside[PPL];
-  bool all_done_lane = true;
+  bool inside[PPL];
+  // A pixel that has stopped (or lies outside the image) is "done".  Instead of a boolean that the compiler keeps as a
+  // 0/1 VGPR and turns back into a lane mask every record (v_and + v_cmp per pixel), the state lives in the alpha
+  // threshold of the validity test: ALPHA_MIN while blending, DONE_AMIN (> ALPHA_MAX) once done, so `alpha >= amin`
+  // is exactly `!done && alpha >= ALPHA_MIN`.  The wave's count of pixels not yet done is kept in a scalar register
+  // (a pixel stops at most once), which replaces the per-record all-done vote.
+  constexpr float DONE_AMIN = 2.0f;
+  float amin[PPL];
+  int live_px = 0;   // wave-uniform
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
     T[k] = 1.0f;
     C0[k] = C1[k] = C2[k] = N0[k] = N1[k] = N2[k] = D[k] = 0.f;
     last[k] = 0;
     inside[k] = pix_x[k & 1] < p.W && pix_y[k >> 1] < p.H;
-    done[k] = !inside[k];
-    all_done_lane = all_done_lane && done[k];
+    amin[k] = inside[k] ? ALPHA_MIN : DONE_AMIN;
+    live_px += __popcll(__ballot(inside[k]));
   }
 
   // two-stage fetch pipeline (list entry -> Gaussian id | id -> whole record), see blend_fwd_seg_kernel
@@ -1837,14 +1844,14 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
       if (MODE == MODE_SURFEL) f_d = rec[4 * (size_t)f_g + 3];
     }
   };
-  if (todo > 0 && !__all(all_done_lane)) {
+  if (todo > 0 && live_px > 0) {
     fetch_ids(0);
     fetch_records();
     if (64 < todo) fetch_ids(64); else n_ok = false;
   }
 
   for (int base = 0; base < todo; base += 64) {
-    if (__all(all_done_lane)) break;
+    if (live_px == 0) break;
     const uint32_t slot = f_slot;
     const float4 ra = f_a, rb = f_b, rc = f_c, rd = f_d;
     const bool ok = f_ok;
@@ -1876,71 +1883,76 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
     // the dominant contributor of) stays in a register until the group is done, then ONE transposed reduce-scatter
     // (raster_common.hpp: wave_reduce16, ~55 vector ops for 16 sums) replaces sixteen 7-step DPP reductions and their
     // dependent chains.  The unrolled group keeps the register indices static.
-    bool stop_all = false;
-    for (int j0 = 0; j0 < n && !stop_all; j0 += 16) {
+    // Each record's sums are assigned once, after its branches: a conditional store into ws[] made the compiler carry
+    // the whole zero-initialised array through every record's control flow (~12 v_mov per record).
+    for (int j0 = 0; j0 < n && live_px > 0; j0 += 16) {
       float ws[16], wc[16];
-#pragma unroll
-      for (int jj = 0; jj < 16; ++jj) { ws[jj] = 0.f; wc[jj] = 0.f; }
 #pragma unroll
       for (int jj = 0; jj < 16; ++jj) {
         const int j = j0 + jj;
-        if (j >= n || stop_all) continue;   // wave-uniform
-        const float4 a = sA[j], b = sB[j], c = sC[j];
-        float4 nn = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (MODE == MODE_SURFEL) nn = sD[j];
-        float dxv[2], p0v[2], pxyv[2];
+        float wsum = 0.f;
+        uint32_t touched = 0;
+        if (j < n && live_px > 0) {   // wave-uniform
+          const float4 a = sA[j], b = sB[j], c = sC[j];
+          float4 nn = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (MODE == MODE_SURFEL) nn = sD[j];
+          float dxv[2], p0v[2], pxyv[2];
 #pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          dxv[h] = a.x - pixf_x[h];
-          p0v[h] = -0.5f * (b.x * dxv[h] * dxv[h]);
-          pxyv[h] = b.y * dxv[h];
-        }
-        float alpha[PPL], test_T[PPL];
-        bool contrib[PPL];
-        bool any_c = false;
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) {
-          const float dy = a.y - pixf_y[k >> 1];
-          const float power = (p0v[k & 1] - 0.5f * (b.z * dy * dy)) - pxyv[k & 1] * dy;
-          alpha[k] = fminf(ALPHA_MAX, a.z * __expf(power));
-          const bool valid = !done[k] && (power <= 0.0f) && (alpha[k] >= ALPHA_MIN);
-          test_T[k] = T[k] * (1.0f - alpha[k]);
-          const bool stop = valid && (test_T[k] < T_EPS);
-          contrib[k] = valid && !stop;
-          done[k] = done[k] || stop;
-          any_c = any_c || contrib[k];
-        }
-        if (__any(any_c)) {
-          float wsum = 0.f;
-          uint32_t touched = 0;
-          const uint32_t e1 = (uint32_t)(sE[j] + 1);
+          for (int h = 0; h < 2; ++h) {
+            dxv[h] = a.x - pixf_x[h];
+            p0v[h] = -0.5f * (b.x * dxv[h] * dxv[h]);
+            pxyv[h] = b.y * dxv[h];
+          }
+          float alpha[PPL], test_T[PPL];
+          bool contrib[PPL];
+          bool any_c = false;
+          int n_stop = 0;
 #pragma unroll
           for (int k = 0; k < PPL; ++k) {
-            const float w = contrib[k] ? alpha[k] * T[k] : 0.f;
-            C0[k] = fmaf(c.x, w, C0[k]);
-            C1[k] = fmaf(c.y, w, C1[k]);
-            C2[k] = fmaf(c.z, w, C2[k]);
-            if (MODE == MODE_SURFEL) {
-              const float den = (nn.x * rx[k & 1] + nn.y * ry[k >> 1]) + nn.z;
-              float d = den < -DEN_EPS ? c.w * __builtin_amdgcn_rcpf(den) : a.w;
-              d = fminf(fmaxf(d, a.w - b.w), a.w + b.w);
-              N0[k] = fmaf(nn.x, w, N0[k]);
-              N1[k] = fmaf(nn.y, w, N1[k]);
-              N2[k] = fmaf(nn.z, w, N2[k]);
-              D[k] = fmaf(d, w, D[k]);
-            } else {
-              D[k] = fmaf(a.w, w, D[k]);
-              touched += (contrib[k] && test_T[k] > 0.5f) ? 1u : 0u;
-            }
-            T[k] = contrib[k] ? test_T[k] : T[k];
-            last[k] = contrib[k] ? e1 : last[k];
-            wsum += w;
+            const float dy = a.y - pixf_y[k >> 1];
+            const float power = (p0v[k & 1] - 0.5f * (b.z * dy * dy)) - pxyv[k & 1] * dy;
+            alpha[k] = fminf(ALPHA_MAX, a.z * __expf(power));
+            const bool valid = (power <= 0.0f) && (alpha[k] >= amin[k]);   // amin folds in !done
+            test_T[k] = T[k] * (1.0f - alpha[k]);
+            const bool lt = test_T[k] < T_EPS;
+            const bool stop = valid && lt;
+            contrib[k] = valid && !lt;
+            amin[k] = stop ? DONE_AMIN : amin[k];
+            n_stop += __popcll(__ballot(stop));
+            any_c = any_c || contrib[k];
           }
-          ws[jj] = wsum;
-          if (MODE == MODE_3DGS) wc[jj] = (float)touched;   // <= 4 per lane, <= 256 per record: exact in fp32
+          live_px -= n_stop;
+          if (__any(any_c)) {
+            const uint32_t e1 = (uint32_t)(sE[j] + 1);
+            // depth clamp as one v_med3: fminf(fmaxf(d, lo), hi) == med3(d, min(lo, hi), hi) for every non-NaN d
+            // (lo > hi clamps to hi either way), and d is never NaN here
+            const float zhi = a.w + b.w, zlo = fminf(a.w - b.w, zhi);
+#pragma unroll
+            for (int k = 0; k < PPL; ++k) {
+              const float w = contrib[k] ? alpha[k] * T[k] : 0.f;
+              C0[k] = fmaf(c.x, w, C0[k]);
+              C1[k] = fmaf(c.y, w, C1[k]);
+              C2[k] = fmaf(c.z, w, C2[k]);
+              if (MODE == MODE_SURFEL) {
+                const float den = (nn.x * rx[k & 1] + nn.y * ry[k >> 1]) + nn.z;
+                const float d0 = den < -DEN_EPS ? c.w * __builtin_amdgcn_rcpf(den) : a.w;
+                const float d = __builtin_amdgcn_fmed3f(d0, zlo, zhi);
+                N0[k] = fmaf(nn.x, w, N0[k]);
+                N1[k] = fmaf(nn.y, w, N1[k]);
+                N2[k] = fmaf(nn.z, w, N2[k]);
+                D[k] = fmaf(d, w, D[k]);
+              } else {
+                D[k] = fmaf(a.w, w, D[k]);
+                touched += (contrib[k] && test_T[k] > 0.5f) ? 1u : 0u;
+              }
+              T[k] = contrib[k] ? test_T[k] : T[k];
+              last[k] = contrib[k] ? e1 : last[k];
+              wsum = k == 0 ? w : wsum + w;   // w >= +0: the same bits as 0.f + w
+            }
+          }
         }
-        all_done_lane = (done[0] && done[1]) && (done[2] && done[3]);
-        stop_all = __all(all_done_lane);
+        ws[jj] = wsum;
+        wc[jj] = (float)touched;   // 3DGS: <= 4 per lane, <= 256 per record: exact in fp32
       }
       // lane l of every 16-lane row ends with the total of slot 8*(l&1) + 4*((l>>1)&1) + ((l>>2)&3)
       const int slot16 = 8 * (lane & 1) + 4 * ((lane >> 1) & 1) + ((lane >> 2) & 3);
