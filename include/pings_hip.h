@@ -804,4 +804,71 @@ PINGS_API int pings_reg_solve(const float* normal_eq, float lm_lambda, double* T
 PINGS_API int pings_reg_solve_checked(const float* normal_eq, float lm_lambda, double* T_out, double* t_out,
                                       int32_t* status_dev, int32_t* status_host, void* stream);
 
+/* ------------------------------------------------------ Gaussian-space loss block (csrc/gauss_loss.hip)
+ * The mapper's opacity, opacity-entropy, isotropy, area, SDF-consistency, SDF-normal-consistency and invalid-opacity
+ * terms (utils/mapper.py:1331-1483) with every count on the device.  One argument block for all entry points; the
+ * caller owns every buffer (pings_amd/gaussian_losses.py carves them from one allocation per direction).  Rows past
+ * the device sample count S (meta[1]) exist in the capacity-sized buffers and are never read as live.
+ *   select     constraint mask, opacity sums, a uniform sample of S = min(count, cap) constrained Gaussians (0 when
+ *              count <= 10) as idx[0..S) in ascending index order, or the injected indices
+ *   prepare    normals, the (1+R)*cap query rows (unshifted block first) and their labels
+ *   (the caller runs pings_sdf_forward on the query rows into sdf / grad / nn and the neighbour lists)
+ *   reduce     valid mask and the seven losses; counts[5] = #alpha_all < min_alpha, constraint count, S, valid rows,
+ *              invalid samples (float64, exact integers)
+ *   backward_rows     d sdf, d dS/dx and d normal per query row from the upstream g[7]
+ *   (the caller runs pings_sdf_backward / pings_sdf_double_backward and pings_sdf_hvp_x into dq)
+ *   backward_scatter  dense d_xyz / d_rot / d_scale / d_alpha (zeroed by the caller) and d_alpha_all
+ * flags: 1 opacity, 2 opacity entropy, 4 isotropy, 8 area, 16 SDF terms. */
+typedef struct pings_gauss_loss_args {
+  int64_t P, Na, cap;            /* local Gaussians, alpha_all elements, sample capacity (bs * gaussian_bs_ratio) */
+  int32_t R, ncols, scale_cols;  /* shift count; scale columns used (2 | 3); row stride of gaussian_scale         */
+  int32_t flags;
+  float min_alpha, contrib_thr, shift_range, grad_min, grad_max, inv_voxel_pow;
+  int64_t n_inject;              /* -1: draw from seed; else the number of injected indices                       */
+  const float* alpha_all;        /* [Na]                                                                          */
+  const uint8_t* visible;        /* [P] local visibility                                                          */
+  const float* contrib;          /* [P] or NULL                                                                   */
+  const uint8_t* free_mask;      /* [P] or NULL                                                                   */
+  const float *xyz, *rot, *scale, *alpha;   /* [P,3] [P,4] [P,scale_cols] [P]                                     */
+  const int64_t* seed;           /* device word: key seed                                                         */
+  const int64_t* inject_idx;     /* [n_inject] distinct indices, or NULL                                          */
+  const float* randn;            /* [R, cap] standard normal draws                                                */
+  uint32_t* keys;                /* [P]                                                                           */
+  double* part;                  /* [256 * 4]                                                                     */
+  int32_t* meta;                 /* [8]: count, S, n below min_alpha, n valid, n invalid                           */
+  int32_t* idx;                  /* [cap]                                                                         */
+  float *normal, *queries, *label;          /* [cap,3] [(1+R)cap,3] [(1+R)cap]                                    */
+  float *sdf, *grad;             /* [(1+R)cap] [(1+R)cap,3]   (pings_sdf_forward outputs)                          */
+  int64_t* nn;                   /* [(1+R)cap]                                                                    */
+  uint8_t* valid;                /* [(1+R)cap]                                                                    */
+  float* losses;                 /* [7]                                                                           */
+  double* counts;                /* [5]                                                                           */
+  const float* g;                /* [7] upstream gradient of the losses                                           */
+  float *ds, *v, *dn, *dq;       /* [(1+R)cap] [(1+R)cap,3] x3                                                    */
+  float *d_xyz, *d_rot, *d_scale, *d_alpha, *d_alpha_all;
+} pings_gauss_loss_args;
+PINGS_API int pings_gauss_loss_select(const pings_gauss_loss_args* a, void* stream);
+PINGS_API int pings_gauss_loss_prepare(const pings_gauss_loss_args* a, void* stream);
+PINGS_API int pings_gauss_loss_reduce(const pings_gauss_loss_args* a, void* stream);
+PINGS_API int pings_gauss_loss_backward_rows(const pings_gauss_loss_args* a, void* stream);
+PINGS_API int pings_gauss_loss_backward_scatter(const pings_gauss_loss_args* a, void* stream);
+
+/* Query gradient of the fused SDF's second order: out[b] = grad_x[b] * ds[b] + H_S(x_b) v[b] for the per-neighbour
+ * decoder (weighted_first = 0), with the neighbour lists of pings_sdf_forward (idx, gidx).  H_S is the Hessian of
+ * S(x) = sum_m w_m(x) scale MLP([f_m, R_m^T (x - p_m)]) with relu'' = 0.  grad_x / ds may be NULL (term omitted). */
+typedef struct pings_sdf_hvp_args {
+  const float *W1, *b1, *W2, *b2;
+  int32_t H, F;
+  float scale;
+  int32_t after_pgo;
+  const float *features, *points, *orientations, *gpoints;
+  const float* queries;
+  int64_t B;
+  int32_t nnk;
+  const int64_t *idx, *gidx;
+  const float *v, *ds, *grad_x;
+  float* out;
+} pings_sdf_hvp_args;
+PINGS_API int pings_sdf_hvp_x(const pings_sdf_hvp_args* a, void* stream);
+
 #endif /* PINGS_HIP_H_ */
