@@ -42,7 +42,10 @@ struct BParams {
 
 constexpr int BATCH = 64;
 // blend_bwd_scan_kernel: tiles whose largest per-pixel contributor count reaches the threshold get four waves per
-// quadrant (PINGS_BWD_LONG overrides the threshold, 0 = never); at most LONG_TILES_MAX tiles per frame.  C3 street
+// quadrant (PINGS_BWD_LONG overrides the threshold, 0 = never); at most LONG_TILES_MAX tiles per frame, taken as whole
+// bins of tile_order_kernel (work / 16, clamped to 1023) from the top down, so that the set of split tiles depends on the
+// per-tile work alone — when the bins at or above the threshold hold more than the cap, the lowest of them stay unsplit,
+// and a threshold above 16,368 splits nothing.  C3 street
 // sweep (r03, kernel ms): never 0.72, 256 0.65, 768 0.59, 2048 0.535, 3072 0.53, 4096 0.52, 8192 0.57 — the split
 // costs four queue walks and two barriers per chunk, so only the lists that set the kernel's duration should pay it.
 constexpr uint32_t LONG_TILES_MAX = 2048;

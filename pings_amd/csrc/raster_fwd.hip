@@ -883,11 +883,22 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* __rest
   hist[1023 - tid] = excl;   // hist[bin] = first output position of the bin
   __syncthreads();
   for (int t = tid; t < num_tiles; t += 1024) order[atomicAdd(&hist[min(work[t] >> 4, 1023u)], 1u)] = (uint32_t)t;
-  // tiles with work >= long_thr (a multiple of 16: whole bins) are the first entries of the order: their number
-  if (n_long && tid == 0) {
-    const uint32_t bin = min(long_thr >> 4, 1023u);
-    const uint32_t cnt = bin == 0u ? (uint32_t)num_tiles : base[1023 - bin];   // inclusive count of the bins >= bin
-    *n_long = min(cnt, long_max);
+  // tiles with work >= long_thr (a multiple of 16: whole bins) are the first entries of the order: their number.
+  // The order WITHIN a bin is the arrival order of the LDS atomics above, so a cap that cut through a bin would make
+  // the set of tiles the backward splits depend on timing.  The cap therefore takes whole bins only: the longest
+  // prefix of bins (from the top, down to the threshold's) whose tiles number at most long_max — if the top bin alone
+  // holds more, nothing is split.  A threshold above the top bin (work >> 4 is clamped to 1023) splits nothing either.
+  if (n_long) {
+    const uint32_t bin = long_thr >> 4;
+    if (bin > 1023u) {
+      if (tid == 0) *n_long = 0u;
+    } else {
+      // base[k] = inclusive count of bins 1023 .. 1023 - k, non-decreasing in k: exactly one thread writes
+      const uint32_t kmax = 1023u - bin;
+      const uint32_t k = (uint32_t)tid;
+      if (k <= kmax && base[k] <= long_max && (k == kmax || base[k + 1] > long_max)) *n_long = base[k];
+      if (tid == 0 && base[0] > long_max) *n_long = 0u;
+    }
   }
 }
 

@@ -1020,6 +1020,13 @@ def test_long_lists_blended_in_parallel_segments(mode, monkeypatch):
         assert rel_err(a, b) <= 2e-4
     o, *_ = _oracle(sc, torch.float64, mode, False)
     assert rel_err(out_s[0], o["color"]) <= 1e-4
+    # ... and the segmented run's gradients pass the fp64 oracle's gate on their own (same forced segments)
+    monkeypatch.setenv("PINGS_BLEND_SEG", "64")
+    monkeypatch.setenv("PINGS_BLEND_SEG_REUSE", "1")
+    _, names, ref64, ups = _oracle_grads(sc, torch.float64, mode, False)
+    _, _, ref32, _ = _oracle_grads(sc, torch.float32, mode, False)
+    _, got, _ = _hip_grads(sc, mode, False, ups)
+    _assert_grad_gate(names, got, ref64, ref32, f"segmented {mode}", flips_allowed=True)
 
 
 @pytest.mark.gpu
@@ -1058,7 +1065,11 @@ def test_long_tiles_share_their_quadrants_between_four_waves(mode, monkeypatch):
     work = nc.view(H // 16, 16, W // 16, 16).permute(0, 2, 1, 3).reshape(-1, 256).max(1).values
     assert int(work.min()) >= 16 and int(work.max()) > 4 * 64, (int(work.min()), int(work.max()))
     median = int(work.float().median())
+    _, names, ref64, ups = _oracle_grads(sc, torch.float64, mode, False)
+    _, _, ref32, _ = _oracle_grads(sc, torch.float32, mode, False)
     for thr in ("16", str(median)):
         g_four, _ = run(thr)
         for a, b in zip(g_four, g_one):
             assert rel_err(a, b) <= 1e-5, thr
+        _, got, _ = _hip_grads(sc, mode, False, ups)      # (same threshold and kernels as run(thr))
+        _assert_grad_gate(names, got, ref64, ref32, f"four-wave split {mode} threshold {thr}", flips_allowed=True)
