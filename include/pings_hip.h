@@ -871,4 +871,46 @@ typedef struct pings_sdf_hvp_args {
 } pings_sdf_hvp_args;
 PINGS_API int pings_sdf_hvp_x(const pings_sdf_hvp_args* a, void* stream);
 
+/* ------------------------------------------------------ SDF-sample loss block (csrc/sdf_loss.hip)
+ * The mapper's BCE, Eikonal and colour terms over one SDF sample batch (utils/mapper.py:836-930, 1493-1544) with the
+ * two subset counts on the device.  One argument block for all entry points; the caller owns every buffer
+ * (pings_amd/sdf_losses.py).  Sizes depend on B and d only: the Eikonal rows live in a capacity cap = ceil(B/d)
+ * buffer whose rows past the device count meta[0] are padding (idx -1, query = coord[0]) and get zero gradient.
+ *   select     Eikonal mask |label| < eik_band, the stable rank of each masked row, rows of rank % d == 0 compacted
+ *              in row order into idx / xsel; meta[0] = ceil(M/d)
+ *   (the caller runs the central-difference gradient on the cap rows of xsel into g)
+ *   reduce     IDW sums (unless weighted_first), sdf_pred, colour sigmoid and mask, fixed-order fp64 sums; losses[3] =
+ *              BCE, Eikonal, colour (NaN for an empty subset, 0 for a disabled term); counts[2] = Eikonal rows, colour
+ *              rows (float64, exact integers); meta[1] = colour rows
+ *   backward   d s [B,k] (or [B]), d g [cap,3] (zero on padding), d c [B,k,C] (or [B,C]; zero off the colour mask)
+ * flags: 1 Eikonal, 2 colour, 4 colour weighted by |weight|, 8 BCE weighted by |weight|, 16 weighted_first. */
+typedef struct pings_sdf_loss_args {
+  int64_t B, cap;                /* batch rows; Eikonal capacity ceil(B/d)                                          */
+  int32_t k, C, d, flags;        /* neighbours, colour channels, gradient decimation                                */
+  float sigma, eik_band, col_band;   /* sdf_scale; free_sample_end_dist_m; 0.5 * surface_sample_range_m          */
+  const float* coord;            /* [B,3]                                                                         */
+  const float* label;            /* [B]                                                                           */
+  const float* weight;           /* [B] (read as |weight|) or NULL when no term is weighted                       */
+  const float* color_label;      /* [B,C]                                                                         */
+  const float* w;                /* [B,k] IDW weights                                                             */
+  const float* s;                /* [B,k] decoder SDF per neighbour, [B] when weighted_first                      */
+  const float* c;                /* [B,k,C] colour decoder output (pre-sigmoid), [B,C] when weighted_first        */
+  const float* g;                /* [cap,3] finite-difference gradient of the xsel rows                           */
+  int32_t* idx;                  /* [cap] compacted Eikonal rows, -1 on padding                                   */
+  float* xsel;                   /* [cap,3]                                                                       */
+  int32_t* meta;                 /* [2]: Eikonal rows, colour rows                                                */
+  double* part;                  /* [pings_sdf_loss_partials(B, cap) * 4] per-block sums                          */
+  float* sdf_pred;               /* [B]                                                                           */
+  float* losses;                 /* [3]                                                                           */
+  double* counts;                /* [2]                                                                           */
+  const float* gl;               /* [3] upstream gradient of the losses                                           */
+  const float* g_pred;           /* [B] upstream gradient of sdf_pred, or NULL                                    */
+  float *d_s, *d_g, *d_c;        /* shapes of s, g, c                                                             */
+} pings_sdf_loss_args;
+PINGS_API int pings_sdf_loss_select(const pings_sdf_loss_args* a, void* stream);
+PINGS_API int pings_sdf_loss_reduce(const pings_sdf_loss_args* a, void* stream);
+PINGS_API int pings_sdf_loss_backward(const pings_sdf_loss_args* a, void* stream);
+/* Number of per-block partials the reduce writes (part holds 4 doubles each). */
+PINGS_API int pings_sdf_loss_partials(int64_t B, int64_t cap);
+
 #endif /* PINGS_HIP_H_ */
