@@ -804,6 +804,53 @@ PINGS_API int pings_reg_solve(const float* normal_eq, float lm_lambda, double* T
 PINGS_API int pings_reg_solve_checked(const float* normal_eq, float lm_lambda, double* T_out, double* t_out,
                                       int32_t* status_dev, int32_t* status_host, void* stream);
 
+/* ------------------------------------------------------ device-resident odometry loop (csrc/tracker.hip)
+ * One iteration of `Tracker.tracking` / `registration_step` (utils/tracker.py:43-210, 353-605) with the pose on the
+ * device and one small record read back per iteration (pings_amd/tracker_ops.py: tracking).
+ *   transform   cur = T p for the n source points; T is the fp64 pose in device memory, cast to fp32 and applied in
+ *               fp32 as utils/tools.py:888-900
+ *   assemble    validity (mask, min_grad < |g| < max_grad, std < max_std), residual (sdf - label, or sdf / |g| - label),
+ *               Geman-McClure and normal weights; fp64 per-block sums of the 21 + 6 normal-equation entries, the valid
+ *               count, sum w, sum |r| and sum w r^2 (invalid points weighted out, nothing compacted); optional valid[n]
+ *   step        one workgroup: the per-block sums in block order; fewer than 10 valid points -> identity step and
+ *               residual 0; else N, g scaled by n / (2 sum w) when `PINGS_REG_F_WEIGHTED` (the reference's w /= 2 mean w),
+ *               LM damping, fp64 solve and exponential map (as pings_reg_solve_checked); T <- dT T in fp64;
+ *               record[8] = valid count, status bits (PINGS_REG_*), then three doubles: residual mean in cm, rotation
+ *               acos((tr dT - 1) / 2) in degrees (NaN kept), translation |dt| in metres; trace row `iter` (optional,
+ *               24 doubles: count, residual, rotation, translation, status, sum w, sum w r^2, 0, dT[16])
+ * The caller owns every buffer; no launch allocates, copies or waits. */
+#define PINGS_REG_F_NORMALS 1      /* normals[n,3] given: w *= 0.5 + |n . g / (|g| + 1e-7)|                          */
+#define PINGS_REG_F_DIV_GRAD 2     /* reg_dist_div_grad_norm: residual = sdf / |g| - label                          */
+#define PINGS_REG_F_WEIGHTED 4     /* w is a tensor in the reference (any weight on): normalise by 2 mean(w)         */
+typedef struct pings_reg_loop_args {
+  int64_t n;                     /* source points                                                                  */
+  int32_t flags, iter, trace_cap;   /* PINGS_REG_F_*; trace row of this step; rows in trace                        */
+  float min_grad, max_grad, max_std;   /* validity window on |g|; bound on the SDF spread                         */
+  float gm_dist, gm_grad;        /* Geman-McClure scales of residual / gradient anomaly (<= 0: off)               */
+  float lm_lambda;               /* LM damping                                                                     */
+  const float* src;              /* [n,3] source points (transform)                                               */
+  float* cur;                    /* [n,3] transformed points (transform output, assemble input)                   */
+  const float* sdf;              /* [n]                                                                            */
+  const float* grad;             /* [n,3] d sdf / dx                                                               */
+  const float* std;              /* [n] spread of the per-neighbour predictions                                   */
+  const uint8_t* mask;           /* [n] registration mask (bool)                                                  */
+  const float* label;            /* [n] SDF labels                                                                 */
+  const float* normals;          /* [n,3] or NULL                                                                  */
+  uint8_t* valid;                /* [n] validity out, or NULL                                                      */
+  double* part;                  /* [pings_reg_partials(n) * 32] per-block sums                                    */
+  double* T;                     /* [16] pose, row-major, updated in place by step                                 */
+  double* delta;                 /* [16] dT of the step                                                            */
+  int32_t* record;               /* [8] device record of the step                                                  */
+  double* trace;                 /* [trace_cap * 24] or NULL                                                       */
+} pings_reg_loop_args;
+PINGS_API int pings_reg_partials(int64_t n);
+PINGS_API int pings_reg_transform(const pings_reg_loop_args* a, void* stream);
+PINGS_API int pings_reg_assemble(const pings_reg_loop_args* a, void* stream);
+PINGS_API int pings_reg_step(const pings_reg_loop_args* a, void* stream);
+/* The one host read of an iteration: the 8 record words behind everything queued on `stream`, by the polled
+ * read-back the other checked entry points use (not a launch function: it returns when the words have arrived). */
+PINGS_API int pings_reg_read_record(const int32_t* record_dev, int32_t* record_host, void* stream);
+
 /* ------------------------------------------------------ Gaussian-space loss block (csrc/gauss_loss.hip)
  * The mapper's opacity, opacity-entropy, isotropy, area, SDF-consistency, SDF-normal-consistency and invalid-opacity
  * terms (utils/mapper.py:1331-1483) with every count on the device.  One argument block for all entry points; the

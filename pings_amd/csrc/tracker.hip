@@ -7,6 +7,12 @@
 // 21 distinct entries of N and the 6 of g in fp64 registers; wave shuffle + LDS reduce per workgroup, per-workgroup
 // partials in global memory, and a second tiny kernel sums them in fixed order: bitwise reproducible.  HBM bound:
 // 32 B per point.
+//
+// The odometry loop (`pings_reg_transform` / `_assemble` / `_step`, pings_amd/tracker_ops.py: tracking) runs a whole
+// iteration of Tracker.tracking around the fused query with the pose in device memory: the validity filter and the
+// weights are folded into the same one-pass accumulation (invalid points weighted out, nothing compacted), and one
+// single-workgroup kernel sums the partials, solves, composes the pose and writes the small record the host reads.
+#include <cmath>
 #include "common.hpp"
 
 namespace {
@@ -82,8 +88,9 @@ __global__ void reg_finish_kernel(const double* __restrict__ partial, int nblock
 // reference's torch.linalg.inv raises (utils/tracker.py:668; LAPACK getrf info > 0); PINGS_REG_ILL_CONDITIONED = the
 // smallest pivot is below 1e-7 (one fp32 ulp: N arrives rounded to fp32) of the largest entry of the damped matrix,
 // i.e. the step is decided by rounding noise; PINGS_REG_NONFINITE = t or the pose came out Inf / NaN.
-__global__ void reg_solve_kernel(const float* __restrict__ ng, float lm_lambda, double* __restrict__ T_out,
-                                 double* __restrict__ t_out, int32_t* __restrict__ status) {
+// The solve of one step from the 42 floats [N | g]: returns the status bits (PINGS_REG_*), writes T[16] and t[6].
+__device__ int reg_solve_dev(const float* __restrict__ ng, float lm_lambda, double* __restrict__ T_out,
+                             double* __restrict__ t_out) {
   double A[6][7];
   double scale = 0.0, min_piv = 1e300;
   int flags = 0;
@@ -130,14 +137,167 @@ __global__ void reg_solve_kernel(const float* __restrict__ ng, float lm_lambda, 
   T_out[12] = 0.0; T_out[13] = 0.0; T_out[14] = 0.0; T_out[15] = 1.0;
   if (t_out)
     for (int r = 0; r < 6; ++r) t_out[r] = t[r];
-  if (status) {
-    if (!(min_piv >= 1e-7 * scale)) flags |= PINGS_REG_ILL_CONDITIONED;   // also when scale is NaN
-    bool fin = true;
-    for (int r = 0; r < 6; ++r) fin = fin && isfinite(t[r]);
-    // (t = 0 exactly makes the axis 0 / 0, as in the reference's expmap: reported as non-finite, not as singular)
-    for (int r = 0; r < 12; ++r) fin = fin && isfinite(T_out[r]);
-    if (!fin) flags |= PINGS_REG_NONFINITE;
-    *status = flags;
+  if (!(min_piv >= 1e-7 * scale)) flags |= PINGS_REG_ILL_CONDITIONED;   // also when scale is NaN
+  bool fin = true;
+  for (int r = 0; r < 6; ++r) fin = fin && isfinite(t[r]);
+  // (t = 0 exactly makes the axis 0 / 0, as in the reference's expmap: reported as non-finite, not as singular)
+  for (int r = 0; r < 12; ++r) fin = fin && isfinite(T_out[r]);
+  if (!fin) flags |= PINGS_REG_NONFINITE;
+  return flags;
+}
+
+__global__ void reg_solve_kernel(const float* __restrict__ ng, float lm_lambda, double* __restrict__ T_out,
+                                 double* __restrict__ t_out, int32_t* __restrict__ status) {
+  const int flags = reg_solve_dev(ng, lm_lambda, T_out, t_out);
+  if (status) *status = flags;
+}
+
+// ---------------------------------------------------------------- device-resident odometry loop
+// One iteration of Tracker.tracking (utils/tracker.py:43-210) around the fused query: transform, assemble, step.  The
+// pose stays in device memory; the host reads the 8-word record of the step and nothing else.
+
+constexpr int kLoopTerms = 32;   // 27 normal-equation entries, valid count, sum w, sum |r|, sum w r^2, (pad)
+constexpr int kLoopBlocks = 256;
+constexpr int kTraceRow = 24;
+
+__host__ __device__ inline int loop_blocks(long long n) {
+  long long nb = (n + 255) / 256;
+  return (int)(nb < 1 ? 1 : (nb > kLoopBlocks ? kLoopBlocks : nb));
+}
+
+// transform_torch (utils/tools.py:888-900): [p, 1] @ T.to(fp32).T, in fp32
+__global__ __launch_bounds__(256) void reg_transform_kernel(const float* __restrict__ src, const double* __restrict__ T,
+                                                            long long n, float* __restrict__ out) {
+  float M[12];
+#pragma unroll
+  for (int k = 0; k < 12; ++k) M[k] = (float)T[k];
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+    const float x = src[3 * i], y = src[3 * i + 1], z = src[3 * i + 2];
+#pragma unroll
+    for (int r = 0; r < 3; ++r) out[3 * i + r] = ((M[4 * r] * x + M[4 * r + 1] * y) + M[4 * r + 2] * z) + M[4 * r + 3];
+  }
+}
+
+// registration_step (utils/tracker.py:353-605) up to implicit_reg's GEMMs, with the invalid points weighted out
+__global__ __launch_bounds__(256) void reg_assemble_kernel(pings_reg_loop_args a) {
+  __shared__ double red[4][kLoopTerms];
+  double acc[kLoopTerms];
+#pragma unroll
+  for (int k = 0; k < kLoopTerms; ++k) acc[k] = 0.0;
+  const bool normals = (a.flags & PINGS_REG_F_NORMALS) && a.normals, div = a.flags & PINGS_REG_F_DIV_GRAD;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long long)gridDim.x * blockDim.x) {
+    const float gx = a.grad[3 * i], gy = a.grad[3 * i + 1], gz = a.grad[3 * i + 2];
+    const float gn = sqrtf((gx * gx + gy * gy) + gz * gz);
+    const bool ok = a.mask[i] && gn < a.max_grad && gn > a.min_grad && a.std[i] < a.max_std;
+    if (a.valid) a.valid[i] = ok;
+    if (!ok) continue;
+    float sdf = a.sdf[i];
+    if (div) sdf = sdf / gn;
+    const float r = sdf - a.label[i];
+    float w = 1.f;
+    if (a.gm_dist > 0.f) { const float q = a.gm_dist / (a.gm_dist + r * r); w = q * q; }          // w_res
+    if (a.gm_grad > 0.f) {                                                                        // * w_grad
+      const float an = gn - 1.f, q = a.gm_grad / (a.gm_grad + an * an);
+      w = w * (q * q);
+    }
+    if (normals) {                                                                                // * w_normal
+      const float den = gn + 1e-7f;
+      const float ux = gx / den, uy = gy / den, uz = gz / den;
+      const float d = (a.normals[3 * i] * ux + a.normals[3 * i + 1] * uy) + a.normals[3 * i + 2] * uz;
+      w = w * (0.5f + fabsf(d));
+    }
+    const float px = a.cur[3 * i], py = a.cur[3 * i + 1], pz = a.cur[3 * i + 2];
+    float J[6];
+    J[0] = py * gz - pz * gy;
+    J[1] = pz * gx - px * gz;
+    J[2] = px * gy - py * gx;
+    J[3] = gx; J[4] = gy; J[5] = gz;
+    const double wd = (double)w, rd = (double)r;
+    int k = 0;
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+      const double wa = wd * (double)J[p];
+#pragma unroll
+      for (int q = p; q < 6; ++q) acc[k++] += wa * (double)J[q];
+      acc[21 + p] -= wa * rd;
+    }
+    acc[27] += 1.0;
+    acc[28] += wd;
+    acc[29] += fabs(rd);
+    acc[30] += wd * rd * rd;
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kLoopTerms; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kLoopTerms)
+    a.part[(size_t)blockIdx.x * kLoopTerms + threadIdx.x] =
+        ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+}
+
+// The update of one iteration (utils/tracker.py:407-413, :494-497, :608-689, :121-168) in one workgroup of 64
+__global__ __launch_bounds__(64) void reg_step_kernel(pings_reg_loop_args a, int nblocks) {
+  __shared__ double tot[kLoopTerms];
+  const int k = threadIdx.x;
+  if (k < kLoopTerms) {
+    double v = 0.0;
+    for (int b = 0; b < nblocks; ++b) v += a.part[(size_t)b * kLoopTerms + k];
+    tot[k] = v;
+  }
+  __syncthreads();
+  if (k != 0) return;
+  const double cnt = tot[27];
+  double D[16];
+  double res_cm = 0.0;
+  int flags = 0;
+  if (cnt < 10.0) {   // registration_step's early return: identity step, residual 0.0
+    for (int e = 0; e < 16; ++e) D[e] = (e % 5 == 0) ? 1.0 : 0.0;
+  } else {
+    // w /= 2 mean(w) scales N and g by one factor: the step is unchanged, the damped N is not re-rounded differently
+    const double c = (a.flags & PINGS_REG_F_WEIGHTED) ? cnt / (2.0 * tot[28]) : 1.0;
+    float ng[42];
+    int t = 0;
+    for (int p = 0; p < 6; ++p)
+      for (int q = p; q < 6; ++q) {
+        const float v = (float)(c * tot[t++]);
+        ng[p * 6 + q] = v;
+        ng[q * 6 + p] = v;
+      }
+    for (int p = 0; p < 6; ++p) ng[36 + p] = (float)(c * tot[21 + p]);
+    flags = reg_solve_dev(ng, a.lm_lambda, D, nullptr);
+    res_cm = (double)(float)(tot[29] / cnt) * 100.0;   // torch.mean(|r|).item() of an fp32 tensor, times 100
+  }
+  double Tn[16];
+  for (int r = 0; r < 4; ++r)
+    for (int c = 0; c < 4; ++c) {
+      double v = 0.0;
+      for (int m = 0; m < 4; ++m) v += D[r * 4 + m] * a.T[m * 4 + c];
+      Tn[r * 4 + c] = v;
+    }
+  for (int e = 0; e < 16; ++e) {
+    a.T[e] = Tn[e];
+    a.delta[e] = D[e];
+  }
+  const double rot_deg = acos(((D[0] + D[5]) + D[10] - 1.0) / 2.0) * 180.0 / M_PI;   // NaN when (tr - 1) / 2 > 1
+  const double tran_m = sqrt((D[3] * D[3] + D[7] * D[7]) + D[11] * D[11]);
+  a.record[0] = (int32_t)cnt;
+  a.record[1] = flags;
+  const double vals[3] = {res_cm, rot_deg, tran_m};
+  for (int e = 0; e < 3; ++e) {
+    const unsigned long long u = (unsigned long long)__double_as_longlong(vals[e]);
+    a.record[2 + 2 * e] = (int32_t)(uint32_t)(u & 0xffffffffull);
+    a.record[3 + 2 * e] = (int32_t)(uint32_t)(u >> 32);
+  }
+  if (a.trace && a.iter >= 0 && a.iter < a.trace_cap) {
+    double* row = a.trace + (size_t)a.iter * kTraceRow;
+    row[0] = cnt; row[1] = res_cm; row[2] = rot_deg; row[3] = tran_m; row[4] = (double)flags;
+    row[5] = tot[28]; row[6] = tot[30]; row[7] = 0.0;
+    for (int e = 0; e < 16; ++e) row[8 + e] = D[e];
   }
 }
 
@@ -183,4 +343,49 @@ PINGS_API int pings_reg_normal_equations(const float* points, const float* sdf_g
   reg_finish_kernel<<<1, 64, 0, st>>>(reinterpret_cast<const double*>(scratch), nb, out);
   PINGS_LAUNCH_CHECK();
   return PINGS_OK;
+}
+
+PINGS_API int pings_reg_partials(int64_t n) { return loop_blocks(n); }
+
+PINGS_API int pings_reg_transform(const pings_reg_loop_args* a, void* stream) {
+  PINGS_ARG_CHECK(a && a->n >= 0 && a->T && a->cur, "bad argument");
+  PINGS_ARG_CHECK(a->n == 0 || a->src, "null source points");
+  if (a->n == 0) return PINGS_OK;
+  hipStream_t st = pings::as_stream(stream);
+  pings::prof::Scope sc("reg_transform", st);
+  long long nb = (a->n + 255) / 256;
+  nb = nb > 2048 ? 2048 : nb;
+  reg_transform_kernel<<<(int)nb, 256, 0, st>>>(a->src, a->T, (long long)a->n, a->cur);
+  PINGS_LAUNCH_CHECK();
+  return PINGS_OK;
+}
+
+PINGS_API int pings_reg_assemble(const pings_reg_loop_args* a, void* stream) {
+  PINGS_ARG_CHECK(a && a->n >= 0 && a->part, "bad argument");
+  PINGS_ARG_CHECK(a->n == 0 || (a->cur && a->sdf && a->grad && a->std && a->mask && a->label), "null input");
+  PINGS_ARG_CHECK(!(a->flags & PINGS_REG_F_NORMALS) || a->normals, "PINGS_REG_F_NORMALS without normals");
+  PINGS_ARG_CHECK((a->flags & ~7) == 0, "unknown flag");
+  hipStream_t st = pings::as_stream(stream);
+  pings::prof::Scope sc("reg_assemble", st);
+  reg_assemble_kernel<<<loop_blocks(a->n), 256, 0, st>>>(*a);
+  PINGS_LAUNCH_CHECK();
+  return PINGS_OK;
+}
+
+PINGS_API int pings_reg_step(const pings_reg_loop_args* a, void* stream) {
+  PINGS_ARG_CHECK(a && a->n >= 0 && a->part && a->T && a->delta && a->record, "bad argument");
+  PINGS_ARG_CHECK(!a->trace || a->trace_cap > 0, "trace without rows");
+  PINGS_ARG_CHECK((a->flags & ~7) == 0, "unknown flag");
+  hipStream_t st = pings::as_stream(stream);
+  pings::prof::Scope sc("reg_step", st);
+  reg_step_kernel<<<1, 64, 0, st>>>(*a, loop_blocks(a->n));
+  PINGS_LAUNCH_CHECK();
+  return PINGS_OK;
+}
+
+PINGS_API int pings_reg_read_record(const int32_t* record_dev, int32_t* record_host, void* stream) {
+  PINGS_ARG_CHECK(record_dev && record_host, "null pointer");
+  const uint32_t* w[8];
+  for (int i = 0; i < 8; ++i) w[i] = reinterpret_cast<const uint32_t*>(record_dev) + i;
+  return pings::host_read_words(w, 8, reinterpret_cast<uint32_t*>(record_host), pings::as_stream(stream));
 }

@@ -12,13 +12,23 @@ term (`query_color_grad`) keeps the reference's torch tail behind the HIP `query
 `pings_reg_normal_equations` (one pass, fp64 accumulation, fixed-order reduction); LM damping, the fp64 6x6 solve and
 the exponential map run in `pings_reg_solve` (one single-thread kernel, the reference's formulas).
 
-`install(tracker_module)` rebinds both.  Host tensors raise: there is no CPU path (oracle/tracker_cpu.py is the
-CPU restatement used by the tests).
+`tracking` — drop-in for `Tracker.tracking` (utils/tracker.py:43-210): the odometry loop with the pose in device
+memory.  Each iteration runs `pings_reg_transform`, the fused query, `pings_reg_assemble` (validity, residual, weights
+and the normal equations in one pass, nothing compacted) and `pings_reg_step` (solve, pose update, convergence
+quantities), then reads ONE 8-word record back; the reference's decision logic runs on those host numbers.
+`registration_step` — drop-in for `Tracker.registration_step` (:353-605) on the same two kernels; it keeps the
+reference's host reads (compacted `valid_points`, the residual as a float).
+
+`install(tracker_module)` rebinds `query_source_points` and `implicit_reg`; `install(tracker_module, loop=True)` also
+rebinds `Tracker.tracking` and `Tracker.registration_step`, keeping the originals for what the loop delegates (the
+photometric and colour-consistency configurations, and the Open3D weight cloud of a `vis_result` run).  Host tensors
+raise: there is no CPU path (oracle/tracker_cpu.py is the CPU restatement used by the tests).
 """
 from __future__ import annotations
 
 import ctypes as C
 import math
+import struct
 
 import torch
 
@@ -29,6 +39,12 @@ from . import neural_points as _np
 REG_SINGULAR, REG_ILL_CONDITIONED, REG_NONFINITE = 1, 2, 4     # include/pings_hip.h: PINGS_REG_*
 _REG_CHECK = __import__("os").environ.get("PINGS_REG_CHECK", "1") != "0"
 last_solve_status = None    # int32[1] device tensor of the most recent `implicit_reg` (bit mask above)
+# float64 [iterations, 24] device tensor of the most recent `tracking` call, one row per executed iteration: valid
+# count, residual (cm), rotation (deg), translation (m), status bits, sum w, sum w r^2, 0, then dT row-major (16)
+last_trace = None
+_ORIG = {}                  # the reference's Tracker.tracking / registration_step, kept by install(loop=True)
+F_NORMALS, F_DIV_GRAD, F_WEIGHTED = 1, 2, 4     # include/pings_hip.h: PINGS_REG_F_*
+TRACE_ROW = 24
 
 
 def _declare(L):
@@ -43,7 +59,23 @@ def _declare(L):
     L.pings_reg_solve.argtypes = [vp, C.c_float, vp, vp, vp]
     L.pings_reg_solve_checked.restype = C.c_int
     L.pings_reg_solve_checked.argtypes = [vp, C.c_float, vp, vp, vp, C.POINTER(C.c_int32), vp]
+    if hasattr(L, "pings_reg_step"):
+        for n in ("transform", "assemble", "step"):
+            f = getattr(L, "pings_reg_" + n)
+            f.restype, f.argtypes = C.c_int, [C.POINTER(_LoopArgs), vp]
+        L.pings_reg_partials.restype = C.c_int
+        L.pings_reg_partials.argtypes = [C.c_int64]
+        L.pings_reg_read_record.restype = C.c_int
+        L.pings_reg_read_record.argtypes = [vp, vp, vp]
     L._trk_declared = True
+
+
+class _LoopArgs(C.Structure):     # pings_reg_loop_args
+    _fields_ = [("n", C.c_int64), ("flags", C.c_int32), ("iter", C.c_int32), ("trace_cap", C.c_int32),
+                ("min_grad", C.c_float), ("max_grad", C.c_float), ("max_std", C.c_float), ("gm_dist", C.c_float),
+                ("gm_grad", C.c_float), ("lm_lambda", C.c_float)] + \
+               [(k, C.c_void_p) for k in ("src", "cur", "sdf", "grad", "std", "mask", "label", "normals", "valid",
+                                          "part", "T", "delta", "record", "trace")]
 
 
 def normal_equations(points, sdf_grad, sdf_residual, weight):
@@ -187,7 +219,236 @@ def query_source_points(self, coord, bs, query_sdf=True, query_sdf_grad=True, qu
     return sdf_pred, sdf_grad, color_pred, color_grad, sem_pred, mc_mask, certainty, sdf_std
 
 
-def install(tracker_module) -> None:
-    """`import utils.tracker as T; install(T)`: Tracker.query_source_points and implicit_reg -> HIP."""
+# ---------------------------------------------------------------- device-resident odometry loop
+def _loop_lib():
+    L = _lib.lib()
+    _declare(L)
+    if not hasattr(L, "pings_reg_step"):
+        raise _lib.PingsHipError(f"{_lib.LIB_PATH} has no pings_reg_step: rebuild it with `python -m pings_amd.build`")
+    return L
+
+
+class _Loop:
+    """Buffers and argument block of one `tracking` / `registration_step` call (caller-owned scratch of the kernels)."""
+
+    def __init__(self, self_, points, labels, normals, min_grad, max_grad, GM_dist, GM_grad, lm_lambda, weighted,
+                 pose, trace_rows=0, valid_out=False):
+        if not points.is_cuda:
+            raise _lib.PingsHipError("tracking runs on the HIP device only (got a CPU tensor); there is no CPU fallback")
+        cfg = self_.config
+        self.L = L = _loop_lib()
+        dev = points.device
+        self.dev, self.n = dev, int(points.shape[0])
+        f = lambda t: t.detach().to(dev, torch.float32).contiguous()
+        self.src = f(points)
+        self.cur = torch.empty_like(self.src)
+        self.label = f(labels).reshape(-1)
+        self.normals = f(normals) if normals is not None else None
+        self.part = torch.empty(int(L.pings_reg_partials(self.n)) * 32, dtype=torch.float64, device=dev)
+        self.T = pose
+        self.delta = torch.empty(4, 4, dtype=torch.float64, device=dev)
+        self.record = torch.empty(8, dtype=torch.int32, device=dev)
+        self.trace = torch.zeros(max(trace_rows, 1), TRACE_ROW, dtype=torch.float64, device=dev) if trace_rows else None
+        self.valid = torch.empty(self.n, dtype=torch.bool, device=dev) if valid_out else None
+        self.host = (C.c_int32 * 8)()
+        flags = (F_NORMALS if normals is not None else 0) | (F_DIV_GRAD if cfg.reg_dist_div_grad_norm else 0) | \
+                (F_WEIGHTED if weighted else 0)
+        max_std = cfg.surface_sample_range_m * cfg.max_sdf_std_ratio
+        a = _LoopArgs(self.n, flags, 0, trace_rows, float(min_grad), float(max_grad), float(max_std),
+                      float(GM_dist) if GM_dist is not None else 0.0, float(GM_grad) if GM_grad is not None else 0.0,
+                      float(lm_lambda))
+        a.src, a.cur, a.label, a.normals = self.src.data_ptr(), self.cur.data_ptr(), self.label.data_ptr(), \
+            _lib.ptr(self.normals)
+        a.valid = _lib.ptr(self.valid)
+        a.part, a.T, a.delta, a.record = (t.data_ptr() for t in (self.part, self.T, self.delta, self.record))
+        a.trace = _lib.ptr(self.trace)
+        self.args = a
+        self.stream = _lib.stream_ptr(dev)
+        self.bs = int(cfg.infer_bs)
+        self.nn_k = int(getattr(cfg, "track_mask_query_nn_k", getattr(cfg, "query_nn_k", 4)))
+
+    def transform(self):
+        _lib.check(self.L.pings_reg_transform(C.byref(self.args), self.stream), "pings_reg_transform")
+        return self.cur
+
+    def iterate(self, self_, it, sync_tag):
+        """query, assemble, step and the one host read; returns (valid count, status, residual cm, rot deg, tran m)."""
+        a = self.args
+        # the colour query is skipped: no weight uses it in the configurations that reach this path
+        sdf, grad, _, _, _, mask, _, std = query_source_points(self_, self.cur, self.bs, True, True, False, False,
+                                                                query_certainty=False, query_locally=True,
+                                                                mask_min_nn_count=self.nn_k)
+        keep = [t.contiguous() for t in (sdf, grad, std, mask)]
+        a.sdf, a.grad, a.std = (t.data_ptr() for t in keep[:3])
+        a.mask = keep[3].view(torch.uint8).data_ptr()
+        a.iter = it
+        _lib.check(self.L.pings_reg_assemble(C.byref(a), self.stream), "pings_reg_assemble")
+        _lib.check(self.L.pings_reg_step(C.byref(a), self.stream), "pings_reg_step")
+        _lib.check(self.L.pings_reg_read_record(self.record.data_ptr(), C.addressof(self.host), self.stream),
+                   "pings_reg_read_record")
+        _lib.note_sync(sync_tag)
+        del keep
+        h = self.host
+        raw = bytes(h)
+        res, rot, tran = struct.unpack("<3d", raw[8:32])
+        return int(h[0]), int(h[1]), res, rot, tran
+
+
+def _check_status(status, warned):
+    if status & REG_SINGULAR:
+        raise torch.linalg.LinAlgError(
+            "tracking: the damped normal matrix is singular (a pivot is exactly zero or not finite); the reference's "
+            "torch.linalg.inv raises here as well (utils/tracker.py:668)")
+    if status & (REG_ILL_CONDITIONED | REG_NONFINITE) and not warned:
+        import warnings
+
+        warnings.warn("tracking: " + ("non-finite registration step" if status & REG_NONFINITE else
+                      "normal matrix ill-conditioned (smallest pivot < 1e-7 of its largest entry)") +
+                      "; the step is applied as computed, as the reference's inverse would be (warned once per call)",
+                      RuntimeWarning, stacklevel=3)
+        return True
+    return warned
+
+
+def _say(self, msg):
+    if not self.silence:
+        print(msg)
+
+
+def _original(name):
+    f = _ORIG.get(name)
+    if f is None:
+        raise NotImplementedError(f"tracker_ops: this configuration runs the reference's own `Tracker.{name}`; "
+                                  "bind the loop with install(tracker_module, loop=True) so that it is kept")
+    return f
+
+
+def _colour_branch(cfg, colors):
+    """The reference's colour-using branches (photometric term, consistency weight): delegated, not native."""
+    colors_on = colors is not None and cfg.color_on
+    return colors_on and (cfg.photometric_loss_on or cfg.consist_wieght_on)
+
+
+def tracking(self, source_points, init_pose=None, source_colors=None, source_normals=None, source_semantics=None,
+             source_sdf=None, cur_ts=None, loop_reg: bool = False, vis_result: bool = False):
+    """`Tracker.tracking` (utils/tracker.py:43-210): same arguments, same (T, cov_mat, weight_pc, valid_flag).  One
+    host read per iteration (`note_sync("tracking_iteration")`); the records of the call are left in `last_trace`."""
+    global last_trace
+    cfg = self.config
+    if _colour_branch(cfg, source_colors):
+        return _original("tracking")(self, source_points, init_pose, source_colors, source_normals, source_semantics,
+                                     source_sdf, cur_ts, loop_reg, vis_result)
+    if not source_points.is_cuda:
+        raise _lib.PingsHipError("tracking runs on the HIP device only (got a CPU tensor); there is no CPU fallback")
+    dev = source_points.device
+    pose = torch.eye(4, dtype=torch.float64, device=dev) if init_pose is None else \
+        init_pose.detach().to(dev, torch.float64).clone().contiguous()
+    min_grad_norm, max_grad_norm = cfg.reg_min_grad_norm, cfg.reg_max_grad_norm
+    cur_GM_dist_m = cfg.reg_GM_dist_m if cfg.reg_GM_dist_m > 0 else None
+    cur_GM_grad = cfg.reg_GM_grad if cfg.reg_GM_grad > 0 else None
+    lm_lambda, iter_n = cfg.reg_lm_lambda, cfg.reg_iter_n
+    term_thre_deg, term_thre_m = cfg.reg_term_thre_deg, cfg.reg_term_thre_m
+    max_valid_final_sdf_residual_cm = cfg.surface_sample_range_m * 0.6 * 100.0
+    min_valid_ratio, max_increment_sdf_residual_ratio = 0.05, 1.1
+    eigenvalue_ratio_thre, min_valid_points = 0.005, 10
+    converged, valid_flag, last_sdf_residual_cm = False, True, 1e5
+    cov_mat = eigenvalues = weight_point_cloud = None
+    source_point_count = source_points.shape[0]
+    _say(self, f"# Source point for registeration : {source_point_count}")
+    if source_sdf is None:
+        source_sdf = torch.zeros(source_point_count, device=dev)
+    weighted = cur_GM_dist_m is not None or cur_GM_grad is not None or source_normals is not None
+    lp = _Loop(self, source_points, source_sdf, source_normals, min_grad_norm, max_grad_norm, cur_GM_dist_m,
+               cur_GM_grad, lm_lambda, weighted, pose, trace_rows=max(int(iter_n), 1))
+    warned = False
+    i = -1
+    for i in range(iter_n):
+        cur_points = lp.transform()
+        if vis_result and converged:
+            # the Open3D weight cloud, covariance and eigenvalues: the reference's own registration_step on the current
+            # points (its query and implicit_reg are this module's after install); its dT goes back into the pose
+            (delta_T, cov_mat, eigenvalues, weight_point_cloud, valid_points_torch, sdf_residual_cm,
+             _photo) = _original("registration_step")(self, cur_points, source_normals, source_sdf, source_colors,
+                                                      min_grad_norm, max_grad_norm, cur_GM_dist_m, cur_GM_grad,
+                                                      lm_lambda, True)
+            delta_T = delta_T.to(dev, torch.float64)
+            pose.copy_(delta_T @ pose)
+            valid_point_count = valid_points_torch.shape[0]
+            lp.trace[i, 0], lp.trace[i, 1] = float(valid_point_count), float(sdf_residual_cm)
+            lp.trace[i, 8:] = delta_T.reshape(16)
+        else:
+            valid_point_count, status, sdf_residual_cm, rot_deg, tran_m = lp.iterate(self, i, "tracking_iteration")
+            warned = _check_status(status, warned)
+            cov_mat = eigenvalues = weight_point_cloud = None
+        if (sdf_residual_cm - last_sdf_residual_cm) / last_sdf_residual_cm > max_increment_sdf_residual_ratio:
+            _say(self, "(Warning) registration failed: wrong optimization")
+            valid_flag = False
+        else:
+            last_sdf_residual_cm = sdf_residual_cm
+        if (valid_point_count < min_valid_points) or (1.0 * valid_point_count / source_point_count < min_valid_ratio):
+            _say(self, "(Warning) registration failed: not enough valid points")
+            valid_flag = False
+        if not valid_flag or converged:
+            break
+        # rot_deg is NaN when (tr dT - 1) / 2 > 1: the comparison is False and the loop goes on, as the reference's
+        if abs(rot_deg) < term_thre_deg and tran_m < term_thre_m or i == iter_n - 2:
+            converged = True
+    last_trace = lp.trace[: i + 1]
+    _say(self, f"# Valid source point             : {valid_point_count}")
+    _say(self, f"Odometry residual (cm): {sdf_residual_cm}")
+    if sdf_residual_cm > max_valid_final_sdf_residual_cm:
+        _say(self, "(Warning) registration failed: too large final residual")
+        valid_flag = False
+    if eigenvalues is not None:
+        min_eigenvalue = torch.min(eigenvalues).item()
+        if cfg.eigenvalue_check and min_eigenvalue < valid_point_count * eigenvalue_ratio_thre:
+            _say(self, "(Warning) registration failed: eigenvalue check failed")
+            valid_flag = False
+    if cov_mat is not None:
+        cov_mat = cov_mat.detach().cpu().numpy()
+    T = pose
+    if not valid_flag and i < 10:   # not valid within 10 iterations: the initial guess (None when none was given)
+        T = init_pose
+        cov_mat = None
+    return T, cov_mat, weight_point_cloud, valid_flag
+
+
+def registration_step(self, points: torch.Tensor, normals: torch.Tensor, sdf_labels: torch.Tensor,
+                      colors: torch.Tensor, min_grad_norm, max_grad_norm, GM_dist=None, GM_grad=None, lm_lambda=0.0,
+                      vis_weight_pc=False):
+    """`Tracker.registration_step` (utils/tracker.py:353-605) on the loop's kernels (identity pose): returns the
+    reference's (T, cov_mat, eigenvalues, weight_point_cloud, valid_points, sdf_residual_cm, photo_residual).  Keeps
+    the reference's host reads (compacted valid_points, the residual as a float); `tracking` does not call it."""
+    cfg = self.config
+    if vis_weight_pc or _colour_branch(cfg, colors):
+        return _original("registration_step")(self, points, normals, sdf_labels, colors, min_grad_norm, max_grad_norm,
+                                              GM_dist, GM_grad, lm_lambda, vis_weight_pc)
+    if not points.is_cuda:
+        raise _lib.PingsHipError("registration_step runs on the HIP device only (got a CPU tensor); there is no CPU "
+                                 "fallback")
+    dev = points.device
+    pose = torch.eye(4, dtype=torch.float64, device=dev)
+    weighted = GM_dist is not None or GM_grad is not None or normals is not None
+    lp = _Loop(self, points, sdf_labels, normals, min_grad_norm, max_grad_norm, GM_dist, GM_grad, lm_lambda, weighted,
+               pose, valid_out=True)
+    lp.cur.copy_(lp.src)     # the points arrive transformed already
+    count, status, res_cm, _, _ = lp.iterate(self, 0, "registration_step")
+    valid_points = points[lp.valid]
+    if count < 10:
+        return lp.delta, None, None, None, valid_points, 0.0, 0.0
+    _check_status(status, False)
+    return lp.delta, None, None, None, valid_points, res_cm, None
+
+
+def install(tracker_module, loop: bool = False) -> None:
+    """`import utils.tracker as T; install(T)`: Tracker.query_source_points and implicit_reg -> HIP.  With loop=True
+    also Tracker.tracking and Tracker.registration_step (the originals are kept for what the loop delegates)."""
     tracker_module.Tracker.query_source_points = query_source_points
     tracker_module.implicit_reg = implicit_reg
+    if loop:
+        cls = tracker_module.Tracker
+        for name, fn in (("tracking", tracking), ("registration_step", registration_step)):
+            cur = cls.__dict__.get(name)
+            if cur is not fn:           # installing twice keeps the first originals
+                _ORIG[name] = cur
+            setattr(cls, name, fn)
