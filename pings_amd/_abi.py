@@ -1,0 +1,266 @@
+"""The C ABI of libpings_hip.so, declared once for ctypes: a mirror of include/pings_hip.h and nothing else.
+
+`_lib.lib()` applies `SIGNATURES` when it loads the library and refuses a library whose `pings_abi_version()` is not
+`ABI_VERSION`.  tests/test_abi.py checks every name, type, struct layout and constant here against the header, so a
+change of the header is made here in the same commit.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+ABI_VERSION = 9                                                   # PINGS_ABI_VERSION
+
+RASTER_SURFEL, RASTER_3DGS, RASTER_2DGS = 0, 1, 2                 # PINGS_RASTER_*: pings_raster_settings.mode
+HEAD_COLOR, HEAD_SEMANTIC = 0, 1                                  # PINGS_HEAD_*: pings_head_reduce mode
+REG_SINGULAR, REG_ILL_CONDITIONED, REG_NONFINITE = 1, 2, 4        # PINGS_REG_*: pings_reg_solve_checked status bits
+REG_F_NORMALS, REG_F_DIV_GRAD, REG_F_WEIGHTED = 1, 2, 4           # PINGS_REG_F_*: pings_reg_loop_args.flags
+
+vp = C.c_void_p     # device pointers and the hipStream_t travel as integers (tensor.data_ptr())
+i32, i64, f32, sz = C.c_int, C.c_int64, C.c_float, C.c_size_t
+
+
+# ---------------------------------------------------------------- struct mirrors: pings_<snake_case of the class name>
+class RasterSettings(C.Structure):
+    _fields_ = [
+        ("image_height", C.c_int32), ("image_width", C.c_int32),
+        ("mode", C.c_int32), ("front_only", C.c_int32),
+        ("tanfovx", C.c_double), ("tanfovy", C.c_double), ("scale_modifier", C.c_double),
+        ("bg", C.c_void_p), ("viewmatrix", C.c_void_p), ("projmatrix", C.c_void_p),
+        ("projmatrix_raw", C.c_void_p), ("prcppoint", C.c_void_p),
+    ]
+
+
+class KnnMap(C.Structure):
+    _fields_ = [
+        ("table", C.c_void_p), ("buffer_size", C.c_int64), ("neural_points", C.c_void_p),
+        ("point_ts_create", C.c_void_p), ("travel_dist", C.c_void_p), ("cur_ts", C.c_int32),
+        ("time_filtering", C.c_int32), ("diff_travel_dist_local", C.c_float),
+        ("free_mask", C.c_void_p), ("valid_mask", C.c_void_p),
+        ("use_free_mask", C.c_int32), ("use_valid_mask", C.c_int32),
+        ("global2local", C.c_void_p), ("neighbor_dx", C.c_void_p), ("K", C.c_int32), ("nn_k", C.c_int32),
+        ("resolution", C.c_float), ("max_valid_dist2", C.c_float),
+        ("compact", C.c_void_p), ("compact_mask", C.c_uint32),
+        ("blocks", C.c_void_p), ("block_records", C.c_void_p), ("blocks_ok", C.c_void_p), ("block_mask", C.c_uint32),
+    ]
+
+
+class QfTables(C.Structure):
+    _fields_ = [("geo_features", C.c_void_p), ("color_features", C.c_void_p), ("Fg", C.c_int32), ("Fc", C.c_int32),
+                ("points", C.c_void_p), ("orientations", C.c_void_p), ("certainties", C.c_void_p),
+                ("after_pgo", C.c_int32), ("weighted_first", C.c_int32)]
+
+
+class SdfDecoder(C.Structure):
+    _fields_ = [("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
+                ("hidden", C.c_int32), ("feat_dim", C.c_int32), ("sdf_scale", C.c_float),
+                ("weighted_first", C.c_int32)]
+
+
+class MlpJob(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("IN", C.c_int32), ("OUT", C.c_int32), ("W1", C.c_void_p), ("b1", C.c_void_p),
+                ("W2", C.c_void_p), ("b2", C.c_void_p), ("y", C.c_void_p), ("dL_dy", C.c_void_p), ("dL_dx", C.c_void_p),
+                ("dL_dW1", C.c_void_p), ("dL_db1", C.c_void_p), ("dL_dW2", C.c_void_p), ("dL_db2", C.c_void_p)]
+
+
+class SpawnParams(C.Structure):
+    _fields_ = [("n", C.c_int), ("k", C.c_int), ("scale_dim", C.c_int), ("surfel", C.c_int),
+                ("color_residual", C.c_int), ("alpha_filter_on", C.c_int), ("scale_filter_on", C.c_int),
+                ("displacement_range", C.c_float), ("unit_scale", C.c_float), ("max_scale", C.c_float),
+                ("scale_filter_thr", C.c_float)]
+
+
+class GatherJob(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("rows", C.c_int64)]
+
+
+class ImageLossParams(C.Structure):
+    _fields_ = [("H", C.c_int), ("W", C.c_int), ("v_min", C.c_int), ("v_max", C.c_int), ("depth_min", C.c_float),
+                ("depth_max", C.c_float), ("min_accu_alpha", C.c_float), ("inverse_depth", C.c_int),
+                ("consist_mode", C.c_int)]
+
+
+class RegLoopArgs(C.Structure):
+    _fields_ = [("n", C.c_int64), ("flags", C.c_int32), ("iter", C.c_int32), ("trace_cap", C.c_int32),
+                ("min_grad", C.c_float), ("max_grad", C.c_float), ("max_std", C.c_float), ("gm_dist", C.c_float),
+                ("gm_grad", C.c_float), ("lm_lambda", C.c_float)] + \
+               [(k, C.c_void_p) for k in ("src", "cur", "sdf", "grad", "std", "mask", "label", "normals", "valid",
+                                          "part", "T", "delta", "record", "trace")]
+
+
+class GaussLossArgs(C.Structure):
+    _fields_ = [("P", C.c_int64), ("Na", C.c_int64), ("cap", C.c_int64), ("R", C.c_int32), ("ncols", C.c_int32),
+                ("scale_cols", C.c_int32), ("flags", C.c_int32), ("min_alpha", C.c_float),
+                ("contrib_thr", C.c_float), ("shift_range", C.c_float), ("grad_min", C.c_float),
+                ("grad_max", C.c_float), ("inv_voxel_pow", C.c_float), ("n_inject", C.c_int64)] + \
+               [(n, vp) for n in ("alpha_all", "visible", "contrib", "free_mask", "xyz", "rot", "scale", "alpha", "seed",
+                                  "inject_idx", "randn", "keys", "part", "meta", "idx", "normal", "queries", "label",
+                                  "sdf", "grad", "nn", "valid", "losses", "counts", "g", "ds", "v", "dn", "dq",
+                                  "d_xyz", "d_rot", "d_scale", "d_alpha", "d_alpha_all")]
+
+
+class SdfHvpArgs(C.Structure):
+    _fields_ = [("W1", vp), ("b1", vp), ("W2", vp), ("b2", vp), ("H", C.c_int32), ("F", C.c_int32),
+                ("scale", C.c_float), ("after_pgo", C.c_int32), ("features", vp), ("points", vp),
+                ("orientations", vp), ("gpoints", vp), ("queries", vp), ("B", C.c_int64), ("nnk", C.c_int32),
+                ("idx", vp), ("gidx", vp), ("v", vp), ("ds", vp), ("grad_x", vp), ("out", vp)]
+
+
+class SdfLossArgs(C.Structure):
+    _fields_ = [("B", C.c_int64), ("cap", C.c_int64), ("k", C.c_int32), ("C", C.c_int32), ("d", C.c_int32),
+                ("flags", C.c_int32), ("sigma", C.c_float), ("eik_band", C.c_float), ("col_band", C.c_float)] + \
+               [(n, vp) for n in ("coord", "label", "weight", "color_label", "w", "s", "c", "g", "idx", "xsel", "meta",
+                                  "part", "sdf_pred", "losses", "counts", "gl", "g_pred", "d_s", "d_g", "d_c")]
+
+
+# ---------------------------------------------------------------- entry points: {name: (restype, argtypes)}
+SIGNATURES = {
+    # general
+    "pings_abi_version": (i32, []),
+    "pings_last_error": (C.c_char_p, []),
+    "pings_prof_enable": (i32, [i32]),
+    "pings_prof_only": (i32, [C.c_char_p]),
+    "pings_prof_report": (i32, [C.c_char_p, sz]),
+    # fused SSIM
+    "pings_ssim_partials_count": (sz, [i32, i32, i32]),
+    "pings_ssim_forward": (i32, [vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "pings_ssim_backward": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    # Gaussian(-surfel) rasteriser
+    "pings_raster_mark_visible": (i32, [vp, i32, C.POINTER(RasterSettings), vp, vp]),
+    "pings_raster_geom_bytes": (sz, [i32, i32, i32]),
+    "pings_raster_binning_bytes": (sz, [i64, i32, i32]),
+    "pings_raster_image_bytes": (sz, [i32, i32]),
+    "pings_raster_preprocess": (i32, [C.POINTER(RasterSettings), i32, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64),
+                                      C.POINTER(i32), vp]),
+    "pings_raster_preprocess_dyn": (i32, [C.POINTER(RasterSettings), i32, vp, vp, vp, vp, vp, vp, vp, vp, i32,
+                                          C.POINTER(vp), i32, C.POINTER(i32), C.POINTER(i64), C.POINTER(i32), vp]),
+    "pings_raster_render": (i32, [C.POINTER(RasterSettings), i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "pings_raster_backward_bytes": (sz, [i32, i64]),
+    "pings_raster_backward": (i32, [C.POINTER(RasterSettings), i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                    vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
+    "pings_raster_debug_lists": (i32, [vp, i64, i32, i32, vp, vp, vp]),
+    "pings_raster_debug_image": (i32, [vp, i32, i32, vp, vp, vp]),
+    # 2D Gaussian splatting rasteriser
+    "pings_raster2d_geom_bytes": (sz, [i32, i32, i32]),
+    "pings_raster2d_binning_bytes": (sz, [i64, i32, i32]),
+    "pings_raster2d_image_bytes": (sz, [i32, i32]),
+    "pings_raster2d_preprocess": (i32, [C.POINTER(RasterSettings), i32, vp, vp, vp, vp, vp, vp, vp, vp, i32,
+                                        C.POINTER(vp), i32, C.POINTER(i32), C.POINTER(i64), vp]),
+    "pings_raster2d_render": (i32, [C.POINTER(RasterSettings), i32, i64, vp, vp, vp, vp, vp, vp]),
+    "pings_raster2d_backward_bytes": (sz, [i32, i64]),
+    "pings_raster2d_backward": (i32, [C.POINTER(RasterSettings), i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      vp, vp, vp, vp]),
+    "pings_raster2d_debug_lists": (i32, [vp, i64, i32, i32, vp, vp, vp]),
+    "pings_raster2d_debug_image": (i32, [vp, i32, i32, vp, vp, vp, vp]),
+    # neural-point kNN, query_feature, SDF decode
+    "pings_knn_compact_entries": (sz, [i64]),
+    "pings_knn_compact_build": (i32, [vp, i64, vp, sz, vp]),
+    "pings_knn_blocks_entries": (sz, [i64]),
+    "pings_knn_blocks_build": (i32, [C.POINTER(KnnMap), i64, i64, i32, vp, sz, vp, vp, vp]),
+    "pings_knn_search": (i32, [C.POINTER(KnnMap), vp, i64, vp, vp, vp, vp, vp]),
+    "pings_knn_cells": (i32, [C.POINTER(KnnMap), vp, i64, i64, vp, vp, vp]),
+    "pings_query_feature_forward": (i32, [C.POINTER(KnnMap), C.POINTER(QfTables), vp, i64, vp, vp, vp, vp, vp, vp, vp,
+                                          vp, vp, vp, vp, vp]),
+    "pings_query_feature_accumulate": (i32, [vp, vp, i64, vp, vp]),
+    "pings_query_feature_scratch_bytes": (sz, [i64, i32, i64]),
+    "pings_query_feature_backward": (i32, [C.POINTER(QfTables), vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, i64, vp, vp,
+                                           vp, vp, vp]),
+    "pings_query_feature_double_backward": (i32, [C.POINTER(QfTables), vp, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                  i64, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pings_rows_scatter_add_scratch_bytes": (sz, [i64, i64]),
+    "pings_rows_scatter_add": (i32, [vp, i64, vp, i64, i32, vp, vp, i64, vp, vp, vp]),
+    "pings_rows_plan_bytes": (sz, [i64, i64]),
+    "pings_rows_plan_build": (i32, [vp, i64, i64, vp, vp]),
+    "pings_rows_plan_apply": (i32, [vp, i64, i64, vp, i64, i32, vp, vp, vp]),
+    "pings_sdf_forward": (i32, [C.POINTER(KnnMap), C.POINTER(SdfDecoder), vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp,
+                                vp, vp, vp, vp, vp]),
+    "pings_sdf_backward_scratch_bytes": (sz, [i64, i32, i32, i32, i64]),
+    "pings_sdf_double_backward": (i32, [C.POINTER(SdfDecoder), vp, i64, vp, vp, vp, i32, vp, i64, i32, vp, vp, vp, vp,
+                                        vp, vp, vp, vp, vp, vp, vp]),
+    "pings_sdf_backward": (i32, [C.POINTER(SdfDecoder), vp, i64, vp, vp, i32, vp, i64, i32, vp, vp, vp, vp, vp, vp, vp,
+                                 vp, vp, vp]),
+    # decoder MLP
+    "pings_mlp_backward_scratch_bytes": (sz, [i32, i32, i32]),
+    "pings_mlp_forward": (i32, [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]),
+    "pings_mlp_backward": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pings_mlp_double_backward_supported": (i32, [i32, i32, i32]),
+    "pings_mlp_double_backward": (i32, [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pings_mlp_forward_grouped": (i32, [C.POINTER(MlpJob), i32, i64, vp]),
+    "pings_mlp_forward_grouped_dyn": (i32, [C.POINTER(MlpJob), i32, i64, vp, vp]),
+    "pings_mlp_backward_grouped_scratch_bytes": (sz, [C.POINTER(MlpJob), i32]),
+    "pings_mlp_backward_grouped": (i32, [C.POINTER(MlpJob), i32, i64, vp, vp]),
+    # exposure correction
+    "pings_exposure_forward": (i32, [vp, vp, vp, i64, vp, vp]),
+    "pings_exposure_backward_scratch_bytes": (sz, []),
+    "pings_exposure_backward": (i32, [vp, vp, vp, i64, vp, vp, vp, vp, vp]),
+    # finite-difference SDF gradient
+    "pings_stencil_points": (i32, [vp, i64, f32, i32, vp, vp]),
+    "pings_stencil_gradient": (i32, [vp, vp, i64, f32, i32, vp, vp]),
+    "pings_stencil_gradient_backward": (i32, [vp, i64, f32, i32, vp, vp, vp]),
+    # spawn_gaussians
+    "pings_spawn_gather": (i32, [i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp,
+                                 vp, vp]),
+    "pings_spawn_gather_dyn": (i32, [i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32, vp, vp, vp, vp,
+                                     vp, vp, vp, vp]),
+    "pings_spawn_plan_dyn": (i32, [C.POINTER(SpawnParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pings_spawn_forward_dyn": (i32, [C.POINTER(SpawnParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                      vp, vp, vp, vp, vp, vp, vp]),
+    "pings_spawn_gather_backward": (i32, [i32, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp]),
+    "pings_spawn_plan_scratch_bytes": (sz, [i64]),
+    "pings_spawn_plan": (i32, [C.POINTER(SpawnParams), vp, vp, vp, vp, vp, vp, vp]),
+    "pings_spawn_forward": (i32, [C.POINTER(SpawnParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                  vp, vp, vp, vp]),
+    "pings_spawn_backward": (i32, [C.POINTER(SpawnParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                   vp, vp, vp, vp, vp, vp]),
+    # neural-point map maintenance
+    "pings_voxel_downsample_scratch_bytes": (sz, [i64]),
+    "pings_voxel_downsample": (i32, [vp, i64, f32, vp, vp, C.POINTER(i64), vp]),
+    "pings_voxel_downsample_min_value": (i32, [vp, vp, i64, f32, vp, vp, C.POINTER(i64), vp]),
+    "pings_map_prune_mask": (i32, [i64, vp, i64, i32, vp, vp, f32, f32, vp, vp, vp]),
+    "pings_map_adjust": (i32, [i64, vp, vp, vp, vp, i32, vp, i32, i64, vp, vp]),
+    "pings_map_rehash": (i32, [vp, vp, i64, f32, i64, vp, vp, vp]),
+    "pings_map_update_scratch_bytes": (sz, [i64, i64]),
+    "pings_map_update": (i32, [vp, vp, i64, f32, i64, vp, i64, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                               vp, vp, C.POINTER(i64), vp]),
+    "pings_map_reset_local_scratch_bytes": (sz, [i64]),
+    "pings_map_reset_local": (i32, [i64, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp,
+                                    C.POINTER(i64), vp]),
+    "pings_mask_rows_scratch_bytes": (sz, [i64]),
+    "pings_mask_rows": (i32, [vp, i64, vp, vp, C.POINTER(i64), vp]),
+    "pings_gather_rows_multi": (i32, [C.POINTER(GatherJob), i32, vp, vp]),
+    "pings_gather_rows": (i32, [vp, i64, vp, i64, vp, vp]),
+    "pings_scatter_rows": (i32, [vp, i64, vp, i64, vp, vp]),
+    # depth2normal
+    "pings_depth2normal_forward": (i32, [vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp]),
+    "pings_depth2normal_backward_scratch_bytes": (sz, [i32, i32]),
+    "pings_depth2normal_backward": (i32, [vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp]),
+    # image-space losses
+    "pings_image_losses_scratch_bytes": (sz, []),
+    "pings_image_losses_forward": (i32, [C.POINTER(ImageLossParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "pings_image_losses_backward": (i32, [C.POINTER(ImageLossParams), vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                          vp, vp, vp, vp]),
+    # colour / semantic heads
+    "pings_head_reduce": (i32, [vp, vp, i64, i32, i32, i32, vp, vp, vp]),
+    # tracker registration
+    "pings_reg_normal_equations_scratch_bytes": (sz, []),
+    "pings_reg_normal_equations": (i32, [vp, vp, vp, vp, i64, vp, vp, vp]),
+    "pings_reg_solve": (i32, [vp, f32, vp, vp, vp]),
+    "pings_reg_solve_checked": (i32, [vp, f32, vp, vp, vp, C.POINTER(i32), vp]),
+    # device-resident odometry loop
+    "pings_reg_partials": (i32, [i64]),
+    "pings_reg_transform": (i32, [C.POINTER(RegLoopArgs), vp]),
+    "pings_reg_assemble": (i32, [C.POINTER(RegLoopArgs), vp]),
+    "pings_reg_step": (i32, [C.POINTER(RegLoopArgs), vp]),
+    "pings_reg_read_record": (i32, [vp, vp, vp]),
+    # Gaussian-space loss block
+    "pings_gauss_loss_select": (i32, [C.POINTER(GaussLossArgs), vp]),
+    "pings_gauss_loss_prepare": (i32, [C.POINTER(GaussLossArgs), vp]),
+    "pings_gauss_loss_reduce": (i32, [C.POINTER(GaussLossArgs), vp]),
+    "pings_gauss_loss_backward_rows": (i32, [C.POINTER(GaussLossArgs), vp]),
+    "pings_gauss_loss_backward_scatter": (i32, [C.POINTER(GaussLossArgs), vp]),
+    "pings_sdf_hvp_x": (i32, [C.POINTER(SdfHvpArgs), vp]),
+    # SDF-sample loss block
+    "pings_sdf_loss_select": (i32, [C.POINTER(SdfLossArgs), vp]),
+    "pings_sdf_loss_reduce": (i32, [C.POINTER(SdfLossArgs), vp]),
+    "pings_sdf_loss_backward": (i32, [C.POINTER(SdfLossArgs), vp]),
+    "pings_sdf_loss_partials": (i32, [i64, i64]),
+}

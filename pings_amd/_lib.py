@@ -6,10 +6,11 @@ made with tensors that are not on a HIP device, this module raises.
 from __future__ import annotations
 
 import ctypes as C
-import re
 from pathlib import Path
 
 import torch
+
+from . import _abi
 
 PKG = Path(__file__).resolve().parent
 # PINGS_HIP_LIB: another build of the same library (A/B timing of kernel variants; never set in production)
@@ -20,30 +21,12 @@ if _os.environ.get("PINGS_HIP_LIB"):
     import warnings as _warnings
 
     _warnings.warn(f"pings_amd: loading the HIP library from PINGS_HIP_LIB={LIB_PATH} (A/B timing only)")
-HEADER = PKG.parent / "include" / "pings_hip.h"
 
 _lib = None
-
-c_fp = C.c_void_p  # device pointers travel as integers (tensor.data_ptr())
 
 
 class PingsHipError(RuntimeError):
     pass
-
-
-def header_symbols() -> list[str]:
-    """Names of every PINGS_API function declared in include/pings_hip.h."""
-    txt = HEADER.read_text()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return re.findall(r"PINGS_API\s+[\w\s\*]+?\b(pings_\w+)\s*\(", txt)
-
-
-def expected_abi() -> int:
-    """PINGS_ABI_VERSION of the header this package's ctypes signatures were written against."""
-    m = re.search(r"#define\s+PINGS_ABI_VERSION\s+(\d+)", HEADER.read_text())
-    if not m:
-        raise PingsHipError(f"{HEADER} does not define PINGS_ABI_VERSION")
-    return int(m.group(1))
 
 
 def lib() -> C.CDLL:
@@ -54,28 +37,18 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -m pings_amd.build` "
                 "(or __graft_entry__.build()). There is no CPU fallback for the HIP path.")
         l = C.CDLL(str(LIB_PATH))
-        _declare(l)
+        for name, (restype, argtypes) in _abi.SIGNATURES.items():
+            if hasattr(l, name):    # an older PINGS_HIP_LIB build fails only when a missing entry point is called
+                f = getattr(l, name)
+                f.restype, f.argtypes = restype, argtypes
         # a stale libpings_hip.so (or a PINGS_HIP_LIB A/B build of another revision) would be called with this
         # package's argtypes: refuse it here instead of passing mismatched arguments into kernels
-        got, want = l.pings_abi_version(), expected_abi()
-        if got != want:
-            raise PingsHipError(f"{LIB_PATH} reports ABI version {got}, this package binds version {want} "
-                                f"(include/pings_hip.h): rebuild with `python -m pings_amd.build`")
+        got = l.pings_abi_version()
+        if got != _abi.ABI_VERSION:
+            raise PingsHipError(f"{LIB_PATH} reports ABI version {got}, this package binds version "
+                                f"{_abi.ABI_VERSION} (pings_amd/_abi.py): rebuild with `python -m pings_amd.build`")
         _lib = l
     return _lib
-
-
-def _declare(l: C.CDLL) -> None:
-    l.pings_abi_version.restype = C.c_int
-    l.pings_last_error.restype = C.c_char_p
-    l.pings_ssim_partials_count.restype = C.c_size_t
-    l.pings_ssim_partials_count.argtypes = [C.c_int] * 3
-    l.pings_ssim_forward.restype = C.c_int
-    l.pings_ssim_forward.argtypes = [c_fp, c_fp, C.c_int, C.c_int, C.c_int, C.c_int,
-                                     c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
-    l.pings_ssim_backward.restype = C.c_int
-    l.pings_ssim_backward.argtypes = [c_fp, c_fp, C.c_int, C.c_int, C.c_int,
-                                      c_fp, c_fp, c_fp, c_fp, c_fp, c_fp]
 
 
 def check(status: int, what: str) -> None:

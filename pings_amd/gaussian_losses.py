@@ -20,45 +20,11 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from . import neural_points as _np
 
 GS_TYPES = {"gaussian_surfel": (2, 3, 2), "3d_gs": (3, 3, 3), "2d_gs": (2, 2, 2)}   # ncols, scale columns, voxel power
 F_OPACITY, F_ENT, F_ISO, F_AREA, F_SDF = 1, 2, 4, 8, 16
-vp = C.c_void_p
-
-
-class _Args(C.Structure):
-    _fields_ = [("P", C.c_int64), ("Na", C.c_int64), ("cap", C.c_int64), ("R", C.c_int32), ("ncols", C.c_int32),
-                ("scale_cols", C.c_int32), ("flags", C.c_int32), ("min_alpha", C.c_float),
-                ("contrib_thr", C.c_float), ("shift_range", C.c_float), ("grad_min", C.c_float),
-                ("grad_max", C.c_float), ("inv_voxel_pow", C.c_float), ("n_inject", C.c_int64)] + \
-               [(n, vp) for n in ("alpha_all", "visible", "contrib", "free_mask", "xyz", "rot", "scale", "alpha", "seed",
-                                  "inject_idx", "randn", "keys", "part", "meta", "idx", "normal", "queries", "label",
-                                  "sdf", "grad", "nn", "valid", "losses", "counts", "g", "ds", "v", "dn", "dq",
-                                  "d_xyz", "d_rot", "d_scale", "d_alpha", "d_alpha_all")]
-
-
-class _HvpArgs(C.Structure):
-    _fields_ = [("W1", vp), ("b1", vp), ("W2", vp), ("b2", vp), ("H", C.c_int32), ("F", C.c_int32),
-                ("scale", C.c_float), ("after_pgo", C.c_int32), ("features", vp), ("points", vp),
-                ("orientations", vp), ("gpoints", vp), ("queries", vp), ("B", C.c_int64), ("nnk", C.c_int32),
-                ("idx", vp), ("gidx", vp), ("v", vp), ("ds", vp), ("grad_x", vp), ("out", vp)]
-
-
-def _declare(L):
-    if getattr(L, "_gloss_declared", False):
-        return
-    if not hasattr(L, "pings_sdf_hvp_x"):     # an ABI-9 library built before this block existed
-        raise _lib.PingsHipError(f"{_lib.LIB_PATH} has no pings_gauss_loss_* entry points: rebuild it with "
-                                 "`python -m pings_amd.build`")
-    for n in ("select", "prepare", "reduce", "backward_rows", "backward_scatter"):
-        f = getattr(L, "pings_gauss_loss_" + n)
-        f.restype, f.argtypes = C.c_int, [C.POINTER(_Args), vp]
-    L.pings_sdf_hvp_x.restype, L.pings_sdf_hvp_x.argtypes = C.c_int, [C.POINTER(_HvpArgs), vp]
-    L.pings_sdf_backward_scratch_bytes.restype = C.c_size_t
-    L.pings_sdf_backward_scratch_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64]
-    L._gloss_declared = True
 
 
 class GaussianLosses(NamedTuple):
@@ -97,8 +63,7 @@ def _f32(t):
 class _Block(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz, rot, scale, alpha, alpha_all, feats, W1, b1, W2, b2, st):
-        L = _np._L()
-        _declare(L)
+        L = _lib.lib()
         dev = xyz.device
         a = st["args"]
         P, cap, R = int(a.P), int(a.cap), int(a.R)
@@ -200,10 +165,10 @@ class _Block(torch.autograd.Function):
                 gW1, gb1 = p[:H * (F + 3)].view(H, F + 3), p[H * (F + 3):H * (F + 4)]
                 gW2, gb2 = p[H * (F + 4):H * (F + 5)].view(1, H), p[H * (F + 5):]
             if ctx.need[0] or ctx.need[1]:
-                h = _HvpArgs(dec.W1, dec.b1, dec.W2, dec.b2, H, F, dec.sdf_scale, ap, f.data_ptr(), pts.data_ptr(),
-                             quat.data_ptr(), gpts.data_ptr(), q, rows, nnk, B["nidx"].data_ptr(),
-                             B["gidx"].data_ptr(), O["v"].data_ptr(), O["ds"].data_ptr(), B["grad"].data_ptr(),
-                             O["dq"].data_ptr())
+                h = _abi.SdfHvpArgs(dec.W1, dec.b1, dec.W2, dec.b2, H, F, dec.sdf_scale, ap, f.data_ptr(),
+                                    pts.data_ptr(), quat.data_ptr(), gpts.data_ptr(), q, rows, nnk, B["nidx"].data_ptr(),
+                                    B["gidx"].data_ptr(), O["v"].data_ptr(), O["ds"].data_ptr(), B["grad"].data_ptr(),
+                                    O["dq"].data_ptr())
                 _lib.check(L.pings_sdf_hvp_x(C.byref(h), stream), "pings_sdf_hvp_x")
             else:
                 O["dq"].zero_()
@@ -260,9 +225,10 @@ def gaussian_losses(self, render_pkg: dict, *, gs_type: str, opacity: bool = Tru
     dev = xyz.device
     flags = (F_OPACITY * opacity) | (F_ENT * opacity_ent) | (F_ISO * bool(isotropic)) | (F_AREA * bool(area)) | \
             (F_SDF * bool(sdf_consistency))
-    a = _Args(P, alpha_all.numel(), cap, R, ncols, scols, flags, float(cfg.min_alpha),
-              float(cfg.gs_contribution_threshold), float(cfg.gs_consist_shift_range_m),
-              float(cfg.valid_grad_min_thre), float(cfg.valid_grad_max_thre), float(1.0 / cfg.voxel_size_m ** vpow), -1)
+    a = _abi.GaussLossArgs(P, alpha_all.numel(), cap, R, ncols, scols, flags, float(cfg.min_alpha),
+                           float(cfg.gs_contribution_threshold), float(cfg.gs_consist_shift_range_m),
+                           float(cfg.valid_grad_min_thre), float(cfg.valid_grad_max_thre),
+                           float(1.0 / cfg.voxel_size_m ** vpow), -1)
     keep = {"vis": vis.detach().to(torch.uint8).contiguous(), "contrib": contrib,
             "free": None if free is None else free.detach().to(torch.uint8).contiguous()}
     a.visible, a.contrib, a.free_mask = (_lib.ptr(keep[k]) for k in ("vis", "contrib", "free"))
@@ -296,8 +262,8 @@ def gaussian_losses(self, render_pkg: dict, *, gs_type: str, opacity: bool = Tru
         m = _np._map_args(npm, bool(npm.temporal_local_map_on), True, False, True)
         fc, W1c, b1c, W2c, b2c = (_f32(t) for t in (feats, W1, b1, W2, b2))
         st.update(map=m, nnk=int(m.nn_k), feats=feats, feats_c=fc, params=(W1c, b1c, W2c, b2c),
-                  dec=_np._CDecoder(W1c.data_ptr(), b1c.data_ptr(), W2c.data_ptr(), b2c.data_ptr(), int(W1c.shape[0]),
-                                    int(fc.shape[1]), float(dec.sdf_scale), 0),
+                  dec=_abi.SdfDecoder(W1c.data_ptr(), b1c.data_ptr(), W2c.data_ptr(), b2c.data_ptr(), int(W1c.shape[0]),
+                                      int(fc.shape[1]), float(dec.sdf_scale), 0),
                   pts=_f32(npm.local_neural_points), quat=_f32(npm.local_point_orientations),
                   gpts=_f32(npm.neural_points), after_pgo=bool(npm.after_pgo))
         if W1c.shape[1] != fc.shape[1] + 3:

@@ -16,28 +16,9 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
 CONSIST_MODES = {"both": 0, "normal_fixed": 1, "depth_fixed": 2}
-
-
-class _Params(C.Structure):
-    _fields_ = [("H", C.c_int), ("W", C.c_int), ("v_min", C.c_int), ("v_max", C.c_int), ("depth_min", C.c_float),
-                ("depth_max", C.c_float), ("min_accu_alpha", C.c_float), ("inverse_depth", C.c_int),
-                ("consist_mode", C.c_int)]
-
-
-def _declare(L):
-    if getattr(L, "_imgloss_declared", False):
-        return
-    vp = C.c_void_p
-    L.pings_image_losses_scratch_bytes.restype = C.c_size_t
-    L.pings_image_losses_scratch_bytes.argtypes = []
-    L.pings_image_losses_forward.restype = C.c_int
-    L.pings_image_losses_forward.argtypes = [C.POINTER(_Params)] + [vp] * 12
-    L.pings_image_losses_backward.restype = C.c_int
-    L.pings_image_losses_backward.argtypes = [C.POINTER(_Params)] + [vp] * 16
-    L._imgloss_declared = True
 
 
 class ImageLosses(NamedTuple):
@@ -52,7 +33,6 @@ class _Losses(torch.autograd.Function):
     @staticmethod
     def forward(ctx, prm, rgb, gt_rgb, depth, gt_depth, alpha, normal, dnormal, sky):
         L = _lib.lib()
-        _declare(L)
         dev = rgb.device
         f = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
         planes = [f(rgb), f(gt_rgb), f(depth), f(gt_depth), f(alpha), f(normal), f(dnormal),
@@ -104,8 +84,8 @@ def image_losses(rendered_rgb: torch.Tensor, gt_rgb: torch.Tensor, rendered_dept
         raise _lib.PingsHipError("image_losses runs on the HIP device only (got a CPU tensor); there is no CPU fallback")
     _, H, W = rendered_rgb.shape
     v0, v1, _ = slice(pixel_v_min, pixel_v_max).indices(H)
-    prm = _Params(H, W, v0, max(v0, v1), depth_min, min(depth_max, 3.0e38), depth_min_accu_alpha,
-                  int(bool(inverse_depth_loss)), CONSIST_MODES[consist])
+    prm = _abi.ImageLossParams(H, W, v0, max(v0, v1), depth_min, min(depth_max, 3.0e38), depth_min_accu_alpha,
+                               int(bool(inverse_depth_loss)), CONSIST_MODES[consist])
     for name, t, c in (("gt_rgb", gt_rgb, 3), ("rendered_depth", rendered_depth, 1), ("gt_depth", gt_depth, 1),
                        ("rendered_alpha", rendered_alpha, 1), ("rendered_normal", rendered_normal, 3),
                        ("depth_normal", depth_normal, 3), ("sky_mask", sky_mask, 1)):

@@ -1,31 +1,15 @@
 """Image-space operators of `render` on the HIP device (csrc/image_ops.hip)."""
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
 from . import _lib
-
-
-def _declare(L):
-    if getattr(L, "_img_declared", False):
-        return
-    vp, i32, f32 = C.c_void_p, C.c_int, C.c_float
-    L.pings_depth2normal_forward.restype = C.c_int
-    L.pings_depth2normal_forward.argtypes = [vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp]
-    L.pings_depth2normal_backward_scratch_bytes.restype = C.c_size_t
-    L.pings_depth2normal_backward_scratch_bytes.argtypes = [i32, i32]
-    L.pings_depth2normal_backward.restype = C.c_int
-    L.pings_depth2normal_backward.argtypes = [vp, vp, vp, i32, i32, f32, f32, f32, f32, f32, vp, vp, vp, vp]
-    L._img_declared = True
 
 
 class _Depth2Normal(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth, mask, weight, cx, cy, fx, fy):
         L = _lib.lib()
-        _declare(L)
         # (round 2 cloned the depth here because `render` then normalised it in place, :430-437; it no longer does)
         d = depth.detach()
         if d.dtype != torch.float32 or not d.is_contiguous():
@@ -87,7 +71,6 @@ class _ExposureAffine(torch.autograd.Function):
     @staticmethod
     def forward(ctx, img, M, b):
         L = _lib.lib()
-        _declare_exposure(L)
         x = img.detach().to(torch.float32).contiguous()
         Mc, bc = M.detach().to(torch.float32).contiguous(), b.detach().to(torch.float32).contiguous()
         out = torch.empty_like(x)
@@ -112,20 +95,6 @@ class _ExposureAffine(torch.autograd.Function):
                                              g_img.data_ptr() if g_img is not None else None, gMb.data_ptr(),
                                              gMb.data_ptr() + 36, _lib.stream_ptr(dev)), "pings_exposure_backward")
         return g_img, gMb[:9].view(3, 3), gMb[9:]
-
-
-def _declare_exposure(L):
-    if getattr(L, "_exposure_declared", False):
-        return
-    import ctypes as C
-    vp = C.c_void_p
-    L.pings_exposure_forward.restype = C.c_int
-    L.pings_exposure_forward.argtypes = [vp, vp, vp, C.c_int64, vp, vp]
-    L.pings_exposure_backward_scratch_bytes.restype = C.c_size_t
-    L.pings_exposure_backward_scratch_bytes.argtypes = []
-    L.pings_exposure_backward.restype = C.c_int
-    L.pings_exposure_backward.argtypes = [vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
-    L._exposure_declared = True
 
 
 def exposure_affine(img: torch.Tensor, exposure_mat: torch.Tensor, exposure_offset: torch.Tensor) -> torch.Tensor:

@@ -15,21 +15,15 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from . import neural_points as _np
 
 
 def head_reduce(raw: torch.Tensor, w_knn, mode: int):
     """`pings_head_reduce` (csrc/heads.hip): raw = decoder outputs [B, k, C] (per-neighbour) or [B, C] (`weighted_first`),
-    w_knn = IDW weights [B, k, 1] or None.  mode 0 -> colours [B, C]; mode 1 -> int64 labels [B]."""
-    import ctypes as C
-
+    w_knn = IDW weights [B, k, 1] or None.  mode _abi.HEAD_COLOR -> colours [B, C]; _abi.HEAD_SEMANTIC -> int64
+    labels [B]."""
     L = _lib.lib()
-    if not getattr(L, "_head_declared", False):
-        L.pings_head_reduce.restype = C.c_int
-        L.pings_head_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]
-        L._head_declared = True
     raw = raw.detach().to(torch.float32).contiguous()
     if raw.dim() == 2:
         B, k, Cn, w = raw.shape[0], 1, raw.shape[1], None
@@ -37,11 +31,11 @@ def head_reduce(raw: torch.Tensor, w_knn, mode: int):
         B, k, Cn = raw.shape
         w = None if w_knn is None else w_knn.detach().to(torch.float32).reshape(B, k).contiguous()
     dev = raw.device
-    val = torch.empty(B, Cn, device=dev) if mode == 0 else None
-    lab = torch.empty(B, dtype=torch.int64, device=dev) if mode == 1 else None
+    val = torch.empty(B, Cn, device=dev) if mode == _abi.HEAD_COLOR else None
+    lab = torch.empty(B, dtype=torch.int64, device=dev) if mode == _abi.HEAD_SEMANTIC else None
     _lib.check(L.pings_head_reduce(_lib.ptr(raw), _lib.ptr(w), B, k, Cn, mode, _lib.ptr(val), _lib.ptr(lab),
                                    _lib.stream_ptr(dev)), "pings_head_reduce")
-    return val if mode == 0 else lab
+    return val if mode == _abi.HEAD_COLOR else lab
 
 
 def query_points(self, coord, bs, query_sdf=True, query_sem=False, query_color=False, query_mask=True,
@@ -82,9 +76,9 @@ def query_points(self, coord, bs, query_sdf=True, query_sem=False, query_color=F
                                                         use_only_valid_points=True)
                 wk = None if self.config.weighted_first else w_knn
                 if query_color:
-                    color[head:tail] = head_reduce(_dec.mlp(self.color_mlp, cf), wk, 0)
+                    color[head:tail] = head_reduce(_dec.mlp(self.color_mlp, cf), wk, _abi.HEAD_COLOR)
                 if query_sem:
-                    sem[head:tail] = head_reduce(_dec.mlp(self.sem_mlp, gf), wk, 1).to(sem.dtype)
+                    sem[head:tail] = head_reduce(_dec.mlp(self.sem_mlp, gf), wk, _abi.HEAD_SEMANTIC).to(sem.dtype)
     if out_torch:
         host = lambda t: None if t is None else t.cpu()
     else:

@@ -6,42 +6,9 @@ layer, so nothing but the inputs is kept alive between the passes.  Used for the
 """
 from __future__ import annotations
 
-import ctypes as C
-
 import torch
 
-from . import _lib
-
-
-class _CJob(C.Structure):
-    _fields_ = [("x", C.c_void_p), ("IN", C.c_int32), ("OUT", C.c_int32), ("W1", C.c_void_p), ("b1", C.c_void_p),
-                ("W2", C.c_void_p), ("b2", C.c_void_p), ("y", C.c_void_p), ("dL_dy", C.c_void_p), ("dL_dx", C.c_void_p),
-                ("dL_dW1", C.c_void_p), ("dL_db1", C.c_void_p), ("dL_dW2", C.c_void_p), ("dL_db2", C.c_void_p)]
-
-
-def _declare(L):
-    if getattr(L, "_mlp_declared", False):
-        return
-    vp, i64, i32 = C.c_void_p, C.c_int64, C.c_int
-    L.pings_mlp_backward_scratch_bytes.restype = C.c_size_t
-    L.pings_mlp_backward_scratch_bytes.argtypes = [i32, i32, i32]
-    L.pings_mlp_forward.restype = C.c_int
-    L.pings_mlp_forward.argtypes = [vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-    L.pings_mlp_backward.restype = C.c_int
-    L.pings_mlp_backward.argtypes = [vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pings_mlp_double_backward_supported.restype = C.c_int
-    L.pings_mlp_double_backward_supported.argtypes = [i32, i32, i32]
-    L.pings_mlp_double_backward.restype = C.c_int
-    L.pings_mlp_double_backward.argtypes = [vp, vp, vp, i64, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pings_mlp_forward_grouped.restype = C.c_int
-    L.pings_mlp_forward_grouped.argtypes = [C.POINTER(_CJob), i32, i64, vp]
-    L.pings_mlp_forward_grouped_dyn.restype = C.c_int
-    L.pings_mlp_forward_grouped_dyn.argtypes = [C.POINTER(_CJob), i32, i64, vp, vp]
-    L.pings_mlp_backward_grouped_scratch_bytes.restype = C.c_size_t
-    L.pings_mlp_backward_grouped_scratch_bytes.argtypes = [C.POINTER(_CJob), i32]
-    L.pings_mlp_backward_grouped.restype = C.c_int
-    L.pings_mlp_backward_grouped.argtypes = [C.POINTER(_CJob), i32, i64, vp, vp]
-    L._mlp_declared = True
+from . import _abi, _lib
 
 
 def supported(IN: int, HID: int, OUT: int) -> bool:
@@ -56,7 +23,6 @@ def _f32c(t):
 def _hip_backward(x, W1, b1, W2, gy, need_x):
     """`pings_mlp_backward` on detached fp32 views: (gx or None, gW1, gb1, gW2, gb2)."""
     L = _lib.lib()
-    _declare(L)
     xs, W1c, b1c, W2c = _f32c(x), _f32c(W1), _f32c(b1), _f32c(W2)
     N, IN = xs.shape
     HID, OUT = W1c.shape[0], W2c.shape[0]
@@ -139,7 +105,6 @@ class _FusedMLP(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, W1, b1, W2, b2):
         L = _lib.lib()
-        _declare(L)
         xs, W1c, b1c, W2c, b2c = _f32c(x), _f32c(W1), _f32c(b1), _f32c(W2), _f32c(b2)
         N, IN = xs.shape
         HID, OUT = W1c.shape[0], W2c.shape[0]
@@ -183,19 +148,18 @@ class _FusedMLPGroup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, J, fc, *args):
         L = _lib.lib()
-        _declare(L)
         xs = [_f32c(t) for t in args[:J]]      # (detach only: the shipped decoders are fp32 and contiguous already)
         ps = [_f32c(t) for t in args[J:]]
         N = xs[0].shape[0]
         dev = xs[0].device
-        jobs = (_CJob * J)()
+        jobs = (_abi.MlpJob * J)()
         ys = []
         for g in range(J):
             W1, b1, W2, b2 = ps[4 * g:4 * g + 4]
             y = torch.empty(N, W2.shape[0], dtype=torch.float32, device=dev)
             ys.append(y)
-            jobs[g] = _CJob(xs[g].data_ptr(), xs[g].shape[1], W2.shape[0], W1.data_ptr(), b1.data_ptr(), W2.data_ptr(),
-                            b2.data_ptr(), y.data_ptr(), None, None, None, None, None, None)
+            jobs[g] = _abi.MlpJob(xs[g].data_ptr(), xs[g].shape[1], W2.shape[0], W1.data_ptr(), b1.data_ptr(),
+                                  W2.data_ptr(), b2.data_ptr(), y.data_ptr(), None, None, None, None, None, None)
         # fc (render_core.FrameCounts): N is the capacity, the rows to decode are counted on the device
         _lib.check(L.pings_mlp_forward_grouped_dyn(jobs, J, N, fc.n_dev.data_ptr() if fc is not None else None,
                                                    _lib.stream_ptr(dev)), "pings_mlp_forward_grouped")
@@ -215,7 +179,7 @@ class _FusedMLPGroup(torch.autograd.Function):
         n_rows = ctx.fc.n_sel if ctx.fc is not None else N      # exact since the frame's read-back
         dev = xs[0].device
         f32 = dict(dtype=torch.float32, device=dev)
-        jobs = (_CJob * J)()
+        jobs = (_abi.MlpJob * J)()
         gxs, gps, keep = [], [], []
         # ONE buffer for the 4 J parameter gradients (views handed to autograd), one for the input gradients
         sizes = []
@@ -252,8 +216,8 @@ class _FusedMLPGroup(torch.autograd.Function):
             p_off += s0 + s1 + s2 + s3
             gxs.append(gx)
             gps += [parts[4 * g].view(128, IN), parts[4 * g + 1], parts[4 * g + 2].view(OUT, 128), parts[4 * g + 3]]
-            jobs[g] = _CJob(xs[g].data_ptr(), IN, OUT, W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), None,
-                            gy.data_ptr(), gx_ptr, *ptrs)
+            jobs[g] = _abi.MlpJob(xs[g].data_ptr(), IN, OUT, W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(),
+                                  None, gy.data_ptr(), gx_ptr, *ptrs)
         scratch = torch.empty(L.pings_mlp_backward_grouped_scratch_bytes(jobs, J), dtype=torch.uint8, device=dev)
         _lib.check(L.pings_mlp_backward_grouped(jobs, J, n_rows, scratch.data_ptr(), _lib.stream_ptr(dev)),
                    "pings_mlp_backward_grouped")

@@ -20,7 +20,7 @@ from types import SimpleNamespace
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
 _ROW_ATTRS = {  # attribute -> (columns, dtype)
     "neural_points": (3, torch.float32), "point_orientations": (4, torch.float32),
@@ -28,54 +28,6 @@ _ROW_ATTRS = {  # attribute -> (columns, dtype)
     "point_certainties": (0, torch.float32), "free_gs_mask": (0, torch.bool), "valid_gs_mask": (0, torch.bool),
     "valid_color_mask": (0, torch.bool), "point_colors": (3, torch.float32),
 }
-
-
-class _GatherJob(C.Structure):   # include/pings_hip.h: pings_gather_job
-    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("row_bytes", C.c_int64), ("rows", C.c_int64)]
-
-
-def _declare(L):
-    if getattr(L, "_map_declared", False):
-        return
-    vp, i32, i64, f32 = C.c_void_p, C.c_int, C.c_int64, C.c_float
-    L.pings_voxel_downsample_scratch_bytes.restype = C.c_size_t
-    L.pings_voxel_downsample_scratch_bytes.argtypes = [i64]
-    L.pings_voxel_downsample.restype = C.c_int
-    L.pings_voxel_downsample.argtypes = [vp, i64, f32, vp, vp, C.POINTER(i64), vp]
-    L.pings_map_update_scratch_bytes.restype = C.c_size_t
-    L.pings_map_update_scratch_bytes.argtypes = [i64, i64]
-    L.pings_map_update.restype = C.c_int
-    L.pings_map_update.argtypes = [vp, vp, i64, f32, i64, vp, i64, vp, i32, f32, i32] + [vp] * 11 + [C.POINTER(i64), vp]
-    L.pings_map_reset_local_scratch_bytes.restype = C.c_size_t
-    L.pings_map_reset_local_scratch_bytes.argtypes = [i64]
-    L.pings_map_reset_local.restype = C.c_int
-    L.pings_map_reset_local.argtypes = [i64, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, i32, f32, f32,
-                                        vp, vp, vp, vp, vp, C.POINTER(i64), vp]
-    L.pings_voxel_downsample_min_value.restype = C.c_int
-    L.pings_voxel_downsample_min_value.argtypes = [vp, vp, i64, f32, vp, vp, C.POINTER(i64), vp]
-    L.pings_mask_rows_scratch_bytes.restype = C.c_size_t
-    L.pings_mask_rows_scratch_bytes.argtypes = [i64]
-    L.pings_mask_rows.restype = C.c_int
-    L.pings_mask_rows.argtypes = [vp, i64, vp, vp, C.POINTER(i64), vp]
-    L.pings_gather_rows_multi.restype = C.c_int
-    L.pings_gather_rows_multi.argtypes = [C.POINTER(_GatherJob), i32, vp, vp]
-    L.pings_map_prune_mask.restype = C.c_int
-    L.pings_map_prune_mask.argtypes = [i64, vp, i64, i32, vp, vp, f32, f32, vp, vp, vp]
-    L.pings_map_adjust.restype = C.c_int
-    L.pings_map_adjust.argtypes = [i64, vp, vp, vp, vp, i32, vp, i32, i64, vp, vp]
-    L.pings_map_rehash.restype = C.c_int
-    L.pings_map_rehash.argtypes = [vp, vp, i64, f32, i64, vp, vp, vp]
-    L.pings_gather_rows.restype = C.c_int
-    L.pings_gather_rows.argtypes = [vp, i64, vp, i64, vp, vp]
-    L.pings_scatter_rows.restype = C.c_int
-    L.pings_scatter_rows.argtypes = [vp, i64, vp, i64, vp, vp]
-    L._map_declared = True
-
-
-def _L():
-    L = _lib.lib()
-    _declare(L)
-    return L
 
 
 def _need_device(t: torch.Tensor, what: str):
@@ -87,7 +39,7 @@ def voxel_down_sample(points: torch.Tensor, voxel_size: float, value: torch.Tens
     """`voxel_down_sample_torch(points, voxel_size)` (utils/tools.py:924-967) or, with `value`,
     `voxel_down_sample_min_value_torch(points, voxel_size, value)` (:970-1009): int64 indices, one per voxel."""
     _need_device(points, "voxel_down_sample")
-    L = _L()
+    L = _lib.lib()
     pts = points.detach().to(torch.float32).contiguous()
     n = pts.shape[0]
     dev = pts.device
@@ -132,7 +84,7 @@ def update(m, points, colors=None, normals=None, sensor_position=None, sensor_or
     replace the random feature initialisation (tests); by default rows are drawn with `feature_std * randn` like the
     reference.  Returns new_point_ratio; when `sensor_position` is given the local map is reset afterwards (:370-373)."""
     _need_device(points, "NeuralPoints.update")
-    L = _L()
+    L = _lib.lib()
     dev = points.device
     res = float(m.resolution)
     pts = points.detach().to(torch.float32).contiguous()
@@ -217,7 +169,7 @@ def reset_local_map(m, sensor_position, sensor_orientation=None, cur_ts: int = 0
                     diff_ts_local: int = 50):
     """`NeuralPoints.reset_local_map` (model/neural_gaussians.py:378-478)."""
     _need_device(m.neural_points, "NeuralPoints.reset_local_map")
-    L = _L()
+    L = _lib.lib()
     dev = m.neural_points.device
     m.cur_ts = cur_ts
     m.max_ts = max(getattr(m, "max_ts", 0), cur_ts)
@@ -266,7 +218,7 @@ def reset_local_map(m, sensor_position, sensor_orientation=None, cur_ts: int = 0
 
 def assign_local_to_global(m):
     """`NeuralPoints.assign_local_to_global` (model/neural_gaussians.py:482-494)."""
-    L = _L()
+    L = _lib.lib()
     lidx = getattr(m, "_local_idx", None)
     if lidx is None:   # local map set by other code: rebuild the row list from the mask
         lidx = torch.nonzero(m.local_mask).flatten()
@@ -295,7 +247,7 @@ def _mask_rows(L, mask: torch.Tensor):
 
 def _gather_many(L, pairs, idx: torch.Tensor):
     """[(tensor, rows)] -> [tensor[idx[:rows]]], every tensor in one launch."""
-    outs, jobs = [], (_GatherJob * len(pairs))()
+    outs, jobs = [], (_abi.GatherJob * len(pairs))()
     keep = []
     for g, (src, rows) in enumerate(pairs):
         src = src.detach().contiguous()
@@ -305,7 +257,8 @@ def _gather_many(L, pairs, idx: torch.Tensor):
             row *= int(d)
         out = torch.empty((rows,) + tuple(src.shape[1:]), dtype=src.dtype, device=src.device)
         outs.append(out)
-        jobs[g] = _GatherJob(_lib.ptr(_u8(src)) if src.numel() else None, _lib.ptr(_u8(out)) if rows else None, row, rows)
+        jobs[g] = _abi.GatherJob(_lib.ptr(_u8(src)) if src.numel() else None, _lib.ptr(_u8(out)) if rows else None,
+                                 row, rows)
     _lib.check(L.pings_gather_rows_multi(jobs, len(pairs), _lib.ptr(idx), _lib.stream_ptr(idx.device)),
                "pings_gather_rows_multi")
     return outs
@@ -325,7 +278,7 @@ def gather_local_data(m, with_sorroundings: bool = True):
     if not with_sorroundings:
         return data, None
     _need_device(m.neural_points, "NeuralPoints.gather_local_data")
-    L = _L()
+    L = _lib.lib()
     mask = m.sorrounding_mask                                    # [n + 1]; the features take its padding entry too
     n = int(m.neural_points.shape[0])
     if int(mask.shape[0]) != n + 1:
@@ -385,7 +338,7 @@ def prune_map(m, prune_certainty_thre, min_prune_count=500) -> bool:
     """`NeuralPoints.prune_map` (model/neural_gaussians.py:871-909): drops the inactive, uncertain neural points when
     there are more than `min_prune_count` of them; the caller recreates the hash and the local map afterwards."""
     _need_device(m.neural_points, "NeuralPoints.prune_map")
-    L = _L()
+    L = _lib.lib()
     dev = m.neural_points.device
     n = int(m.neural_points.shape[0])
     travel = m.travel_dist.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -416,7 +369,7 @@ def adjust_map(m, pose_diff_torch: torch.Tensor) -> None:
     """`NeuralPoints.adjust_map` (model/neural_gaussians.py:911-937): after loop closure / PGO every neural point is
     moved by the pose correction of its timestamp, in place."""
     _need_device(m.neural_points, "NeuralPoints.adjust_map")
-    L = _L()
+    L = _lib.lib()
     dev = m.neural_points.device
     m.after_pgo = True
     cfg = getattr(m, "config", m)
@@ -449,7 +402,7 @@ def recreate_hash(m, sensor_position: torch.Tensor, sensor_orientation: torch.Te
     to `cur_ts`, or the most certain), the table rebuilt from them; with `kept_points=False` the map itself is reduced
     to the representatives."""
     _need_device(m.neural_points, "NeuralPoints.recreate_hash")
-    L = _L()
+    L = _lib.lib()
     dev = m.neural_points.device
     cfg = getattr(m, "config", m)
     res = float(m.resolution)

@@ -22,91 +22,7 @@ import os
 
 import torch
 
-from . import _lib
-
-
-class _CKnnMap(C.Structure):
-    _fields_ = [
-        ("table", C.c_void_p), ("buffer_size", C.c_int64), ("neural_points", C.c_void_p),
-        ("point_ts_create", C.c_void_p), ("travel_dist", C.c_void_p), ("cur_ts", C.c_int32),
-        ("time_filtering", C.c_int32), ("diff_travel_dist_local", C.c_float),
-        ("free_mask", C.c_void_p), ("valid_mask", C.c_void_p),
-        ("use_free_mask", C.c_int32), ("use_valid_mask", C.c_int32),
-        ("global2local", C.c_void_p), ("neighbor_dx", C.c_void_p), ("K", C.c_int32), ("nn_k", C.c_int32),
-        ("resolution", C.c_float), ("max_valid_dist2", C.c_float),
-        ("compact", C.c_void_p), ("compact_mask", C.c_uint32),
-        ("blocks", C.c_void_p), ("block_records", C.c_void_p), ("blocks_ok", C.c_void_p), ("block_mask", C.c_uint32),
-    ]
-
-
-class _CDecoder(C.Structure):
-    _fields_ = [("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
-                ("hidden", C.c_int32), ("feat_dim", C.c_int32), ("sdf_scale", C.c_float),
-                ("weighted_first", C.c_int32)]
-
-
-class _CQfTables(C.Structure):
-    _fields_ = [("geo_features", C.c_void_p), ("color_features", C.c_void_p), ("Fg", C.c_int32), ("Fc", C.c_int32),
-                ("points", C.c_void_p), ("orientations", C.c_void_p), ("certainties", C.c_void_p),
-                ("after_pgo", C.c_int32), ("weighted_first", C.c_int32)]
-
-
-def _declare(L):
-    if getattr(L, "_knn_declared", False):
-        return
-    vp = C.c_void_p
-    L.pings_query_feature_forward.restype = C.c_int
-    L.pings_query_feature_forward.argtypes = [C.POINTER(_CKnnMap), C.POINTER(_CQfTables), vp, C.c_int64] + [vp] * 12
-    L.pings_query_feature_accumulate.restype = C.c_int
-    L.pings_query_feature_accumulate.argtypes = [vp, vp, C.c_int64, vp, vp]
-    L.pings_query_feature_scratch_bytes.restype = C.c_size_t
-    L.pings_query_feature_scratch_bytes.argtypes = [C.c_int64, C.c_int, C.c_int64]
-    L.pings_query_feature_backward.restype = C.c_int
-    L.pings_query_feature_backward.argtypes = [C.POINTER(_CQfTables), vp, vp, C.c_int64, C.c_int, vp, vp, vp, vp, vp, vp,
-                                               C.c_int64, vp, vp, vp, vp, vp]
-    L.pings_query_feature_double_backward.restype = C.c_int
-    L.pings_query_feature_double_backward.argtypes = [C.POINTER(_CQfTables), vp, vp, C.c_int64, C.c_int] + [vp] * 8 + \
-        [C.c_int64] + [vp] * 9
-    L.pings_rows_plan_bytes.restype = C.c_size_t
-    L.pings_rows_plan_bytes.argtypes = [C.c_int64, C.c_int64]
-    L.pings_rows_plan_build.restype = C.c_int
-    L.pings_rows_plan_build.argtypes = [vp, C.c_int64, C.c_int64, vp, vp]
-    L.pings_rows_plan_apply.restype = C.c_int
-    L.pings_rows_plan_apply.argtypes = [vp, C.c_int64, C.c_int64, vp, C.c_int64, C.c_int32, vp, vp, vp]
-    L.pings_rows_scatter_add_scratch_bytes.restype = C.c_size_t
-    L.pings_rows_scatter_add_scratch_bytes.argtypes = [C.c_int64, C.c_int64]
-    L.pings_rows_scatter_add.restype = C.c_int
-    L.pings_rows_scatter_add.argtypes = [vp, C.c_int64, vp, C.c_int64, C.c_int32, vp, vp, C.c_int64, vp, vp, vp]
-    L.pings_knn_cells.restype = C.c_int
-    L.pings_knn_cells.argtypes = [C.POINTER(_CKnnMap), vp, C.c_int64, C.c_int64, vp, vp, vp]
-    L.pings_knn_search.restype = C.c_int
-    L.pings_knn_search.argtypes = [C.POINTER(_CKnnMap), vp, C.c_int64, vp, vp, vp, vp, vp]
-    L.pings_knn_compact_entries.restype = C.c_size_t
-    L.pings_knn_compact_entries.argtypes = [C.c_int64]
-    L.pings_knn_compact_build.restype = C.c_int
-    L.pings_knn_compact_build.argtypes = [vp, C.c_int64, vp, C.c_size_t, vp]
-    L.pings_knn_blocks_entries.restype = C.c_size_t
-    L.pings_knn_blocks_entries.argtypes = [C.c_int64]
-    L.pings_knn_blocks_build.restype = C.c_int
-    L.pings_knn_blocks_build.argtypes = [C.POINTER(_CKnnMap), C.c_int64, C.c_int64, C.c_int32, vp, C.c_size_t, vp, vp, vp]
-    L.pings_sdf_forward.restype = C.c_int
-    L.pings_sdf_forward.argtypes = [C.POINTER(_CKnnMap), C.POINTER(_CDecoder), vp, vp, vp, vp, C.c_int32, vp,
-                                    C.c_int64, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pings_sdf_double_backward.restype = C.c_int
-    L.pings_sdf_double_backward.argtypes = [C.POINTER(_CDecoder), vp, C.c_int64, vp, vp, vp, C.c_int32, vp, C.c_int64,
-                                            C.c_int, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pings_sdf_backward_scratch_bytes.restype = C.c_size_t
-    L.pings_sdf_backward_scratch_bytes.argtypes = [C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int64]
-    L.pings_sdf_backward.restype = C.c_int
-    L.pings_sdf_backward.argtypes = [C.POINTER(_CDecoder), vp, C.c_int64, vp, vp, C.c_int32, vp, C.c_int64, C.c_int,
-                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L._knn_declared = True
-
-
-def _L():
-    L = _lib.lib()
-    _declare(L)
-    return L
+from . import _abi, _lib
 
 
 def _nn_k(npm):
@@ -175,7 +91,7 @@ def _block_index(npm):
     cache = getattr(npm, "_pings_blocks", None)
     if cache is not None and _same_tensors(cache.src, src) and cache.versions == versions and cache.scalars == scalars:
         return cache
-    L = _L()
+    L = _lib.lib()
     dev = pts.device
     bi = _BlockIndex()
     bi.src, bi.versions, bi.scalars = src, versions, scalars
@@ -193,9 +109,9 @@ def _block_index(npm):
     va8 = _as_u8(valid) if valid is not None else None
     g2lc = g2l.to(torch.int64).contiguous() if g2l is not None else None
     keep += [ts32, td32, fr8, va8, g2lc]
-    m = _CKnnMap(keep[0].data_ptr(), int(table.shape[0]), keep[1].data_ptr(), _lib.ptr(ts32), _lib.ptr(td32), 0, 0, 0.0,
-                 _lib.ptr(fr8), _lib.ptr(va8), 0, 0, _lib.ptr(g2lc), None, 0, 0, float(npm.resolution),
-                 float(npm.max_valid_dist2), None, 0, None, None, None, 0)
+    m = _abi.KnnMap(keep[0].data_ptr(), int(table.shape[0]), keep[1].data_ptr(), _lib.ptr(ts32), _lib.ptr(td32), 0, 0,
+                    0.0, _lib.ptr(fr8), _lib.ptr(va8), 0, 0, _lib.ptr(g2lc), None, 0, 0, float(npm.resolution),
+                    float(npm.max_valid_dist2), None, 0, None, None, None, 0)
     st = L.pings_knn_blocks_build(C.byref(m), N, int(td32.numel()) if td32 is not None else 0, _max_abs_dx(npm),
                                   bi.blocks.data_ptr(), entries, bi.records.data_ptr(), bi.status.data_ptr(),
                                   _lib.stream_ptr(dev))
@@ -214,7 +130,7 @@ def _compact_table(npm):
     cache = getattr(npm, "_pings_compact", None)
     if cache is not None and cache[0] == key and cache[2] is table:
         return cache[1]
-    L = _L()
+    L = _lib.lib()
     entries = L.pings_knn_compact_entries(int(npm.neural_points.shape[0]))
     comp = torch.empty(entries, 2, dtype=torch.int32, device=table.device)
     st = L.pings_knn_compact_build(_lib.ptr(table.contiguous()), int(table.shape[0]), _lib.ptr(comp), entries,
@@ -259,7 +175,7 @@ class _MapArgs:
                     (query_locally and not b["g2l"]):
                 blk = None
         comp = _compact_table(npm) if (index and USE_COMPACT_TABLE and blk is None) else None
-        self.c = _CKnnMap(
+        self.c = _abi.KnnMap(
             k(table.contiguous()), int(table.shape[0]), k(npm.neural_points.contiguous()),
             k(ts.contiguous()) if ts is not None else None, k(td) if td is not None else None,
             int(npm.cur_ts), int(bool(time_filtering)), float(npm.diff_travel_dist_local),
@@ -296,7 +212,7 @@ def radius_neighborhood_topk(npm, points: torch.Tensor, time_filtering: bool = F
 
     Equivalent to `radius_neighborhood_search` (:1061-1115) followed by the masking, counting,
     sort and top-k of `query_feature` (:544-569)."""
-    L = _L()
+    L = _lib.lib()
     pts = points.detach().to(torch.float32).contiguous()
     B = pts.shape[0]
     a = _map_args(npm, time_filtering, use_only_measured_points, use_only_valid_points, query_locally)
@@ -318,7 +234,7 @@ def radius_neighborhood_search(self, points: torch.Tensor, time_filtering: bool 
     (`radius_neighborhood_topk`); this is for the callers that want the raw pair — `query_certainty` (:1117-1133), which
     the mapper runs on every frame's new samples with the one-cell neighbourhood (utils/mapper.py:461-475).  Reads the
     reference's table directly (no search index is built for it: the neighbourhood changes around the call)."""
-    L = _L()
+    L = _lib.lib()
     pts = points.detach().to(torch.float32).contiguous()
     B = int(pts.shape[0])
     a = _MapArgs(self, time_filtering, False, False, False, index=False)
@@ -334,7 +250,7 @@ def rows_scatter_add(dst_row: torch.Tensor, src: torch.Tensor, rows: int, w: tor
                      src_row: torch.Tensor = None, F: int = None) -> torch.Tensor:
     """out[r] = sum over pairs p with dst_row[p] == r (ascending p) of w[p] * src[src_row[p], :F]; [rows, F], bitwise
     reproducible (`pings_rows_scatter_add`: the backward of a row gather without float atomics)."""
-    L = _L()
+    L = _lib.lib()
     if src.dim() == 2 and src.stride(1) == 1 and src.stride(0) >= src.shape[1] and src.is_cuda:
         src2, ld = src, int(src.stride(0))          # a column slice of a row-major table is read where it lies
     else:
@@ -361,14 +277,14 @@ class _QfState:
                  "has_geo", "has_color", "geo_buf", "col_buf", "plan")
 
 
-def _qf_tables(st: _QfState, geo: torch.Tensor, col: torch.Tensor) -> _CQfTables:
+def _qf_tables(st: _QfState, geo: torch.Tensor, col: torch.Tensor) -> _abi.QfTables:
     """C struct for the CURRENT values of the feature tables (the double backward of weighted_first reads them)."""
     t = st.tables
-    return _CQfTables(_lib.ptr(geo) if st.has_geo else None, _lib.ptr(col) if st.has_color else None,
-                      st.Fg if st.has_geo else 0, st.Fc if st.has_color else 0, t["points"].data_ptr(),
-                      t["quat"].data_ptr() if t["quat"] is not None else None,
-                      t["cert"].data_ptr() if t["cert"] is not None else None, int(t["after_pgo"]),
-                      int(st.weighted_first))
+    return _abi.QfTables(_lib.ptr(geo) if st.has_geo else None, _lib.ptr(col) if st.has_color else None,
+                         st.Fg if st.has_geo else 0, st.Fc if st.has_color else 0, t["points"].data_ptr(),
+                         t["quat"].data_ptr() if t["quat"] is not None else None,
+                         t["cert"].data_ptr() if t["cert"] is not None else None, int(t["after_pgo"]),
+                         int(st.weighted_first))
 
 
 def _c32(t):
@@ -377,7 +293,7 @@ def _c32(t):
 
 def _qf_forward(x, geo_tab, col_tab, npm, opts, want_n: bool):
     """Launches `pings_query_feature_forward`; returns (state, geo, colour, w [B,k], n [B,k,3] | None, cnt, cert)."""
-    L = _L()
+    L = _lib.lib()
     (query_ts, accumulate_stability, query_locally, query_geo, query_color, use_meas, use_valid) = opts[:7]
     dev = x.device
     q = _c32(x)
@@ -451,7 +367,7 @@ class _QfBackward(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, g_geo, g_col, g_w, x, geo_tab, col_tab, st: _QfState, need_geo, need_col):
-        L = _L()
+        L = _lib.lib()
         dev = x.device
         q = _c32(x)
         gg, gc, gw = _c32(g_geo), _c32(g_col), _c32(g_w)
@@ -476,7 +392,7 @@ class _QfBackward(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gg_x, gg_gt, gg_ct):
-        L = _L()
+        L = _lib.lib()
         st = ctx.st
         gg, gc, gw, q, geo_c, col_c = ctx.saved_tensors
         dev = q.device
@@ -539,13 +455,13 @@ class _QueryFeature(torch.autograd.Function):
 class _QfGeomBackward(torch.autograd.Function):
     @staticmethod
     def forward(ctx, g_n, g_w, x, st: _QfState):
-        L = _L()
+        L = _lib.lib()
         dev = x.device
         q = _c32(x)
         gn, gw = _c32(g_n), _c32(g_w)
         if gn is None:
             gn = torch.zeros(st.B, st.nn_k, 3, dtype=torch.float32, device=dev)
-        tabs = _qf_tables(st, None, None) if False else _CQfTables(
+        tabs = _qf_tables(st, None, None) if False else _abi.QfTables(
             None, None, 0, 0, st.tables["points"].data_ptr(),
             st.tables["quat"].data_ptr() if st.tables["quat"] is not None else None, None,
             int(st.tables["after_pgo"]), 0)
@@ -563,15 +479,15 @@ class _QfGeomBackward(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, gg_x):
-        L = _L()
+        L = _lib.lib()
         st = ctx.st
         gn, gw, q = ctx.saved_tensors
         dev = q.device
         if gg_x is None:
             return None, None, None, None
-        tabs = _CQfTables(None, None, 0, 0, st.tables["points"].data_ptr(),
-                          st.tables["quat"].data_ptr() if st.tables["quat"] is not None else None, None,
-                          int(st.tables["after_pgo"]), 0)
+        tabs = _abi.QfTables(None, None, 0, 0, st.tables["points"].data_ptr(),
+                             st.tables["quat"].data_ptr() if st.tables["quat"] is not None else None, None,
+                             int(st.tables["after_pgo"]), 0)
         f32 = dict(dtype=torch.float32, device=dev)
         d_gn = torch.empty(st.B, st.nn_k, 3, **f32)
         d_gw = torch.empty(st.B, st.nn_k, **f32)
@@ -632,7 +548,7 @@ class _QfTable(torch.autograd.Function):
 def _table_grad(st: _QfState, which: int, g: torch.Tensor) -> torch.Tensor:
     """Deterministic row scatter-add of the upstream rows `g` ([B, k, F] or the first F columns of [B, k, F+3]) into a
     dense [rows, F] table gradient (`pings_rows_plan_build` once per batch, `_apply` per table)."""
-    L = _L()
+    L = _lib.lib()
     F = st.Fc if which else st.Fg
     dev = g.device
     n_pairs = st.B * st.nn_k
@@ -822,7 +738,7 @@ def sdf_fused(npm, decoder, x: torch.Tensor, need_grad: bool = False, need_certa
     if not fused_supported(npm, decoder):
         return _sdf_composed(npm, decoder, x, need_grad, need_certainty, query_locally, use_only_measured_points,
                              use_only_valid_points, need_std)
-    L = _L()
+    L = _lib.lib()
     q = x.detach().to(torch.float32).contiguous()
     B = q.shape[0]
     cfg = getattr(npm, "config", None)
@@ -840,8 +756,8 @@ def sdf_fused(npm, decoder, x: torch.Tensor, need_grad: bool = False, need_certa
     F = feats.shape[1]
     if W1.shape[1] != F + 3:
         raise ValueError(f"decoder input dim {W1.shape[1]} != feature dim {F} + 3")
-    dec = _CDecoder(W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), int(W1.shape[0]), int(F),
-                    float(decoder.sdf_scale), int(weighted_first))
+    dec = _abi.SdfDecoder(W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), int(W1.shape[0]), int(F),
+                          float(decoder.sdf_scale), int(weighted_first))
     dev = q.device
     sdf = torch.empty(B, dtype=torch.float32, device=dev)
     grad = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_grad else None
@@ -871,7 +787,7 @@ def _sdf_scratch(L, B, nn_k, F, H, rows, dev):
 
 def _sdf_first_order(st, g_sdf):
     """(g_x, gF, gW1, gb1, gW2, gb2) of the fused query for the upstream gradient g_sdf [B] (no autograd here)."""
-    L = _L()
+    L = _lib.lib()
     q, f, W1c, b1c, W2c, b2c, idx, gidx, w, pts, quat, gpts, unit = st["saved"]
     sdf_scale, weighted_first, after_pgo, nn_k = st["meta"]
     B, F, H = q.shape[0], f.shape[1], W1c.shape[0]
@@ -881,8 +797,8 @@ def _sdf_first_order(st, g_sdf):
         g = g.to(torch.float32).contiguous()
     gF = gW1 = gb1 = gW2 = gb2 = None
     if st["need_params"]:
-        dec = _CDecoder(W1c.data_ptr(), b1c.data_ptr(), W2c.data_ptr(), b2c.data_ptr(), int(H), int(F),
-                        float(sdf_scale), int(weighted_first))
+        dec = _abi.SdfDecoder(W1c.data_ptr(), b1c.data_ptr(), W2c.data_ptr(), b2c.data_ptr(), int(H), int(F),
+                              float(sdf_scale), int(weighted_first))
         gF = torch.empty_like(f)
         flat = torch.empty(H * (F + 5) + 1, dtype=torch.float32, device=dev)      # one allocation for the decoder
         gW1, gb1 = flat[:H * (F + 3)].view(H, F + 3), flat[H * (F + 3):H * (F + 4)]
@@ -921,7 +837,7 @@ class _SdfTrainBackward(torch.autograd.Function):
             raise NotImplementedError("sdf_train: differentiating the PARAMETER gradients once more is not implemented")
         if gg_x is None:
             return (None,) * 8
-        L = _L()
+        L = _lib.lib()
         st = ctx.st
         (g,) = ctx.saved_tensors
         q, f, W1c, b1c, W2c, b2c, idx, gidx, w, pts, quat, gpts, unit = st["saved"]
@@ -930,8 +846,8 @@ class _SdfTrainBackward(torch.autograd.Function):
         dev = q.device
         ggx = gg_x.detach().to(torch.float32).contiguous()
         v = (ggx * g.unsqueeze(1)).contiguous()            # Phi = sum_b <v_b, dS_b/dx>
-        dec = _CDecoder(W1c.data_ptr(), b1c.data_ptr(), W2c.data_ptr(), b2c.data_ptr(), int(H), int(F),
-                        float(sdf_scale), int(weighted_first))
+        dec = _abi.SdfDecoder(W1c.data_ptr(), b1c.data_ptr(), W2c.data_ptr(), b2c.data_ptr(), int(H), int(F),
+                              float(sdf_scale), int(weighted_first))
         f32 = dict(dtype=torch.float32, device=dev)
         dF = torch.empty_like(f)
         dW1, db1 = torch.empty(H, F + 3, **f32), torch.empty(H, **f32)
@@ -955,7 +871,7 @@ def _c(t):
 def _sdf_train_forward(x, feats, W1, b1, W2, b2, npm, sdf_scale, weighted_first, query_locally, use_meas, use_valid,
                        need_gx):
     """`pings_sdf_forward` with the neighbour lists kept: (sdf [B], nn_counts [B], state for `_sdf_first_order`)."""
-    L = _L()
+    L = _lib.lib()
     q = x.detach()
     if q.dtype != torch.float32 or not q.is_contiguous():
         q = q.to(torch.float32).contiguous()
@@ -963,8 +879,8 @@ def _sdf_train_forward(x, feats, W1, b1, W2, b2, npm, sdf_scale, weighted_first,
     a = _map_args(npm, bool(npm.temporal_local_map_on and query_locally), use_meas, use_valid, query_locally)
     f, W1c, b1c, W2c, b2c = _c(feats), _c(W1), _c(b1), _c(W2), _c(b2)
     F = f.shape[1]
-    dec = _CDecoder(W1c.data_ptr(), b1c.data_ptr(), W2c.data_ptr(), b2c.data_ptr(), int(W1c.shape[0]), int(F),
-                    float(sdf_scale), int(weighted_first))
+    dec = _abi.SdfDecoder(W1c.data_ptr(), b1c.data_ptr(), W2c.data_ptr(), b2c.data_ptr(), int(W1c.shape[0]),
+                          int(F), float(sdf_scale), int(weighted_first))
     pts = _c(npm.local_neural_points if query_locally else npm.neural_points)
     quat = _c(npm.local_point_orientations if query_locally else npm.point_orientations)
     gpts = _c(npm.neural_points)
@@ -1028,19 +944,6 @@ def sdf_train(npm, decoder, x: torch.Tensor, query_locally: bool = True, use_onl
 
 
 # ---------------------------------------------------------------- fused finite-difference gradient
-def _declare_stencil(L):
-    if getattr(L, "_stencil_declared", False):
-        return
-    vp = C.c_void_p
-    L.pings_stencil_points.restype = C.c_int
-    L.pings_stencil_points.argtypes = [vp, C.c_int64, C.c_float, C.c_int, vp, vp]
-    L.pings_stencil_gradient.restype = C.c_int
-    L.pings_stencil_gradient.argtypes = [vp, vp, C.c_int64, C.c_float, C.c_int, vp, vp]
-    L.pings_stencil_gradient_backward.restype = C.c_int
-    L.pings_stencil_gradient_backward.argtypes = [vp, C.c_int64, C.c_float, C.c_int, vp, vp, vp]
-    L._stencil_declared = True
-
-
 class _NumGrad(torch.autograd.Function):
     """`Mapper.get_numerical_gradient` (utils/mapper.py:2319-2370) as ONE graph node: shifted points, fused SDF query
     and central differences forward (3 launches); the differences' adjoint and the fused SDF backward to the feature
@@ -1048,8 +951,7 @@ class _NumGrad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, sdf_x, feats, W1, b1, W2, b2, npm, sdf_scale, weighted_first, eps, two_side):
-        L = _L()
-        _declare_stencil(L)
+        L = _lib.lib()
         q = x.detach()
         if q.dtype != torch.float32 or not q.is_contiguous():
             q = q.to(torch.float32).contiguous()
@@ -1079,7 +981,7 @@ class _NumGrad(torch.autograd.Function):
     def backward(ctx, g):
         if g is None:
             return (None,) * 12
-        L = _L()
+        L = _lib.lib()
         N = ctx.N
         dev = g.device
         gg = g.detach()

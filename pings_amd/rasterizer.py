@@ -23,21 +23,9 @@ from typing import NamedTuple, Optional
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _abi, _lib
 
-MODE_SURFEL = 0
-MODE_3DGS = 1
-MODE_2DGS = 2
-
-
-class _CSettings(C.Structure):
-    _fields_ = [
-        ("image_height", C.c_int32), ("image_width", C.c_int32),
-        ("mode", C.c_int32), ("front_only", C.c_int32),
-        ("tanfovx", C.c_double), ("tanfovy", C.c_double), ("scale_modifier", C.c_double),
-        ("bg", C.c_void_p), ("viewmatrix", C.c_void_p), ("projmatrix", C.c_void_p),
-        ("projmatrix_raw", C.c_void_p), ("prcppoint", C.c_void_p),
-    ]
+MODE_SURFEL, MODE_3DGS, MODE_2DGS = _abi.RASTER_SURFEL, _abi.RASTER_3DGS, _abi.RASTER_2DGS
 
 
 class SurfelRasterizationSettings(NamedTuple):
@@ -142,53 +130,17 @@ class _Prepared:
         if int(rs.sh_degree) != 0:
             raise NotImplementedError("SH evaluation is not part of the PINGS path (colors_precomp only)")
         self.device = dev
-        self.c = _CSettings(self.H, self.W, mode, front_only, float(rs.tanfovx), float(rs.tanfovy),
-                            float(rs.scale_modifier), self.bg.data_ptr(), self.view.data_ptr(),
-                            self.proj.data_ptr(), self.proj_raw.data_ptr(),
-                            self.prcp.data_ptr() if self.prcp is not None else None)
+        self.c = _abi.RasterSettings(self.H, self.W, mode, front_only, float(rs.tanfovx), float(rs.tanfovy),
+                                     float(rs.scale_modifier), self.bg.data_ptr(), self.view.data_ptr(),
+                                     self.proj.data_ptr(), self.proj_raw.data_ptr(),
+                                     self.prcp.data_ptr() if self.prcp is not None else None)
 
     def ref(self):
         return C.byref(self.c)
 
 
-def _declare(L):
-    if getattr(L, "_raster_declared", False):
-        return
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    L.pings_raster_mark_visible.restype = C.c_int
-    L.pings_raster_mark_visible.argtypes = [vp, i32, C.POINTER(_CSettings), vp, vp]
-    L.pings_raster_geom_bytes.restype = C.c_size_t
-    L.pings_raster_geom_bytes.argtypes = [i32, i32, i32]
-    L.pings_raster_binning_bytes.restype = C.c_size_t
-    L.pings_raster_binning_bytes.argtypes = [i64, i32, i32]
-    L.pings_raster_image_bytes.restype = C.c_size_t
-    L.pings_raster_image_bytes.argtypes = [i32, i32]
-    L.pings_raster_preprocess.restype = C.c_int
-    L.pings_raster_preprocess.argtypes = [C.POINTER(_CSettings), i32, vp, vp, vp, vp, vp, vp, vp,
-                                          C.POINTER(C.c_int64), C.POINTER(C.c_int32), vp]
-    L.pings_raster_render.restype = C.c_int
-    L.pings_raster_render.argtypes = [C.POINTER(_CSettings), i32, i64, vp, vp, vp, vp, vp, vp, vp,
-                                      vp, i32, vp]
-    L.pings_raster_backward_bytes.restype = C.c_size_t
-    L.pings_raster_backward_bytes.argtypes = [i32, i64]
-    if hasattr(L, "pings_raster_backward"):
-        L.pings_raster_backward.restype = C.c_int
-        L.pings_raster_backward.argtypes = [C.POINTER(_CSettings), i32, i64] + [vp] * 24 + [i32, vp]
-    L.pings_raster_debug_lists.restype = C.c_int
-    L.pings_raster_debug_lists.argtypes = [vp, i64, i32, i32, vp, vp, vp]
-    L.pings_raster_debug_image.restype = C.c_int
-    L.pings_raster_debug_image.argtypes = [vp, i32, i32, vp, vp, vp]
-    L._raster_declared = True
-
-
-def _lib_raster():
-    L = _lib.lib()
-    _declare(L)
-    return L
-
-
 def mark_visible(positions: torch.Tensor, prep: _Prepared) -> torch.Tensor:
-    L = _lib_raster()
+    L = _lib.lib()
     pos = _f32c(positions)
     N = pos.shape[0]
     present = torch.empty(N, dtype=torch.uint8, device=pos.device)
@@ -206,7 +158,7 @@ class _ForwardState:
 
 
 def _forward(prep: _Prepared, means3D, colors, opacities, scales, rotations):
-    L = _lib_raster()
+    L = _lib.lib()
     dev = means3D.device
     P = means3D.shape[0]
     H, W = prep.H, prep.W
@@ -253,7 +205,7 @@ def _forward(prep: _Prepared, means3D, colors, opacities, scales, rotations):
 
 def debug_lists(fs: _ForwardState):
     """(point_list[I] int64, ranges[num_tiles,2] int64, final_T[H,W], n_contrib[H,W]) — parity taps for tests."""
-    L = _lib_raster()
+    L = _lib.lib()
     dev = fs.geom.device
     H, W = fs.prep.H, fs.prep.W
     nt = ((W + 15) // 16) * ((H + 15) // 16)
@@ -308,7 +260,7 @@ class _RasterizeGaussians(torch.autograd.Function):
     def backward(ctx, *grads):
         fs = ctx.fs
         prep = fs.prep
-        L = _lib_raster()
+        L = _lib.lib()
         if prep.mode == MODE_SURFEL:
             g_color, g_normal, g_depth, g_alpha, _, _ = grads
         else:
@@ -387,47 +339,13 @@ class GS3DGaussianRasterizer(_RasterizerBase):
 
 
 # ------------------------------------------------------------------ 2D Gaussian splatting (diff_surfel_rasterization)
-def _declare2d(L):
-    if getattr(L, "_raster2d_declared", False):
-        return
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    L.pings_raster2d_geom_bytes.restype = C.c_size_t
-    L.pings_raster2d_geom_bytes.argtypes = [i32, i32, i32]
-    L.pings_raster2d_binning_bytes.restype = C.c_size_t
-    L.pings_raster2d_binning_bytes.argtypes = [i64, i32, i32]
-    L.pings_raster2d_image_bytes.restype = C.c_size_t
-    L.pings_raster2d_image_bytes.argtypes = [i32, i32]
-    L.pings_raster2d_preprocess.restype = C.c_int
-    L.pings_raster2d_preprocess.argtypes = [C.POINTER(_CSettings), i32, vp, vp, vp, vp, vp, vp, vp, vp, i32,
-                                            C.POINTER(C.c_void_p), i32, C.POINTER(C.c_int32),
-                                            C.POINTER(C.c_int64), vp]
-    L.pings_raster2d_render.restype = C.c_int
-    L.pings_raster2d_render.argtypes = [C.POINTER(_CSettings), i32, i64, vp, vp, vp, vp, vp, vp]
-    L.pings_raster2d_backward_bytes.restype = C.c_size_t
-    L.pings_raster2d_backward_bytes.argtypes = [i32, i64]
-    L.pings_raster2d_backward.restype = C.c_int
-    L.pings_raster2d_backward.argtypes = [C.POINTER(_CSettings), i32, i64] + [vp] * 14 + [vp]
-    L.pings_raster2d_debug_lists.restype = C.c_int
-    L.pings_raster2d_debug_lists.argtypes = [vp, i64, i32, i32, vp, vp, vp]
-    L.pings_raster2d_debug_image.restype = C.c_int
-    L.pings_raster2d_debug_image.argtypes = [vp, i32, i32, vp, vp, vp, vp]
-    L._raster2d_declared = True
-
-
-def _lib_raster2d():
-    L = _lib.lib()
-    _declare(L)
-    _declare2d(L)
-    return L
-
-
 class _Forward2DState:
     """What the 2DGS backward pass reads: the three blobs, the inputs it differentiates through, the sizes."""
     __slots__ = ("prep", "P", "I", "geom", "binning", "image", "scales", "rotations", "color", "allmap")
 
 
 def _forward2d(prep: _Prepared, means3D, colors, opacities, scales, rotations):
-    L = _lib_raster2d()
+    L = _lib.lib()
     dev = means3D.device
     P = means3D.shape[0]
     H, W = prep.H, prep.W
@@ -458,7 +376,7 @@ def _forward2d(prep: _Prepared, means3D, colors, opacities, scales, rotations):
 
 def debug_lists2d(fs: _Forward2DState):
     """(point_list[I] int64 Gaussian ids, ranges[num_tiles,2] int64, final_T[H,W], last[H,W], median[H,W])."""
-    L = _lib_raster2d()
+    L = _lib.lib()
     dev = fs.geom.device
     H, W = fs.prep.H, fs.prep.W
     nt = ((W + 15) // 16) * ((H + 15) // 16)
@@ -477,7 +395,7 @@ def debug_lists2d(fs: _Forward2DState):
 
 def backward2d(fs: _Forward2DState, g_color, g_allmap):
     """(d_means3D[P,3], d_means2D[P,3], d_colors[P,3], d_opacities[P,1], d_scales[P,2], d_rotations[P,4])."""
-    L = _lib_raster2d()
+    L = _lib.lib()
     dev = fs.geom.device
     P, I = fs.P, fs.I
     f32 = dict(dtype=torch.float32, device=dev)

@@ -27,9 +27,8 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from . import rasterizer as _rast
-from . import spawn as _spawn
 
 
 class SkipFrame(Exception):
@@ -49,24 +48,6 @@ class FrameCounts:
         self.n_vis_dev, self.n_dev = n_vis_dev, n_dev
         self.k = 0
         self.n_vis = self.n_sel = self.count = self.I = None
-
-
-def _declare(L):
-    if getattr(L, "_core_declared", False):
-        return
-    vp, i32 = C.c_void_p, C.c_int
-    _rast._declare(L)
-    _rast._declare2d(L)
-    _spawn._declare(L)
-    L.pings_spawn_plan_dyn.restype = C.c_int
-    L.pings_spawn_plan_dyn.argtypes = [C.POINTER(_spawn.SpawnParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pings_spawn_forward_dyn.restype = C.c_int
-    L.pings_spawn_forward_dyn.argtypes = [C.POINTER(_spawn.SpawnParams), vp] + [vp] * 18 + [vp, vp]
-    L.pings_raster_preprocess_dyn.restype = C.c_int
-    L.pings_raster_preprocess_dyn.argtypes = [C.POINTER(_rast._CSettings), i32, vp, vp, vp, vp, vp, vp, vp, vp, i32,
-                                              C.POINTER(C.c_void_p), i32, C.POINTER(C.c_int32),
-                                              C.POINTER(C.c_int64), C.POINTER(C.c_int32), vp]
-    L._core_declared = True
 
 
 _BLOB_SIZES: dict = {}
@@ -91,14 +72,13 @@ class _SpawnRaster(torch.autograd.Function):
     def forward(ctx, xyz_raw, rot_raw, scale_raw, alpha_raw, color_raw, theta, rho,
                 fz_xyz, fz_alpha, fz_scale, fz_rot, fz_color, st: _State):
         L = _lib.lib()
-        _declare(L)
         prep, fc = st.prep, st.fc
         dev = xyz_raw.device
         stream = _lib.stream_ptr(dev)
         raws = [_f32c(t) for t in (xyz_raw, rot_raw, scale_raw, alpha_raw, color_raw)]
         pos, quat, base, dist_ratio = _f32c(st.pos), _f32c(st.quat), _f32c(st.base), _f32c(st.dist_ratio)
         prm = dict(st.prm)
-        p = _spawn.SpawnParams(**prm)                      # p.n = capacity (n_all rows)
+        p = _abi.SpawnParams(**prm)                      # p.n = capacity (n_all rows)
         n_cap, k = p.n, p.k
         nk = n_cap * k
         M = int(fz_xyz.shape[0]) if fz_xyz is not None else 0
@@ -294,7 +274,7 @@ class _SpawnRaster(torch.autograd.Function):
             vsp.grad = torch.cat((d_m2d[:count], d_m2d[nk:])) if M else d_m2d[:count]
         prm = dict(ctx.prm)
         prm["n"] = n_sel
-        p = _spawn.SpawnParams(**prm)
+        p = _abi.SpawnParams(**prm)
         # rows behind the selected ones are never written (nor read downstream); under anomaly detection autograd scans
         # every returned gradient for NaN, so only then are they cleared
         alloc = torch.zeros_like if torch.is_anomaly_enabled() else torch.empty_like

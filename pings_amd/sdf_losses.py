@@ -21,33 +21,11 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from . import decoder as _dec
 from . import neural_points as _np
 
 F_EIK, F_COL, F_COL_W, F_BCE_W, F_WF = 1, 2, 4, 8, 16
-vp = C.c_void_p
-
-
-class _Args(C.Structure):
-    _fields_ = [("B", C.c_int64), ("cap", C.c_int64), ("k", C.c_int32), ("C", C.c_int32), ("d", C.c_int32),
-                ("flags", C.c_int32), ("sigma", C.c_float), ("eik_band", C.c_float), ("col_band", C.c_float)] + \
-               [(n, vp) for n in ("coord", "label", "weight", "color_label", "w", "s", "c", "g", "idx", "xsel", "meta",
-                                  "part", "sdf_pred", "losses", "counts", "gl", "g_pred", "d_s", "d_g", "d_c")]
-
-
-def _declare(L):
-    if getattr(L, "_sloss_declared", False):
-        return
-    if not hasattr(L, "pings_sdf_loss_select"):     # an ABI-9 library built before this block existed
-        raise _lib.PingsHipError(f"{_lib.LIB_PATH} has no pings_sdf_loss_* entry points: rebuild it with "
-                                 "`python -m pings_amd.build`")
-    for n in ("select", "reduce", "backward"):
-        f = getattr(L, "pings_sdf_loss_" + n)
-        f.restype, f.argtypes = C.c_int, [C.POINTER(_Args), vp]
-    L.pings_sdf_loss_partials.restype = C.c_int
-    L.pings_sdf_loss_partials.argtypes = [C.c_int64, C.c_int64]
-    L._sloss_declared = True
 
 
 class SdfLosses(NamedTuple):
@@ -176,7 +154,6 @@ def sdf_losses(mapper, coord: torch.Tensor, sdf_label: torch.Tensor, ts: torch.T
     if not coord.is_cuda:
         raise _lib.PingsHipError("sdf_losses runs on the HIP device only (got a CPU tensor); there is no CPU fallback")
     L = _lib.lib()
-    _declare(L)
     dev = coord.device
     cap = (B + d - 1) // d
     loss_w = bool(getattr(cfg, "loss_weight_on", False))
@@ -192,9 +169,9 @@ def sdf_losses(mapper, coord: torch.Tensor, sdf_label: torch.Tensor, ts: torch.T
 
     flags = (F_EIK * bool(eikonal)) | (F_COL * bool(color)) | (F_COL_W * bool(color and color_w)) | \
             (F_BCE_W * loss_w) | (F_WF * wf)
-    a = _Args(B, cap, k, int(c.shape[-1]) if color else 0, d, flags, float(mapper.sdf_scale),
-              float(getattr(cfg, "free_sample_end_dist_m", 0.0)),
-              float(0.5 * getattr(cfg, "surface_sample_range_m", 0.0)))
+    a = _abi.SdfLossArgs(B, cap, k, int(c.shape[-1]) if color else 0, d, flags, float(mapper.sdf_scale),
+                         float(getattr(cfg, "free_sample_end_dist_m", 0.0)),
+                         float(0.5 * getattr(cfg, "surface_sample_range_m", 0.0)))
     keep = {"coord": _f32(coord), "label": _f32(sdf_label), "w": _f32(wk).view(B, k),
             "weight": _f32(weight) if (flags & (F_COL_W | F_BCE_W)) else None,
             "color_label": _f32(color_label) if color else None}

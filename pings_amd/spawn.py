@@ -15,43 +15,7 @@ from typing import Optional
 
 import torch
 
-from . import _lib
-
-
-class SpawnParams(C.Structure):
-    _fields_ = [("n", C.c_int), ("k", C.c_int), ("scale_dim", C.c_int), ("surfel", C.c_int),
-                ("color_residual", C.c_int), ("alpha_filter_on", C.c_int), ("scale_filter_on", C.c_int),
-                ("displacement_range", C.c_float), ("unit_scale", C.c_float), ("max_scale", C.c_float),
-                ("scale_filter_thr", C.c_float)]
-
-
-def _declare(L):
-    if getattr(L, "_spawn_declared", False):
-        return
-    vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
-    L.pings_spawn_gather.restype = C.c_int
-    L.pings_spawn_gather.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32,
-                                     vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pings_spawn_gather_dyn.restype = C.c_int
-    L.pings_spawn_gather_dyn.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, i32, vp, i32, vp, i32, i32, i32,
-                                         vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pings_spawn_gather_backward.restype = C.c_int
-    L.pings_spawn_gather_backward.argtypes = [i32, vp, vp, i32, i32, vp, i32, i32, vp, vp, vp]
-    L.pings_spawn_plan_scratch_bytes.restype = C.c_size_t
-    L.pings_spawn_plan_scratch_bytes.argtypes = [i64]
-    L.pings_spawn_plan.restype = C.c_int
-    L.pings_spawn_plan.argtypes = [C.POINTER(SpawnParams), vp, vp, vp, vp, vp, vp, vp]
-    L.pings_spawn_forward.restype = C.c_int
-    L.pings_spawn_forward.argtypes = [C.POINTER(SpawnParams)] + [vp] * 19
-    L.pings_spawn_backward.restype = C.c_int
-    L.pings_spawn_backward.argtypes = [C.POINTER(SpawnParams)] + [vp] * 21
-    L._spawn_declared = True
-
-
-def _lib_ready():
-    L = _lib.lib()
-    _declare(L)
-    return L
+from . import _abi, _lib
 
 
 def _f32c(t: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -62,7 +26,7 @@ class _Gather(torch.autograd.Function):
     @staticmethod
     def forward(ctx, geo_feature, color_feature, sel, position, orientation, color, free_mask, cam_origin,
                 xy_only, view_concat, dist_concat, fc=None):
-        L = _lib_ready()
+        L = _lib.lib()
         dev = geo_feature.device
         gf, cf = _f32c(geo_feature), _f32c(color_feature)
         pos_all, quat_all = _f32c(position), _f32c(orientation)
@@ -98,7 +62,7 @@ class _Gather(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_geo_in, g_col_in, *_):
-        L = _lib_ready()
+        L = _lib.lib()
         gshape, cshape, n, Fg, Fc, ldg, ldc = ctx.shapes
         if ctx.fc is not None:
             n = ctx.fc.n_sel                    # the exact row count, known since the frame's read-back
@@ -141,11 +105,11 @@ class Spawned:
 class _Activate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, xyz_raw, rot_raw, scale_raw, alpha_raw, color_raw, pos, quat, base, dist_ratio, free, prm):
-        L = _lib_ready()
+        L = _lib.lib()
         dev = xyz_raw.device
         raws = [_f32c(t) for t in (xyz_raw, rot_raw, scale_raw, alpha_raw, color_raw)]
         pos, quat, base, dist_ratio = _f32c(pos), _f32c(quat), _f32c(base), _f32c(dist_ratio)
-        p = SpawnParams(**prm)
+        p = _abi.SpawnParams(**prm)
         n, k = p.n, p.k
         nk = n * k
         f32 = dict(dtype=torch.float32, device=dev)
@@ -182,7 +146,7 @@ class _Activate(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_xyz, g_scale, g_rot, g_alpha, g_color, g_alpha_all, *_):
-        L = _lib_ready()
+        L = _lib.lib()
         sv = list(ctx.saved_tensors)
         raws, quat = sv[:5], sv[5]
         rest = sv[6:]
@@ -190,7 +154,7 @@ class _Activate(torch.autograd.Function):
         base = rest.pop(0) if has_base else None
         dist_ratio = rest.pop(0) if has_dr else None
         dest = rest.pop(0) if has_dest else None
-        p = SpawnParams(**ctx.prm)
+        p = _abi.SpawnParams(**ctx.prm)
         dev = raws[0].device
         gs = [_f32c(g) for g in (g_xyz, g_scale, g_rot, g_alpha, g_color, g_alpha_all)]
         outs = [torch.empty_like(r) for r in raws]

@@ -32,50 +32,17 @@ import struct
 
 import torch
 
-from . import _lib
+from . import _abi, _lib
 from . import neural_points as _np
+from ._abi import REG_ILL_CONDITIONED, REG_NONFINITE, REG_SINGULAR     # re-exported: the solve's status bits
 
-
-REG_SINGULAR, REG_ILL_CONDITIONED, REG_NONFINITE = 1, 2, 4     # include/pings_hip.h: PINGS_REG_*
 _REG_CHECK = __import__("os").environ.get("PINGS_REG_CHECK", "1") != "0"
-last_solve_status = None    # int32[1] device tensor of the most recent `implicit_reg` (bit mask above)
+last_solve_status = None    # int32[1] device tensor of the most recent `implicit_reg` (REG_* bit mask)
 # float64 [iterations, 24] device tensor of the most recent `tracking` call, one row per executed iteration: valid
 # count, residual (cm), rotation (deg), translation (m), status bits, sum w, sum w r^2, 0, then dT row-major (16)
 last_trace = None
 _ORIG = {}                  # the reference's Tracker.tracking / registration_step, kept by install(loop=True)
-F_NORMALS, F_DIV_GRAD, F_WEIGHTED = 1, 2, 4     # include/pings_hip.h: PINGS_REG_F_*
 TRACE_ROW = 24
-
-
-def _declare(L):
-    if getattr(L, "_trk_declared", False):
-        return
-    vp = C.c_void_p
-    L.pings_reg_normal_equations_scratch_bytes.restype = C.c_size_t
-    L.pings_reg_normal_equations_scratch_bytes.argtypes = []
-    L.pings_reg_normal_equations.restype = C.c_int
-    L.pings_reg_normal_equations.argtypes = [vp, vp, vp, vp, C.c_int64, vp, vp, vp]
-    L.pings_reg_solve.restype = C.c_int
-    L.pings_reg_solve.argtypes = [vp, C.c_float, vp, vp, vp]
-    L.pings_reg_solve_checked.restype = C.c_int
-    L.pings_reg_solve_checked.argtypes = [vp, C.c_float, vp, vp, vp, C.POINTER(C.c_int32), vp]
-    if hasattr(L, "pings_reg_step"):
-        for n in ("transform", "assemble", "step"):
-            f = getattr(L, "pings_reg_" + n)
-            f.restype, f.argtypes = C.c_int, [C.POINTER(_LoopArgs), vp]
-        L.pings_reg_partials.restype = C.c_int
-        L.pings_reg_partials.argtypes = [C.c_int64]
-        L.pings_reg_read_record.restype = C.c_int
-        L.pings_reg_read_record.argtypes = [vp, vp, vp]
-    L._trk_declared = True
-
-
-class _LoopArgs(C.Structure):     # pings_reg_loop_args
-    _fields_ = [("n", C.c_int64), ("flags", C.c_int32), ("iter", C.c_int32), ("trace_cap", C.c_int32),
-                ("min_grad", C.c_float), ("max_grad", C.c_float), ("max_std", C.c_float), ("gm_dist", C.c_float),
-                ("gm_grad", C.c_float), ("lm_lambda", C.c_float)] + \
-               [(k, C.c_void_p) for k in ("src", "cur", "sdf", "grad", "std", "mask", "label", "normals", "valid",
-                                          "part", "T", "delta", "record", "trace")]
 
 
 def normal_equations(points, sdf_grad, sdf_residual, weight):
@@ -83,7 +50,6 @@ def normal_equations(points, sdf_grad, sdf_residual, weight):
     if not points.is_cuda:
         raise _lib.PingsHipError("implicit_reg runs on the HIP device only (got a CPU tensor); there is no CPU fallback")
     L = _lib.lib()
-    _declare(L)
     f = lambda t: t.detach().to(torch.float32).contiguous()
     p, g = f(points), f(sdf_grad)
     r, w = f(sdf_residual).reshape(-1), f(weight).reshape(-1)
@@ -201,9 +167,10 @@ def query_source_points(self, coord, bs, query_sdf=True, query_sdf_grad=True, qu
                                                         use_only_valid_points=True)
                 wk = None if self.config.weighted_first else w_knn
                 if query_sem:
-                    sem_pred[head:tail] = head_reduce(_dec.mlp(self.sem_mlp, gf), wk, 1).to(sem_pred.dtype)
+                    sem_pred[head:tail] = head_reduce(_dec.mlp(self.sem_mlp, gf), wk,
+                                                      _abi.HEAD_SEMANTIC).to(sem_pred.dtype)
                 if query_color and not query_color_grad:
-                    color_pred[head:tail] = head_reduce(_dec.mlp(self.color_mlp, cf), wk, 0)
+                    color_pred[head:tail] = head_reduce(_dec.mlp(self.color_mlp, cf), wk, _abi.HEAD_COLOR)
         if query_color and query_color_grad:   # photometric term with its gradient: HIP query_feature + the reference's torch tail
             xc = x.detach().clone().requires_grad_(bool(query_color_grad))
             _, color_feature, w_knn, _, _ = npm.query_feature(xc, accumulate_stability=False, query_locally=query_locally,
@@ -222,7 +189,6 @@ def query_source_points(self, coord, bs, query_sdf=True, query_sdf_grad=True, qu
 # ---------------------------------------------------------------- device-resident odometry loop
 def _loop_lib():
     L = _lib.lib()
-    _declare(L)
     if not hasattr(L, "pings_reg_step"):
         raise _lib.PingsHipError(f"{_lib.LIB_PATH} has no pings_reg_step: rebuild it with `python -m pings_amd.build`")
     return L
@@ -251,12 +217,12 @@ class _Loop:
         self.trace = torch.zeros(max(trace_rows, 1), TRACE_ROW, dtype=torch.float64, device=dev) if trace_rows else None
         self.valid = torch.empty(self.n, dtype=torch.bool, device=dev) if valid_out else None
         self.host = (C.c_int32 * 8)()
-        flags = (F_NORMALS if normals is not None else 0) | (F_DIV_GRAD if cfg.reg_dist_div_grad_norm else 0) | \
-                (F_WEIGHTED if weighted else 0)
+        flags = (_abi.REG_F_NORMALS if normals is not None else 0) | \
+                (_abi.REG_F_DIV_GRAD if cfg.reg_dist_div_grad_norm else 0) | (_abi.REG_F_WEIGHTED if weighted else 0)
         max_std = cfg.surface_sample_range_m * cfg.max_sdf_std_ratio
-        a = _LoopArgs(self.n, flags, 0, trace_rows, float(min_grad), float(max_grad), float(max_std),
-                      float(GM_dist) if GM_dist is not None else 0.0, float(GM_grad) if GM_grad is not None else 0.0,
-                      float(lm_lambda))
+        a = _abi.RegLoopArgs(self.n, flags, 0, trace_rows, float(min_grad), float(max_grad), float(max_std),
+                             float(GM_dist) if GM_dist is not None else 0.0,
+                             float(GM_grad) if GM_grad is not None else 0.0, float(lm_lambda))
         a.src, a.cur, a.label, a.normals = self.src.data_ptr(), self.cur.data_ptr(), self.label.data_ptr(), \
             _lib.ptr(self.normals)
         a.valid = _lib.ptr(self.valid)

@@ -115,10 +115,11 @@ def test_dropin_resolves_with_the_reference_field_list():
 
 def test_header_declares_and_library_exports_the_2dgs_entries():
     from pings_amd import _lib
+    from tests import abi_header
 
-    hdr = _lib.HEADER.read_text()
+    hdr = abi_header.HEADER.read_text()
     assert re.search(r"#define\s+PINGS_RASTER_2DGS\s+2", hdr)
-    assert _lib.expected_abi() == 9
+    assert abi_header.expected_abi() == 9
     names = ("pings_raster2d_geom_bytes", "pings_raster2d_binning_bytes", "pings_raster2d_image_bytes",
              "pings_raster2d_preprocess", "pings_raster2d_render", "pings_raster2d_backward_bytes",
              "pings_raster2d_backward", "pings_raster2d_debug_lists", "pings_raster2d_debug_image")
@@ -130,21 +131,18 @@ def test_header_declares_and_library_exports_the_2dgs_entries():
 
 
 def test_2dgs_entries_refuse_null_arguments_before_any_gpu_work():
-    from pings_amd import _lib
-    from pings_amd import rasterizer as hr
+    from pings_amd import _abi, _lib
 
     L = _lib.lib()
-    hr._declare(L)
-    hr._declare2d(L)
     n = C.c_int64(0)
     assert L.pings_raster2d_preprocess(None, 10, None, None, None, None, None, None, None, None, 0, None, 0, None,
                                        C.byref(n), None) == 1
-    s = hr._CSettings(48, 64, 2, 0, 0.5, 0.5, 1.0, None, None, None, None, None)
+    s = _abi.RasterSettings(48, 64, 2, 0, 0.5, 0.5, 1.0, None, None, None, None, None)
     assert L.pings_raster2d_preprocess(C.byref(s), 10, None, None, None, None, None, None, None, None, 0, None, 0,
                                        None, C.byref(n), None) == 1
     assert L.pings_raster2d_render(C.byref(s), 10, 0, None, None, None, None, None, None) == 1
     assert L.pings_raster2d_backward(C.byref(s), 10, 0, *([None] * 14), None) == 1
-    s1 = hr._CSettings(48, 64, 1, 0, 0.5, 0.5, 1.0, 8, 8, 8, 8, None)     # mode 3DGS: the 2DGS entries refuse it
+    s1 = _abi.RasterSettings(48, 64, 1, 0, 0.5, 0.5, 1.0, 8, 8, 8, 8, None)     # mode 3DGS: the 2DGS entries refuse it
     assert L.pings_raster2d_render(C.byref(s1), 10, 0, 8, 8, 8, 8, 8, None) == 1
     assert L.pings_raster2d_debug_image(None, 4, 4, None, None, None, None) == 1
 
