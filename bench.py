@@ -2,9 +2,11 @@
 """bench.py — PINGS hot-path benchmark on MI355X (contract: see the build prompt / DESIGN.md §measurement).
 
 Headline metric (BASELINE.json): raster fwd+bwd Mpix/s at 1M Gaussians, 1920x1080 (SURVEY.md §8d
-Metric 1); the same run also reports SDF Msamples/s (Metric 2) once the SDF kernels exist.
+Metric 1).  A plain run sets up, warms up, times the K steps and prints the headline line, nothing more; with --full
+the same line also carries the per-kernel times, the roofline, the CPU-oracle baselines and parity, Metric 2 (SDF
+Msamples/s) and the secondary legs (other workloads, tile-rectangle rules, training steps, decoders, SSIM, map).
 
-  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full [--no-sdf] [--no-cpu-baseline]]
   (--dump-outputs: the last timed step's outputs as DIR/<name>.npy, for comparing two builds output for output;
    N > 1: launched by torch.distributed.run, one rank per GPU; every rank renders its own camera
    view of the same Gaussian cloud and the parameter gradients are all-reduced over RCCL, as a
@@ -1184,11 +1186,14 @@ def main():
     ap.add_argument("--width", type=int, default=1920)
     ap.add_argument("--height", type=int, default=1080)
     ap.add_argument("--mode", default="surfel", choices=["surfel", "3dgs"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sdf", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure and check everything else: per-kernel times and roofline, "
+                         "CPU-oracle baselines and parity, Metric 2 (SDF) and the secondary legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU-oracle legs")
+    ap.add_argument("--no-sdf", action="store_true", help="--full without Metric 2 and the secondary legs")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N > 1 (nccl = RCCL)")
     ap.add_argument("--exchange-leg", action="store_true",
-                    help="N > 1: run the render_step_exchange leg even with --no-sdf (rehearsals)")
+                    help="--full, N > 1: run the render_step_exchange leg even with --no-sdf (rehearsals)")
     ap.add_argument("--single-device", action="store_true",
                     help="rehearsal only: put every rank on cuda:0 (use with --backend gloo)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -1197,6 +1202,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if args.exchange_leg and not args.full:
+        ap.error("--exchange-leg is a leg of --full")
 
     # backward passes run on the calling thread: the hand-off to autograd's per-device worker thread and back costs
     # 40-300 us per backward() depending on the box (measured: a two-operator graph 40 vs 73 us, the fused SDF step 178
@@ -1390,9 +1397,37 @@ def main():
         del arrays
     del out
 
+    line = None
+    if rank == 0:
+        line = {
+            "metric": "raster fwd+bwd Mpix/s @1M Gaussians 1080p",
+            "value": round(value, 3), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"workload": f"{args.mode} rasteriser fwd+bwd, {P} Gaussians, {W}x{H}, one view per GPU"
+                                   + (", then the multi-view exchange of SURVEY 8e over RCCL: row-sparse all-gather of the "
+                                      "visible neural points' feature-gradient rows (shared table [N x P/8 + 1, 48]: every "
+                                      "camera of the rig sees its own sector of the local map) + all-reduce of the six "
+                                      "decoder MLPs" if world > 1 else ""),
+                       "exchange": (ex.last if ex is not None else None),
+                       "rect_rule": {"tight": "tight: published 3-sigma tile square minus the tiles in which no pixel can "
+                                              "pass alpha >= 1/255 (output-identical to the square; legs raster_rect_3sigma / "
+                                              "raster_rect_ellipse of --full time the other two rules)",
+                                     "3sigma": "3sigma: published 3DGS tile square",
+                                     "ellipse": "ellipse: truncating alpha-ellipse box of rounds 1-3 (NOT output-identical)"}[
+                           {"3": "3sigma", "e": "ellipse"}.get(os.environ.get("PINGS_RASTER_RECT", "t")[:1], "tight")],
+                       "gaussians": P, "width": W, "height": H},
+            # False = torch.autograd.set_multithreading_enabled(False), see the top of main()
+            "autograd_multithreading": os.environ.get("PINGS_BENCH_AUTOGRAD_MT", "0") == "1",
+            "hsa_enable_interrupt": os.environ.get("HSA_ENABLE_INTERRUPT"),   # see the top of this file
+            "host_issue_ms_per_step": {"min": round(min(host_ms), 3), "median": round(sorted(host_ms)[len(host_ms) // 2], 3),
+                                       "max": round(max(host_ms), 3)},
+        }
+
+    # Everything below measures or checks something other than the headline, each in runs of its own: --full only.
     # N > 1: the real multi-view mapping step (every rank takes part: collectives inside), VERDICT r3 #7
     rse = None
-    if world > 1 and (not args.no_sdf or args.exchange_leg):
+    if args.full and world > 1 and (not args.no_sdf or args.exchange_leg):
         try:
             rse = bench_render_step(dev, max(args.steps // 2, 5), 2, exchange=(world, rank))
         except Exception as e:  # noqa: BLE001
@@ -1402,7 +1437,7 @@ def main():
         torch.cuda.empty_cache()
         dist.barrier()
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # instance count of this view (for the algorithmic-bytes figures)
         prep = rast._prepared()
         with torch.no_grad():
@@ -1537,39 +1572,19 @@ def main():
             extras["render_step_exchange"] = rse
         decoder, map_maint, img_losses = extras.pop("decoder", None), extras.pop("map_maintenance", None), \
             extras.pop("image_losses", None)
-        line = {
-            "metric": "raster fwd+bwd Mpix/s @1M Gaussians 1080p",
-            "value": round(value, 3), "unit": "Mpix/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.mode} rasteriser fwd+bwd, {P} Gaussians, {W}x{H}, one view per GPU"
-                                   + (", then the multi-view exchange of SURVEY 8e over RCCL: row-sparse all-gather of the "
-                                      "visible neural points' feature-gradient rows (shared table [N x P/8 + 1, 48]: every "
-                                      "camera of the rig sees its own sector of the local map) + all-reduce of the six "
-                                      "decoder MLPs" if world > 1 else ""),
-                       "exchange": (ex.last if ex is not None else None),
-                       "rect_rule": {"tight": "tight: published 3-sigma tile square minus the tiles in which no pixel can "
-                                              "pass alpha >= 1/255 (output-identical to the square; legs raster_rect_3sigma / "
-                                              "raster_rect_ellipse time the other two rules)",
-                                     "3sigma": "3sigma: published 3DGS tile square",
-                                     "ellipse": "ellipse: truncating alpha-ellipse box of rounds 1-3 (NOT output-identical)"}[
-                           {"3": "3sigma", "e": "ellipse"}.get(os.environ.get("PINGS_RASTER_RECT", "t")[:1], "tight")],
-                       "gaussians": P, "width": W, "height": H, "instances": int(I), "instances_blended": I_proc,
-                       "visible_gaussians": int((radii > 0).sum().item()),
-                       "mean_list_len_per_tile": round(I / (math.ceil(W / 16) * math.ceil(H / 16)), 1)},
-            # False = torch.autograd.set_multithreading_enabled(False), see the top of main()
-            "autograd_multithreading": os.environ.get("PINGS_BENCH_AUTOGRAD_MT", "0") == "1",
-            "hsa_enable_interrupt": os.environ.get("HSA_ENABLE_INTERRUPT"),   # see the top of this file
+        line["config"].update({"instances": int(I), "instances_blended": I_proc,
+                               "visible_gaussians": int((radii > 0).sum().item()),
+                               "mean_list_len_per_tile": round(I / (math.ceil(W / 16) * math.ceil(H / 16)), 1)})
+        line.update({
             # what a device allocation costs on THIS box (hipMalloc + first use / hipFree of 64 MB through torch, cache
             # emptied first): the map-maintenance leg allocates while the map grows, and any step that misses torch's cache
             # pays this per block (20 ms render steps on a box where it is milliseconds)
             "device_malloc_probe": _malloc_probe(dev),
             "secondary_legs_timing": "best of 3 runs of `steps` calls (bench._timeit); the headline is one run of K steps",
-            "host_issue_ms_per_step": {"min": round(min(host_ms), 3), "median": round(sorted(host_ms)[len(host_ms) // 2], 3),
-                                       "max": round(max(host_ms), 3)},
             "roofline": roofline, "kernels": kernels, "cpu_baseline": cpu, "sdf": sdf, "decoder": decoder,
             "map_maintenance": map_maint, "image_losses": img_losses, **extras,
-        }
+        })
+    if rank == 0:
         if dumped is not None:
             line["dump_outputs"] = dumped
         print(json.dumps(line), flush=True)

@@ -3,6 +3,8 @@ line committed under profiles/ — the file bench.py itself produced on the GPU 
 import json
 from pathlib import Path
 
+import pytest
+
 PROFILES = Path(__file__).resolve().parent.parent / "profiles"
 
 
@@ -95,3 +97,39 @@ def test_bench_refuses_zero_steps(monkeypatch):
     with pytest.raises(SystemExit) as e:
         bench.main()
     assert e.value.code == 2
+
+
+def test_bench_refuses_exchange_leg_without_full(monkeypatch):
+    import sys
+
+    sys.path.insert(0, str(PROFILES.parent))
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "1", "--warmup", "1", "--exchange-leg"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
+@pytest.mark.gpu
+def test_plain_bench_prints_the_headline_alone(tmp_path):
+    """A plain run times the headline and stops: the line holds the headline fields, consistent with each other, and
+    none of the figures that take runs of their own (they come with --full); --dump-outputs still writes the arrays."""
+    import subprocess
+    import sys
+
+    root = PROFILES.parent
+    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], cwd=root, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads(r.stdout.strip().splitlines()[-1])
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int),
+                 ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str), ("config", dict)):
+        assert isinstance(d[k], t), k
+    assert (d["unit"], d["higher_is_better"], d["dtype"], d["steps"], d["warmup"]) == ("Mpix/s", True, "f32", 2, 1)
+    assert abs(d["value"] - 1920 * 1080 / (d["ms_per_step"] * 1e-3) / 1e6) < 1e-2 * d["value"]
+    for k in ("roofline", "kernels", "cpu_baseline", "sdf", "decoder", "render_step", "device_malloc_probe"):
+        assert k not in d, k
+    assert "instances" not in d["config"]
+    assert set(d["dump_outputs"]["arrays"]) >= {"image", "radii", "grad_means3D"}
+    assert (tmp_path / "out" / "image.npy").exists()

@@ -3,7 +3,7 @@
 V=$1; A=$2; B=$3; R=${4:-3}
 for i in $(seq $R); do
   for val in $A $B; do
-    env $V=$val python bench.py --no-sdf --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | python -c "
+    env $V=$val python bench.py --full --no-sdf --no-cpu-baseline --steps 40 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']

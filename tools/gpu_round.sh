@@ -11,11 +11,11 @@ if [ "$part" = "1" ]; then
   timeout -k 10 800 python -m pytest tests -m gpu -q > $O/pytest.log 2>&1; echo "pytest rc=$?" | tee -a $O/pytest.log
   tail -3 $O/pytest.log
   timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1; echo "smoke rc=$?"
-  timeout -k 10 500 python bench.py > $O/bench.log 2>&1; echo "bench rc=$?"
+  timeout -k 10 500 python bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?"
   tail -c 400 $O/bench.log
 else
   cd /tmp
-  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o s -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline > $O/prof.log 2>&1; echo "prof rc=$?"
+  timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o s -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > $O/prof.log 2>&1; echo "prof rc=$?"
   timeout -k 10 200 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch -o f -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-sdf > $O/pmc_fetch.log 2>&1; echo "pmc fetch rc=$?"
   timeout -k 10 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $O/pmc_write -o w -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-sdf > $O/pmc_write.log 2>&1; echo "pmc write rc=$?"
   timeout -k 10 200 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $O/pmc_sq -o q -- python3 $R/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-sdf > $O/pmc_sq.log 2>&1; echo "pmc sq rc=$?"
@@ -41,7 +41,7 @@ else
   cd $R
   cp $O/c3/c_kernel_stats.csv $O/c3_kernel_stats.csv 2>/dev/null
   bash tools/pmc_mlp.sh > $O/mlp_pmc.txt 2>&1; echo "mlp pmc rc=$?"
-  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --backend gloo --single-device --no-sdf --no-cpu-baseline --exchange-leg > $O/bench_2rank_gloo.log 2>&1; echo "2-rank rehearsal rc=$?"
+  timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 bench.py --gpus 2 --steps 5 --warmup 2 --backend gloo --single-device --full --no-sdf --no-cpu-baseline --exchange-leg > $O/bench_2rank_gloo.log 2>&1; echo "2-rank rehearsal rc=$?"
   tail -c 300 $O/bench_2rank_gloo.log
   find $O -type f -size +12M -delete
   find $O -name "*kernel_trace.csv" -size +3M -delete

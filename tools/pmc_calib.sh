@@ -13,6 +13,6 @@ timeout -k 10 200 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv 
 timeout -k 10 200 rocprofv3 --kernel-trace --stats --output-format csv -d $O/calib_s -o s -- $R/profiles/_build/pmc_calib > $O/calib_s.log 2>&1; echo "calib stats rc=$?"
 cd $R
 python profiles/pmc_calib_summary.py $O/calib_f/f_counter_collection.csv $O/calib_w/w_counter_collection.csv $O/calib_stdout.txt $O/pmc_calibration.json
-timeout -k 10 500 python bench.py > $O/bench.log 2>&1; echo "bench rc=$?"
+timeout -k 10 500 python bench.py --full > $O/bench.log 2>&1; echo "bench rc=$?"
 tail -c 300 $O/bench.log
 find $O -name "*kernel_trace.csv" -size +3M -delete
