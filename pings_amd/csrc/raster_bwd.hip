@@ -58,17 +58,23 @@ inline uint32_t long_list_threshold() {
 constexpr uint32_t DEAD_ROW = 0xFFFFFFFFu;
 constexpr int CH = 64;  // rows per first-level chunk of the per-Gaussian sum
 
+#define PINGS_BLEND_BWD_PARAMS                                                                         \
+    BParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,              \
+    const float4* __restrict__ rec, const uint32_t* __restrict__ gval,                                 \
+    const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,                         \
+    const float* __restrict__ out_depth, const float* __restrict__ dL_dcolor,                          \
+    const float* __restrict__ dL_dnormal, const float* __restrict__ dL_ddepth,                         \
+    const float* __restrict__ dL_dalpha, const float* __restrict__ inst_w,                             \
+    const uint32_t* __restrict__ cidx, float* __restrict__ rows, const uint32_t* __restrict__ tile_order
+#define PINGS_BLEND_BWD_ARGS                                                                           \
+    p, ranges, point_list, rec, gval, final_T, n_contrib, out_depth, dL_dcolor, dL_dnormal, dL_ddepth, \
+    dL_dalpha, inst_w, cidx, rows, tile_order
+
 // PPL = pixels per lane (same lane -> pixel map as blend_fwd_kernel): the 16 gradient terms of a
 // lane's PPL pixels are summed in registers before the wave reduction, which is the expensive part.
+// PPL 1 / 2 (A/B variants, PINGS_BLEND_BWD_PPL): four / two waves per tile.  PPL 4 (footprint class 2): blend_bwd_tile.
 template <int MODE, int PPL>
-__global__ __launch_bounds__(BLOCK / PPL, PPL == 4 ? 3 : 4) void blend_bwd_kernel(
-    BParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
-    const float4* __restrict__ rec, const uint32_t* __restrict__ gval,
-    const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,
-    const float* __restrict__ out_depth, const float* __restrict__ dL_dcolor,
-    const float* __restrict__ dL_dnormal, const float* __restrict__ dL_ddepth,
-    const float* __restrict__ dL_dalpha, const float* __restrict__ inst_w,
-    const uint32_t* __restrict__ cidx, float* __restrict__ rows, const uint32_t* __restrict__ tile_order) {
+__device__ __forceinline__ void blend_bwd_pixels(PINGS_BLEND_BWD_PARAMS) {
   constexpr int NT = BLOCK / PPL;
   constexpr int NWV = NT / 64;
   __shared__ float4 sA[BATCH], sB[BATCH], sC[BATCH], sD[BATCH];
@@ -359,6 +365,261 @@ __global__ __launch_bounds__(BLOCK / PPL, PPL == 4 ? 3 : 4) void blend_bwd_kerne
       }
     }
   }
+}
+
+// Footprint class 2: ONE wave owns the 16x16 tile, four pixels per lane (lane -> pixel map of blend_fwd_tile_kernel:
+// pixel (h, r) of lane l is (8h + (l & 7), 8r + (l >> 3)) in the tile).  The per-record overhead (LDS record fetch,
+// 16-value wave reduction) is paid once per 256 pixels, and a lane's two pixels of a row (h = 0, 1) are computed as
+// one packed pair (f2: .x = left half, .y = right half): they share the row's dy / ry terms, their x terms are one
+// packed value, and nearly every per-pixel operation becomes one v_pk_* instruction for two pixels.  Only exp and the
+// reciprocals stay scalar.  The alpha / validity decisions are the forward pass's operations, component for component
+// (packed multiplies and adds round each component as the scalar ones do; no contraction there).
+template <int MODE>
+__device__ __forceinline__ void blend_bwd_tile(PINGS_BLEND_BWD_PARAMS) {
+  __shared__ float4 sA[BATCH], sB[BATCH], sC[BATCH], sD[BATCH];
+  __shared__ uint32_t sRow[BATCH];  // compact gradient-row index, DEAD_ROW for dead instances
+  __shared__ float4 sG[BATCH][4];
+  __shared__ uint8_t sList[BATCH];  // live records of the batch that may reach the tile (ascending)
+
+  const int lane = threadIdx.x;
+  const int tile = (int)tile_order[blockIdx.x];   // longest-processing-time-first dispatch (raster_fwd.hip)
+  const int tx = tile % p.gx, ty = tile / p.gx;
+  const int pix_x = tx * TILE + (lane & 7), pix_y0 = ty * TILE + (lane >> 3);
+  const f2 pixf_x = {(float)pix_x, (float)(pix_x + 8)};
+  const float pixf_y[2] = {(float)pix_y0, (float)(pix_y0 + 8)};
+  const float tileX0 = (float)(tx * TILE), tileY0 = (float)(ty * TILE);
+  const size_t HW = (size_t)p.W * p.H;
+
+  f2 rx = {0.f, 0.f};
+  float ry[2] = {0.f, 0.f};
+  if (MODE == MODE_SURFEL) {
+    const float cxp = (p.prcp ? p.prcp[0] : 0.5f) * (float)p.W - 0.5f;
+    const float cyp = (p.prcp ? p.prcp[1] : 0.5f) * (float)p.H - 0.5f;
+    rx = f2{(pixf_x.x - cxp) / p.fx, (pixf_x.y - cxp) / p.fx};
+#pragma unroll
+    for (int r = 0; r < 2; ++r) ry[r] = (pixf_y[r] - cyp) / p.fy;
+  }
+
+  const uint2 range = ranges[tile];
+  // per row r, component h: the pixel (h, r)
+  uint32_t last[2][2];
+  f2 T[2], gC0[2], gC1[2], gC2[2], gN0[2], gN1[2], gN2[2], gD[2];
+  // Bs: blend of s = (upstream gradient) . (record features) over the records behind, normalised, MINUS
+  // coefT / T with coefT = (dL/dalpha_out - bg . dL/dcolor) T_final.  The offset is what makes
+  //   dL/dalpha_rec = (s - Bs_true) Tn + coefT / (1 - alpha) = (s - Bs) Tn
+  // hold with T the transmittance behind the record and Tn = T / (1 - alpha) in front of it, and Bs keeps the same
+  // recurrence Bs <- Bs + alpha (s - Bs): the offset -coefT / T turns into -coefT / Tn exactly when alpha is blended
+  // in.  It starts at -coefT / T_final = bg . dL/dcolor - dL/dalpha_out, and no per-pixel coefT is carried.
+  f2 Bs[2];
+  uint32_t lmax = 0;
+#pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    T[r] = f2{1.f, 1.f};
+    gC0[r] = gC1[r] = gC2[r] = gN0[r] = gN1[r] = gN2[r] = gD[r] = Bs[r] = f2{0.f, 0.f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      last[r][h] = 0;
+      const int pix_y = pix_y0 + 8 * r, pix_xh = pix_x + 8 * h;
+      if (pix_xh < p.W && pix_y < p.H) {
+        const size_t pix_id = (size_t)pix_y * p.W + pix_xh;
+        last[r][h] = n_contrib[pix_id];
+        const float T_final = final_T[pix_id];
+        T[r][h] = T_final;
+        float c0 = 0.f, c1 = 0.f, c2 = 0.f;
+        if (dL_dcolor) {
+          c0 = dL_dcolor[pix_id];
+          c1 = dL_dcolor[HW + pix_id];
+          c2 = dL_dcolor[2 * HW + pix_id];
+        }
+        gC0[r][h] = c0;
+        gC1[r][h] = c1;
+        gC2[r][h] = c2;
+        float gA = dL_dalpha ? dL_dalpha[pix_id] : 0.f;
+        const float gDo = dL_ddepth ? dL_ddepth[pix_id] : 0.f;
+        if (MODE == MODE_SURFEL) {
+          if (dL_dnormal) {
+            gN0[r][h] = dL_dnormal[pix_id];
+            gN1[r][h] = dL_dnormal[HW + pix_id];
+            gN2[r][h] = dL_dnormal[2 * HW + pix_id];
+          }
+          const float A = 1.0f - T_final;
+          if (A > DEPTH_ALPHA_EPS) {
+            gD[r][h] = gDo / A;
+            gA -= gDo * out_depth[pix_id] / A;
+          }
+        } else {
+          gD[r][h] = gDo;
+        }
+        Bs[r][h] = ((p.bg[0] * c0 + p.bg[1] * c1) + p.bg[2] * c2) - gA;
+      }
+      lmax = max(lmax, last[r][h]);
+    }
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) lmax = max(lmax, (uint32_t)__shfl_xor((int)lmax, off, 64));
+  const int max_last = __builtin_amdgcn_readfirstlane((int)lmax);
+  // the 0.5 of the cov2D xx / yy gradient terms, applied to the reduced sums (lane < 16 holds slot red_slot)
+  const int red_slot = ((lane & 1) << 3) | ((lane & 2) << 1) | (lane >> 2);
+  const float red_scale = (red_slot == G_CONX || red_slot == G_CONZ) ? 0.5f : 1.0f;
+
+  const int nbatch = ceil_div(max_last, BATCH);
+  for (int b = nbatch - 1; b >= 0; --b) {
+    const int start = b * BATCH;
+    const int n = min(BATCH, max_last - start);
+    __syncthreads();  // previous batch's LDS fully consumed
+    bool hit = false;
+    if (lane < n) {
+      const uint32_t slot = point_list[range.x + start + lane];
+      const uint32_t g = gval[slot];
+      const float4 ra = rec[4 * (size_t)g + 0];
+      const float4 rb = rec[4 * (size_t)g + 1];
+      sA[lane] = ra;
+      sB[lane] = rb;
+      sC[lane] = rec[4 * (size_t)g + 2];
+      if (MODE == MODE_SURFEL) sD[lane] = rec[4 * (size_t)g + 3];
+      const bool live = inst_w[slot] > 0.f;  // blended something in the forward pass
+      sRow[lane] = live ? cidx[slot] : DEAD_ROW;
+      if (live) hit = quadrant_mask(ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, tileX0, tileY0) != 0u;
+    }
+    const unsigned long long bal = __ballot(hit);
+    if (hit) sList[__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = (uint8_t)lane;
+    const int cnt = __popcll(bal);
+    {
+      float4* z = &sG[0][0];
+      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int e = lane; e < BATCH * 4; e += 64) z[e] = zero;
+    }
+    __syncthreads();
+
+    // Two-deep software pipeline over the list: the INDEX of record jj-2 and the RECORD jj-1 are fetched from LDS
+    // while record jj is processed, so neither LDS latency sits in an iteration's dependency chain.
+    int jcur = cnt > 0 ? (int)sList[cnt - 1] : 0;
+    int jnext = cnt > 1 ? (int)sList[cnt - 2] : 0;
+    float4 a = sA[jcur], bq = sB[jcur], c = sC[jcur], nn = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (MODE == MODE_SURFEL) nn = sD[jcur];
+    for (int jj = cnt - 1; jj >= 0; --jj) {
+      const int j = jcur;
+      const int jn = jnext;
+      const int jn2 = (int)sList[jj > 1 ? jj - 2 : 0];
+      const float4 a_n = sA[jn], b_n = sB[jn], c_n = sC[jn];
+      float4 n_n = nn;
+      if (MODE == MODE_SURFEL) n_n = sD[jn];
+      const float4 ca = a, cb = bq, cc = c, cn = nn;
+      a = a_n; bq = b_n; c = c_n; nn = n_n;
+      jcur = jn;
+      jnext = jn2;
+      const uint32_t idx = (uint32_t)(start + j);
+      // the forward pass's alpha and validity, operation for operation (blend_fwd_tile_kernel)
+      const f2 dx = f2s(ca.x) - pixf_x;
+      const f2 p0 = f2s(-0.5f) * ((f2s(cb.x) * dx) * dx);
+      const f2 pxy = f2s(cb.y) * dx;
+      f2 Gs[2], raw[2], alpha[2];
+      float dyv[2];
+      bool valid[2][2];
+      bool any_v = false;
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const float dy = ca.y - pixf_y[r];
+        dyv[r] = dy;
+        const f2 power = (p0 - f2s(0.5f * (cb.z * dy * dy))) - pxy * f2s(dy);
+        Gs[r] = f2{__expf(power.x), __expf(power.y)};
+        raw[r] = f2s(ca.z) * Gs[r];
+        alpha[r] = f2{fminf(ALPHA_MAX, raw[r].x), fminf(ALPHA_MAX, raw[r].y)};
+        valid[r][0] = idx < last[r][0] && (power.x <= 0.0f) && (alpha[r].x >= ALPHA_MIN);
+        valid[r][1] = idx < last[r][1] && (power.y <= 0.0f) && (alpha[r].y >= ALPHA_MIN);
+        any_v = any_v || valid[r][0] || valid[r][1];
+      }
+      if (!__any(any_v)) continue;
+
+      // gradient accumulation only: multiply-adds may fuse here (fewer instructions, one rounding less per term).
+      // The first row assigns the 16 packed accumulators, the second adds to them; they are folded once per record.
+      {
+#pragma clang fp contract(fast)
+      f2 v2[16];
+      if (MODE != MODE_SURFEL) v2[G_NX] = v2[G_NY] = v2[G_NZ] = v2[G_Q] = v2[G_ZLO] = v2[G_ZHI] = f2{0.f, 0.f};
+      const float zlo = ca.w - cb.w, zhi = ca.w + cb.w;
+      const float zlo_m = fminf(zlo, zhi);   // med3(d, min(lo, hi), hi) == fminf(fmaxf(d, lo), hi) for non-NaN d
+      const f2 cxdx = f2s(cb.x) * dx;        // q = conic . (dx, dy) as two adds per pixel
+#pragma unroll
+      for (int r = 0; r < 2; ++r) {
+        const bool first = r == 0;
+        auto acc = [&](int q, f2 x) { v2[q] = first ? x : v2[q] + x; };
+        // Validity folded into alpha: an invalid pixel blends av = 0, so 1 - av = 1, rcp(1) = 1 exactly and Tn == T
+        // bit for bit; w = av * Tn and T = Tn need no select.
+        const f2 av = sel2(valid[r][0], valid[r][1], alpha[r], f2{0.f, 0.f});
+        const f2 one_m = f2s(1.0f) - av;
+        const f2 inv_one_m = {__builtin_amdgcn_rcpf(one_m.x), __builtin_amdgcn_rcpf(one_m.y)};  // alpha <= 0.99
+        const f2 Tn = T[r] * inv_one_m;
+        const f2 w = av * Tn;
+        // dL/dalpha needs sum_ch (feature_ch - B_ch) g_ch with B the normalised blend of the records behind.  Both
+        // the blend recurrence and the dot product are linear, so ONE scalar per pixel is tracked instead of the
+        // eight channels:  s = g . feature,  dLda = s - Bs,  Bs <- Bs + alpha (s - Bs).
+        f2 sdot = (f2s(cc.x) * gC0[r] + f2s(cc.y) * gC1[r]) + f2s(cc.z) * gC2[r];
+        acc(G_R, gC0[r] * w);
+        acc(G_G, gC1[r] * w);
+        acc(G_B, gC2[r] * w);
+        if (MODE == MODE_SURFEL) {
+          sdot += (f2s(cn.x) * gN0[r] + f2s(cn.y) * gN1[r]) + f2s(cn.z) * gN2[r];
+          // per-pixel depth of this surfel
+          const f2 den = fma2(f2s(cn.x), rx, f2s(fmaf(cn.y, ry[r], cn.z)));
+          const bool hit0 = den.x < -DEN_EPS, hit1 = den.y < -DEN_EPS;
+          const f2 inv_den = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+          const f2 d0 = sel2(hit0, hit1, f2s(cc.w) * inv_den, f2s(ca.w));
+          const f2 d = {__builtin_amdgcn_fmed3f(d0.x, zlo_m, zhi), __builtin_amdgcn_fmed3f(d0.y, zlo_m, zhi)};
+          sdot = fma2(d, gD[r], sdot);
+          const f2 gd = gD[r] * w;
+          const bool lo0 = d0.x < zlo, lo1 = d0.y < zlo, hi0 = d0.x > zhi, hi1 = d0.y > zhi;
+          const bool mid0 = !lo0 && !hi0, mid1 = !lo1 && !hi1;
+          const f2 zero = {0.f, 0.f};
+          acc(G_ZLO, sel2(lo0, lo1, gd, zero));
+          acc(G_ZHI, sel2(hi0, hi1, gd, zero));
+          const f2 gq = sel2(mid0 && hit0, mid1 && hit1, gd * inv_den, zero);
+          acc(G_Q, gq);
+          acc(G_PZ, sel2(mid0 && !hit0, mid1 && !hit1, gd, zero));
+          const f2 gden = -gq * d0;  // = -gd * d0 / den on the unclamped ray hit, else 0
+          v2[G_NX] = fma2(gden, rx, first ? gN0[r] * w : fma2(gN0[r], w, v2[G_NX]));
+          v2[G_NY] = fma2(gden, f2s(ry[r]), first ? gN1[r] * w : fma2(gN1[r], w, v2[G_NY]));
+          v2[G_NZ] = fma2(gN2[r], w, first ? gden : v2[G_NZ] + gden);
+        } else {
+          sdot = fma2(f2s(ca.w), gD[r], sdot);
+          acc(G_PZ, gD[r] * w);
+        }
+        f2 dLda = sdot - Bs[r];
+        Bs[r] = fma2(av, dLda, Bs[r]);
+        dLda = dLda * Tn;
+        // alpha = min(0.99, opacity * G): no gradient through the clamp when it is active
+        dLda = sel2(valid[r][0] && raw[r].x <= ALPHA_MAX, valid[r][1] && raw[r].y <= ALPHA_MAX, dLda, f2{0.f, 0.f});
+        acc(G_OPAC, Gs[r] * dLda);
+        const f2 dLp = raw[r] * dLda;  // dL/dpower = G * (opacity * dL/dalpha)
+        // gradient w.r.t. the 2-D COVARIANCE (see blend_bwd_pixels): every per-pixel term O(1)
+        const f2 qx = cxdx + f2s(cb.y * dyv[r]), qy = pxy + f2s(cb.z * dyv[r]);
+        const f2 ux = dLp * qx, uy = dLp * qy;
+        acc(G_MX, -ux);
+        acc(G_MY, -uy);
+        acc(G_CONX, ux * qx);
+        acc(G_CONY, ux * qy);
+        acc(G_CONZ, uy * qy);
+        T[r] = Tn;
+      }
+      float v[16];
+#pragma unroll
+      for (int q = 0; q < 16; ++q) v[q] = v2[q].x + v2[q].y;
+      const float tot = wave_reduce16(v, lane) * red_scale;
+      if (lane < 16) reinterpret_cast<float*>(&sG[j][0])[red_slot] = tot;
+      }
+    }
+    __syncthreads();
+    for (int e = lane; e < n * 4; e += 64) {
+      const int j = e >> 2, part = e & 3;
+      if (sRow[j] != DEAD_ROW) reinterpret_cast<float4*>(rows)[(size_t)sRow[j] * 4 + part] = sG[j][part];
+    }
+  }
+}
+
+template <int MODE, int PPL>
+__global__ __launch_bounds__(BLOCK / PPL, PPL == 4 ? 3 : 4) void blend_bwd_kernel(PINGS_BLEND_BWD_PARAMS) {
+  if constexpr (PPL == 4) blend_bwd_tile<MODE>(PINGS_BLEND_BWD_ARGS);
+  else blend_bwd_pixels<MODE, PPL>(PINGS_BLEND_BWD_ARGS);
 }
 
 // ---------------------------------------------------------------- blend backward, Gaussian-per-lane ("wave64 scan")

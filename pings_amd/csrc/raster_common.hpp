@@ -141,6 +141,14 @@ int occlusion_buckets(int num_tiles);
 BinState carve_binning(void* blob, int64_t I, int num_tiles);
 ImageState carve_image(void* blob, int W, int H);
 
+// Two fp32 values in one VGPR pair: + - * on f2 compile to v_pk_add_f32 / v_pk_mul_f32, fma2 to v_pk_fma_f32.  Each
+// component is rounded exactly as the scalar instruction rounds it, so a packed multiply or add may stand in for a
+// scalar one wherever results must stay bit-identical (the class-2 blend kernels pair a lane's two x halves).
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ inline f2 f2s(float x) { return f2{x, x}; }
+__device__ inline f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ inline f2 sel2(bool c0, bool c1, f2 a, f2 b) { return f2{c0 ? a.x : b.x, c1 ? a.y : b.y}; }
+
 // wave64 sum through DPP; the total ends up in lane 63.
 template <int CTRL>
 __device__ inline float dpp_mov(float v) {

@@ -1813,7 +1813,12 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
   }
   const uint2 range = ranges[tile];
   const int todo = (int)(range.y - range.x);
-  float T[PPL], C0[PPL], C1[PPL], C2[PPL], N0[PPL], N1[PPL], N2[PPL], D[PPL];
+  // pixel state per row r = k >> 1 as packed pairs (f2 component h = k & 1): the two pixels of a row share the
+  // record's dy terms, and every per-pixel multiply / add / fma below is one v_pk_* instruction for both, rounded per
+  // component as the scalar instruction would be — images, final_T and n_contrib stay bit-identical to the
+  // pixel-per-lane kernel.
+  const f2 pixf_x2 = {pixf_x[0], pixf_x[1]}, rx2 = {rx[0], rx[1]};
+  f2 T[2], C0[2], C1[2], C2[2], N0[2], N1[2], N2[2], D[2];
   uint32_t last[PPL];
   bool inside[PPL];
   // A pixel that has stopped (or lies outside the image) is "done".  Instead of a boolean that the compiler keeps as a
@@ -1825,9 +1830,12 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
   float amin[PPL];
   int live_px = 0;   // wave-uniform
 #pragma unroll
+  for (int r = 0; r < 2; ++r) {
+    T[r] = f2{1.0f, 1.0f};
+    C0[r] = C1[r] = C2[r] = N0[r] = N1[r] = N2[r] = D[r] = f2{0.f, 0.f};
+  }
+#pragma unroll
   for (int k = 0; k < PPL; ++k) {
-    T[k] = 1.0f;
-    C0[k] = C1[k] = C2[k] = N0[k] = N1[k] = N2[k] = D[k] = 0.f;
     last[k] = 0;
     inside[k] = pix_x[k & 1] < p.W && pix_y[k >> 1] < p.H;
     amin[k] = inside[k] ? ALPHA_MIN : DONE_AMIN;
@@ -1907,30 +1915,31 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
           const float4 a = sA[j], b = sB[j], c = sC[j];
           float4 nn = make_float4(0.f, 0.f, 0.f, 0.f);
           if (MODE == MODE_SURFEL) nn = sD[j];
-          float dxv[2], p0v[2], pxyv[2];
-#pragma unroll
-          for (int h = 0; h < 2; ++h) {
-            dxv[h] = a.x - pixf_x[h];
-            p0v[h] = -0.5f * (b.x * dxv[h] * dxv[h]);
-            pxyv[h] = b.y * dxv[h];
-          }
-          float alpha[PPL], test_T[PPL];
+          const f2 dx = f2s(a.x) - pixf_x2;
+          const f2 p0 = f2s(-0.5f) * ((f2s(b.x) * dx) * dx);
+          const f2 pxy = f2s(b.y) * dx;
+          f2 alpha[2], test_T[2];
           bool contrib[PPL];
           bool any_c = false;
           int n_stop = 0;
 #pragma unroll
-          for (int k = 0; k < PPL; ++k) {
-            const float dy = a.y - pixf_y[k >> 1];
-            const float power = (p0v[k & 1] - 0.5f * (b.z * dy * dy)) - pxyv[k & 1] * dy;
-            alpha[k] = fminf(ALPHA_MAX, a.z * __expf(power));
-            const bool valid = (power <= 0.0f) && (alpha[k] >= amin[k]);   // amin folds in !done
-            test_T[k] = T[k] * (1.0f - alpha[k]);
-            const bool lt = test_T[k] < T_EPS;
-            const bool stop = valid && lt;
-            contrib[k] = valid && !lt;
-            amin[k] = stop ? DONE_AMIN : amin[k];
-            n_stop += __popcll(__ballot(stop));
-            any_c = any_c || contrib[k];
+          for (int r = 0; r < 2; ++r) {
+            const float dy = a.y - pixf_y[r];
+            const f2 power = (p0 - f2s(0.5f * (b.z * dy * dy))) - pxy * f2s(dy);
+            const f2 ag = f2s(a.z) * f2{__expf(power.x), __expf(power.y)};
+            alpha[r] = f2{fminf(ALPHA_MAX, ag.x), fminf(ALPHA_MAX, ag.y)};
+            test_T[r] = T[r] * (f2s(1.0f) - alpha[r]);
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {
+              const int k = 2 * r + h;
+              const bool valid = (power[h] <= 0.0f) && (alpha[r][h] >= amin[k]);   // amin folds in !done
+              const bool lt = test_T[r][h] < T_EPS;
+              const bool stop = valid && lt;
+              contrib[k] = valid && !lt;
+              amin[k] = stop ? DONE_AMIN : amin[k];
+              n_stop += __popcll(__ballot(stop));
+              any_c = any_c || contrib[k];
+            }
           }
           live_px -= n_stop;
           if (__any(any_c)) {
@@ -1939,26 +1948,30 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
             // (lo > hi clamps to hi either way), and d is never NaN here
             const float zhi = a.w + b.w, zlo = fminf(a.w - b.w, zhi);
 #pragma unroll
-            for (int k = 0; k < PPL; ++k) {
-              const float w = contrib[k] ? alpha[k] * T[k] : 0.f;
-              C0[k] = fmaf(c.x, w, C0[k]);
-              C1[k] = fmaf(c.y, w, C1[k]);
-              C2[k] = fmaf(c.z, w, C2[k]);
+            for (int r = 0; r < 2; ++r) {
+              const bool c0 = contrib[2 * r], c1 = contrib[2 * r + 1];
+              const f2 w = sel2(c0, c1, alpha[r] * T[r], f2{0.f, 0.f});
+              C0[r] = fma2(f2s(c.x), w, C0[r]);
+              C1[r] = fma2(f2s(c.y), w, C1[r]);
+              C2[r] = fma2(f2s(c.z), w, C2[r]);
               if (MODE == MODE_SURFEL) {
-                const float den = (nn.x * rx[k & 1] + nn.y * ry[k >> 1]) + nn.z;
-                const float d0 = den < -DEN_EPS ? c.w * __builtin_amdgcn_rcpf(den) : a.w;
-                const float d = __builtin_amdgcn_fmed3f(d0, zlo, zhi);
-                N0[k] = fmaf(nn.x, w, N0[k]);
-                N1[k] = fmaf(nn.y, w, N1[k]);
-                N2[k] = fmaf(nn.z, w, N2[k]);
-                D[k] = fmaf(d, w, D[k]);
+                const f2 den = (f2s(nn.x) * rx2 + f2s(nn.y * ry[r])) + f2s(nn.z);
+                const f2 dq = f2s(c.w) * f2{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+                const f2 d0 = sel2(den.x < -DEN_EPS, den.y < -DEN_EPS, dq, f2s(a.w));
+                const f2 d = {__builtin_amdgcn_fmed3f(d0.x, zlo, zhi), __builtin_amdgcn_fmed3f(d0.y, zlo, zhi)};
+                N0[r] = fma2(f2s(nn.x), w, N0[r]);
+                N1[r] = fma2(f2s(nn.y), w, N1[r]);
+                N2[r] = fma2(f2s(nn.z), w, N2[r]);
+                D[r] = fma2(d, w, D[r]);
               } else {
-                D[k] = fmaf(a.w, w, D[k]);
-                touched += (contrib[k] && test_T[k] > 0.5f) ? 1u : 0u;
+                D[r] = fma2(f2s(a.w), w, D[r]);
+                touched += (c0 && test_T[r].x > 0.5f) ? 1u : 0u;
+                touched += (c1 && test_T[r].y > 0.5f) ? 1u : 0u;
               }
-              T[k] = contrib[k] ? test_T[k] : T[k];
-              last[k] = contrib[k] ? e1 : last[k];
-              wsum = k == 0 ? w : wsum + w;   // w >= +0: the same bits as 0.f + w
+              T[r] = sel2(c0, c1, test_T[r], T[r]);
+              last[2 * r] = c0 ? e1 : last[2 * r];
+              last[2 * r + 1] = c1 ? e1 : last[2 * r + 1];
+              wsum = r == 0 ? w.x + w.y : (wsum + w.x) + w.y;   // pixel order k = 0..3, as the scalar sum
             }
           }
         }
@@ -1988,21 +2001,23 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
 #pragma unroll
   for (int k = 0; k < PPL; ++k) {
     if (!inside[k]) continue;
-    const size_t pix_id = (size_t)pix_y[k >> 1] * p.W + pix_x[k & 1];
-    const float A = 1.0f - T[k];
-    final_T[pix_id] = T[k];
+    const int r = k >> 1, h = k & 1;
+    const float Tk = T[r][h];
+    const size_t pix_id = (size_t)pix_y[r] * p.W + pix_x[h];
+    const float A = 1.0f - Tk;
+    final_T[pix_id] = Tk;
     n_contrib[pix_id] = last[k];
-    out_color[pix_id] = C0[k] + T[k] * p.bg[0];
-    out_color[HW + pix_id] = C1[k] + T[k] * p.bg[1];
-    out_color[2 * HW + pix_id] = C2[k] + T[k] * p.bg[2];
+    out_color[pix_id] = C0[r][h] + Tk * p.bg[0];
+    out_color[HW + pix_id] = C1[r][h] + Tk * p.bg[1];
+    out_color[2 * HW + pix_id] = C2[r][h] + Tk * p.bg[2];
     out_alpha[pix_id] = A;
     if (MODE == MODE_SURFEL) {
-      out_normal[pix_id] = N0[k];
-      out_normal[HW + pix_id] = N1[k];
-      out_normal[2 * HW + pix_id] = N2[k];
-      out_depth[pix_id] = D[k] / fmaxf(A, DEPTH_ALPHA_EPS);
+      out_normal[pix_id] = N0[r][h];
+      out_normal[HW + pix_id] = N1[r][h];
+      out_normal[2 * HW + pix_id] = N2[r][h];
+      out_depth[pix_id] = D[r][h] / fmaxf(A, DEPTH_ALPHA_EPS);
     } else {
-      out_depth[pix_id] = D[k];
+      out_depth[pix_id] = D[r][h];
     }
   }
 }
