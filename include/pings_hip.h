@@ -960,4 +960,21 @@ PINGS_API int pings_sdf_loss_backward(const pings_sdf_loss_args* a, void* stream
 /* Number of per-block partials the reduce writes (part holds 4 doubles each). */
 PINGS_API int pings_sdf_loss_partials(int64_t B, int64_t cap);
 
+/* ------------------------------------------------------ marching cubes (csrc/mc.hip)
+ * The surface `v = level` of a C-contiguous [nx, ny, nz] fp32 volume (point (i, j, k) at (i*ny + j)*nz + k), by the
+ * rules of DESIGN §2.7: cell (i, j, k) is processed iff mask[i, j, k] != 0 (mask NULL: every cell) and its 8 corners
+ * are finite; vertices in index units, ascending key 4 p + slot (slot 0 the grid point p, 1..3 its +x, +y, +z edge);
+ * faces int64 vertex indices in ascending cell order.  Two phases with one host read between them:
+ *   count   per-block counts, scans and totals[2] (HOST): vertices, faces
+ *   emit    keys[nv] (int64 workspace), verts[nv, 3], faces[nf, 3] with the nv / nf of the count call on the same
+ *           inputs and the same scratch (pings_mc_scratch_bytes: O(nx*ny*nz / 256) bytes; 0 for a bad shape). */
+#define PINGS_MC_ALLOW_DEGENERATE 1   /* keep faces with a repeated vertex                                           */
+#define PINGS_MC_ASCENT 2             /* gradient_direction 'ascent': right-hand normals toward increasing values     */
+PINGS_API size_t pings_mc_scratch_bytes(int64_t nx, int64_t ny, int64_t nz);
+PINGS_API int pings_mc_count(const float* vol, const uint8_t* mask, int64_t nx, int64_t ny, int64_t nz, float level,
+                             int flags, void* scratch, int64_t* totals, void* stream);
+PINGS_API int pings_mc_emit(const float* vol, const uint8_t* mask, int64_t nx, int64_t ny, int64_t nz, float level,
+                            int flags, const void* scratch, int64_t nv, int64_t nf, int64_t* keys, float* verts,
+                            int64_t* faces, void* stream);
+
 #endif /* PINGS_HIP_H_ */

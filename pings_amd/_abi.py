@@ -14,6 +14,7 @@ RASTER_SURFEL, RASTER_3DGS, RASTER_2DGS = 0, 1, 2                 # PINGS_RASTER
 HEAD_COLOR, HEAD_SEMANTIC = 0, 1                                  # PINGS_HEAD_*: pings_head_reduce mode
 REG_SINGULAR, REG_ILL_CONDITIONED, REG_NONFINITE = 1, 2, 4        # PINGS_REG_*: pings_reg_solve_checked status bits
 REG_F_NORMALS, REG_F_DIV_GRAD, REG_F_WEIGHTED = 1, 2, 4           # PINGS_REG_F_*: pings_reg_loop_args.flags
+MC_ALLOW_DEGENERATE, MC_ASCENT = 1, 2                             # PINGS_MC_*: pings_mc_count / pings_mc_emit flags
 
 vp = C.c_void_p     # device pointers and the hipStream_t travel as integers (tensor.data_ptr())
 i32, i64, f32, sz = C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -263,4 +264,8 @@ SIGNATURES = {
     "pings_sdf_loss_reduce": (i32, [C.POINTER(SdfLossArgs), vp]),
     "pings_sdf_loss_backward": (i32, [C.POINTER(SdfLossArgs), vp]),
     "pings_sdf_loss_partials": (i32, [i64, i64]),
+    # marching cubes
+    "pings_mc_scratch_bytes": (sz, [i64, i64, i64]),
+    "pings_mc_count": (i32, [vp, vp, i64, i64, i64, f32, i32, vp, C.POINTER(i64), vp]),
+    "pings_mc_emit": (i32, [vp, vp, i64, i64, i64, f32, i32, vp, i64, i64, vp, vp, vp, vp]),
 }

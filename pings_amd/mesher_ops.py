@@ -7,9 +7,14 @@ result arrays; the host copy happens once at the end.  The colour and semantic h
 HIP `query_feature`, the head's decoder through the fused MFMA kernels and one activation + IDW-sum (+ arg-max) pass
 (`pings_head_reduce`).  Same arguments and the same 4-tuple
 (sdf_pred, sem_pred, color_pred, mc_mask) with the reference's container types: numpy float64 arrays, or CPU float32
-tensors with `out_torch=True`.  `install(mesher_module)` rebinds the method."""
+tensors with `out_torch=True`.  `install(mesher_module)` rebinds the method.
+
+Marching cubes (`Mesher.mc_mesh`, skimage on the host in the reference) runs on the device too: `marching_cubes`
+(csrc/mc.hip), the drop-ins `mc_mesh` / `mc_mesh_torch` (`install(M, mc=True)`), and `mesh_bbx`, one
+chunk from box to mesh without a host copy of the grid."""
 from __future__ import annotations
 
+import ctypes as C
 import math
 
 import numpy as np
@@ -38,8 +43,9 @@ def head_reduce(raw: torch.Tensor, w_knn, mode: int):
     return val if mode == _abi.HEAD_COLOR else lab
 
 
-def query_points(self, coord, bs, query_sdf=True, query_sem=False, query_color=False, query_mask=True,
-                 query_locally=False, mask_min_nn_count: int = 4, out_torch: bool = False):
+def _query_device(self, coord, bs, query_sdf=True, query_sem=False, query_color=False, query_mask=True,
+                  query_locally=False, mask_min_nn_count: int = 4):
+    """The batch loop of `query_points` with its results left on the device: (sdf, sem, color, mask) tensors or None."""
     if not coord.is_cuda:
         raise _lib.PingsHipError("Mesher.query_points runs on the HIP device only (got a CPU tensor); "
                                  "there is no CPU fallback")
@@ -79,6 +85,13 @@ def query_points(self, coord, bs, query_sdf=True, query_sem=False, query_color=F
                     color[head:tail] = head_reduce(_dec.mlp(self.color_mlp, cf), wk, _abi.HEAD_COLOR)
                 if query_sem:
                     sem[head:tail] = head_reduce(_dec.mlp(self.sem_mlp, gf), wk, _abi.HEAD_SEMANTIC).to(sem.dtype)
+    return sdf, sem, color, mask
+
+
+def query_points(self, coord, bs, query_sdf=True, query_sem=False, query_color=False, query_mask=True,
+                 query_locally=False, mask_min_nn_count: int = 4, out_torch: bool = False):
+    sdf, sem, color, mask = _query_device(self, coord, bs, query_sdf, query_sem, query_color, query_mask, query_locally,
+                                          mask_min_nn_count)
     if out_torch:
         host = lambda t: None if t is None else t.cpu()
     else:
@@ -86,6 +99,118 @@ def query_points(self, coord, bs, query_sdf=True, query_sem=False, query_color=F
     return host(sdf), host(sem), host(color), host(mask)
 
 
-def install(mesher_module) -> None:
-    """`import utils.mesher as M; install(M)`: Mesher.query_points -> one fused kernel launch per batch."""
+# ------------------------------------------------------------------ marching cubes (utils/mesher.py:363-389, :570-581)
+def marching_cubes(volume: torch.Tensor, level: float = 0.0, mask=None, allow_degenerate: bool = False,
+                   gradient_direction: str = "descent"):
+    """The surface `volume == level` of a device [nx, ny, nz] grid (csrc/mc.hip, rules in DESIGN §2.7): verts [V, 3]
+    fp32 in index units, faces [F, 3] int64, both on the device.  `mask` (any dtype, nonzero = true, the volume's
+    shape) gates each cell by its lowest corner.  One host read per call (the two totals)."""
+    if gradient_direction not in ("descent", "ascent"):
+        raise ValueError(f"gradient_direction must be 'descent' or 'ascent', got {gradient_direction!r}")
+    if not volume.is_cuda:
+        raise _lib.PingsHipError("marching_cubes runs on the HIP device only (got a CPU tensor); "
+                                 "there is no CPU fallback")
+    if volume.dim() != 3:
+        raise ValueError(f"marching_cubes needs a 3-D volume, got shape {tuple(volume.shape)}")
+    dev = volume.device
+    vol = volume.detach().to(torch.float32).contiguous()
+    nx, ny, nz = (int(d) for d in vol.shape)
+    empty = torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int64, device=dev)
+    if vol.numel() == 0:
+        return empty
+    m = None
+    if mask is not None:
+        if tuple(mask.shape) != (nx, ny, nz):
+            raise ValueError(f"mask shape {tuple(mask.shape)} differs from the volume's {(nx, ny, nz)}")
+        if not mask.is_cuda:
+            raise _lib.PingsHipError("marching_cubes: the mask must be on the HIP device")
+        m = (mask.detach() != 0).to(torch.uint8).contiguous()
+    flags = (_abi.MC_ALLOW_DEGENERATE if allow_degenerate else 0) | (_abi.MC_ASCENT if gradient_direction == "ascent" else 0)
+    L = _lib.lib()
+    st = _lib.stream_ptr(dev)
+    scratch = torch.empty(L.pings_mc_scratch_bytes(nx, ny, nz), dtype=torch.uint8, device=dev)
+    tot = (C.c_int64 * 2)(0, 0)
+    _lib.note_sync("mc_count")
+    _lib.check(L.pings_mc_count(_lib.ptr(vol), _lib.ptr(m), nx, ny, nz, float(level), flags, _lib.ptr(scratch), tot, st),
+               "pings_mc_count")
+    nv, nf = int(tot[0]), int(tot[1])
+    if nv == 0:
+        return empty
+    keys = torch.empty(nv, dtype=torch.int64, device=dev)
+    verts = torch.empty(nv, 3, device=dev)
+    faces = torch.empty(nf, 3, dtype=torch.int64, device=dev)
+    _lib.check(L.pings_mc_emit(_lib.ptr(vol), _lib.ptr(m), nx, ny, nz, float(level), flags, _lib.ptr(scratch), nv, nf,
+                               _lib.ptr(keys), _lib.ptr(verts), _lib.ptr(faces), st), "pings_mc_emit")
+    return verts, faces
+
+
+def _device(self):
+    dev = getattr(self, "cur_device", None) or getattr(self, "device", None)
+    dev = torch.device(dev) if dev is not None else torch.device("cuda", torch.cuda.current_device())
+    return dev if dev.type == "cuda" else torch.device("cuda", torch.cuda.current_device())
+
+
+def mc_mesh(self, mc_sdf, mc_mask, voxel_size, mc_origin):
+    """`Mesher.mc_mesh` (mesher.py:363-389) on the device: numpy grid and mask in, numpy (verts, faces) out, verts in
+    world units.  No surface: the reference's `except` return, zeros((0, 3)) for both (verts shifted by the origin)."""
+    dev = _device(self)
+    vol = torch.from_numpy(np.ascontiguousarray(mc_sdf, dtype=np.float32)).to(dev)
+    mask = None if mc_mask is None else torch.from_numpy(np.ascontiguousarray(mc_mask)).to(dev)
+    verts, faces = marching_cubes(vol, 0.0, mask, allow_degenerate=False)
+    if faces.shape[0] == 0:
+        return mc_origin + np.zeros((0, 3)) * voxel_size, np.zeros((0, 3))
+    return mc_origin + verts.cpu().numpy() * voxel_size, faces.cpu().numpy()
+
+
+def mc_mesh_torch(self, mc_sdf, mc_mask, voxel_size, mc_origin):
+    """The `Mesher.mc_mesh_torch` that `recon_aabb_mesh(use_torch_mc=True)` calls (mesher.py:570-581): CPU or device
+    tensors in, device (verts in world units, fp32 origin + verts * voxel_size; faces int64) out."""
+    dev = mc_sdf.device if mc_sdf.is_cuda else _device(self)
+    vol = mc_sdf.to(dev, torch.float32)
+    mask = None if mc_mask is None else mc_mask.to(dev)
+    verts, faces = marching_cubes(vol, 0.0, mask, allow_degenerate=False)
+    origin = torch.as_tensor(mc_origin).to(dev, torch.float32)
+    return origin + verts * voxel_size, faces
+
+
+def grid_from_bbx(bbx_min, bbx_max, voxel_size, pad_voxel=0, skip_top_voxel=0, device=None):
+    """`Mesher.get_query_from_bbx` (mesher.py:168-212) on the device: (coord [N, 3] fp32, voxel_num_xyz, voxel_origin),
+    or (None, None, None) past the reference's 5e8-point cap."""
+    min_bound, max_bound = np.asarray(bbx_min, dtype=np.float64), np.asarray(bbx_max, dtype=np.float64)
+    num = (np.ceil((max_bound - min_bound) / voxel_size) + pad_voxel * 2).astype(np.int_)
+    origin = min_bound - pad_voxel * voxel_size
+    origin[2] -= voxel_size          # one extra voxel underground
+    num[2] += 1
+    num[2] -= skip_top_voxel
+    if num[0] * num[1] * num[2] > 5e8:
+        return None, None, None
+    ax = [torch.arange(int(k), dtype=torch.int16, device=device) for k in num]
+    x, y, z = torch.meshgrid(*ax, indexing="ij")
+    coord = torch.stack((x.flatten(), y.flatten(), z.flatten())).transpose(0, 1).float()
+    coord *= voxel_size
+    coord += torch.tensor(origin, dtype=torch.float32, device=device)
+    return coord, num, origin
+
+
+def mesh_bbx(self, bbx_min, bbx_max, voxel_size, query_locally=False, mesh_min_nn=10):
+    """One mesher chunk on the device (recon_aabb_mesh, mesher.py:540-581, without Open3D): the grid by
+    `get_query_from_bbx`'s rule with config.pad_voxel / skip_top_voxel, the fused SDF + mask query, marching cubes.
+    -> (verts [V, 3] fp32 world units, faces [F, 3] int64) on the device, or None past the 5e8-point cap."""
+    cfg = self.config
+    coord, num, origin = grid_from_bbx(bbx_min, bbx_max, voxel_size, cfg.pad_voxel, cfg.skip_top_voxel, _device(self))
+    if coord is None:
+        return None
+    sdf, _, _, mask = _query_device(self, coord, cfg.infer_bs, True, False, False, getattr(cfg, "mc_mask_on", True),
+                                    query_locally, mesh_min_nn)
+    shape = tuple(int(k) for k in num)
+    verts, faces = marching_cubes(sdf.view(shape), 0.0, None if mask is None else mask.view(shape))
+    return torch.tensor(origin, dtype=torch.float32, device=coord.device) + verts * voxel_size, faces
+
+
+def install(mesher_module, mc: bool = False) -> None:
+    """`import utils.mesher as M; install(M)`: Mesher.query_points -> one fused kernel launch per batch.  With mc=True
+    also Mesher.mc_mesh and Mesher.mc_mesh_torch -> marching cubes on the device (csrc/mc.hip)."""
     mesher_module.Mesher.query_points = query_points
+    if mc:
+        mesher_module.Mesher.mc_mesh = mc_mesh
+        mesher_module.Mesher.mc_mesh_torch = mc_mesh_torch
