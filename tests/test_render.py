@@ -113,11 +113,11 @@ def test_render_none_cases():
     assert render(cam, None, data, decs, None, bg, view_concat_on=True) is not None
 
 
-@pytest.mark.gpu
-@pytest.mark.parametrize("hw", [(96, 160), (37, 53)])
-def test_exposure_affine_matches_the_reference_expression(hw):
+def _check_exposure(hw, misaligned=False, img_grad=True):
     """`pings_exposure_forward/backward` vs the reference's own expression (gaussian_renderer/__init__.py:454-458) in
-    fp64: image, and gradients w.r.t. the image, the 3x3 matrix and the offset; bitwise reproducible."""
+    fp64: image, and gradients w.r.t. the image, the 3x3 matrix and the offset; bitwise reproducible.
+    misaligned: the image is a view one element into a larger buffer (not 16-byte aligned: the scalar path);
+    img_grad=False: the image does not require grad (no image gradient is written)."""
     from pings_amd.image_ops import exposure_affine
 
     H, W = hw
@@ -128,17 +128,50 @@ def test_exposure_affine_matches_the_reference_expression(hw):
     up = torch.randn(3, H, W, generator=g)
     i64, M64, b64 = (t.double().requires_grad_(True) for t in (img, M, b))
     ref = (i64.permute(1, 2, 0).reshape(-1, 3) @ M64.T + b64).view(H, W, 3).permute(2, 0, 1)
-    gref = torch.autograd.grad((ref * up.double()).sum(), [i64, M64, b64])
+    wrt = [i64, M64, b64] if img_grad else [M64, b64]
+    gref = torch.autograd.grad((ref * up.double()).sum(), wrt)
     outs = []
     for _ in range(2):
-        ih, Mh, bh = (t.cuda().requires_grad_(True) for t in (img, M, b))
+        if misaligned:
+            buf = torch.zeros(img.numel() + 4, device="cuda")
+            buf[1:1 + img.numel()].copy_(img.reshape(-1).cuda())
+            ih = buf[1:1 + img.numel()].view(3, H, W).detach()
+            assert ih.data_ptr() % 16 != 0 and (H * W) % 4 == 0   # HW % 4 == 0, yet not float4-addressable
+        else:
+            ih = img.cuda()
+        ih.requires_grad_(img_grad)
+        Mh, bh = (t.cuda().requires_grad_(True) for t in (M, b))
         out = exposure_affine(ih, Mh, bh)
-        outs.append((out,) + torch.autograd.grad((out * up.cuda()).sum(), [ih, Mh, bh]))
+        outs.append((out,) + torch.autograd.grad((out * up.cuda()).sum(), [ih, Mh, bh] if img_grad else [Mh, bh]))
     assert rel_err(outs[0][0], ref) <= 1e-6
     for a, r in zip(outs[0][1:], gref):
         assert rel_err(a, r) <= 1e-5
     for a, c in zip(*outs):
         assert torch.equal(a, c)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hw", [(96, 160), (37, 53)])
+def test_exposure_affine_matches_the_reference_expression(hw):
+    _check_exposure(hw)
+
+
+@pytest.mark.gpu
+def test_exposure_affine_at_1080p():
+    """1,024 workgroups, two grid-stride iterations per thread on the float4 path."""
+    _check_exposure((1080, 1920))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hw", [(96, 160), (1080, 1920)])
+def test_exposure_affine_scalar_path_on_unaligned_storage(hw):
+    _check_exposure(hw, misaligned=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("hw", [(96, 160), (37, 53)])
+def test_exposure_affine_image_without_grad(hw):
+    _check_exposure(hw, img_grad=False)
 
 
 # ------------------------------------------------------------------ one host synchronisation per frame
