@@ -22,41 +22,18 @@
 // zero gradient where active, min(0.99, .) included).
 #include <hipcub/hipcub.hpp>
 
-#include <cstdlib>
-#include <cstring>
+#include <algorithm>
+#include <type_traits>
 
 #include "raster_common.hpp"
 
 namespace pings {
 namespace raster {
 
-struct BParams {
-  int P, W, H, gx, gy;
-  int front_only;
-  float fx, fy, limx, limy, scale_mod;
-  const float* view;
-  const float* proj_raw;
-  const float* bg;
-  const float* prcp;
-};
-
 constexpr int BATCH = 64;
-// blend_bwd_scan_kernel: tiles whose largest per-pixel contributor count reaches the threshold get four waves per
-// quadrant (PINGS_BWD_LONG overrides the threshold, 0 = never); at most LONG_TILES_MAX tiles per frame, taken as whole
-// bins of tile_order_kernel (work / 16, clamped to 1023) from the top down, so that the set of split tiles depends on the
-// per-tile work alone — when the bins at or above the threshold hold more than the cap, the lowest of them stay unsplit,
-// and a threshold above 16,368 splits nothing.  C3 street
-// sweep (r03, kernel ms): never 0.72, 256 0.65, 768 0.59, 2048 0.535, 3072 0.53, 4096 0.52, 8192 0.57 — the split
-// costs four queue walks and two barriers per chunk, so only the lists that set the kernel's duration should pay it.
+// cap on the tiles per frame that blend_bwd_scan_kernel splits over four waves per quadrant (BlendPlan::long_thr)
 constexpr uint32_t LONG_TILES_MAX = 2048;
-inline uint32_t long_list_threshold() {
-  long v = 3072;
-  if (const char* e = getenv("PINGS_BWD_LONG")) v = atol(e);   // read per call: tests switch it
-  if (v <= 0) return 0xFFFFFFF0u;
-  return (uint32_t)((v + 15) / 16 * 16);
-}
 constexpr uint32_t DEAD_ROW = 0xFFFFFFFFu;
-constexpr int CH = 64;  // rows per first-level chunk of the per-Gaussian sum
 
 #define PINGS_BLEND_BWD_PARAMS                                                                         \
     BParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,              \
@@ -1329,50 +1306,7 @@ __global__ __launch_bounds__(256) void tau_reduce_kernel(const float* __restrict
 }  // namespace raster
 }  // namespace pings
 
-namespace pings {
-namespace raster {
-
-struct BwdState {
-  uint32_t* cidx;        // [I+2] exclusive scan of live flags over instance slots (cidx[I] = #live)
-  float* rows;           // [I][16] gradient rows of live instances (upper bound; only #live used)
-  uint32_t *cbeg, *nch, *pair_off, *pair_owner;
-  float* partials;       // [NPmax][16]
-  float* tau_partials;   // [ceil(P/256)][6]
-  char* temp;
-  size_t temp_bytes, np_max, total;
-};
-
-static BwdState carve_bwd(void* blob, int P, int64_t I) {
-  Carver c(blob);
-  BwdState b;
-  // gradient rows: one per live (instance, 8x8 quadrant) pair in the Gaussian-per-lane kernel, i.e. at most 4 I
-  const size_t ni = (size_t)(I > 0 ? I : 1), n = 4 * ni, np = (size_t)(P > 0 ? P : 1);
-  b.np_max = n / CH + np + 1;
-  b.cidx = c.take<uint32_t>(ni + 2);
-  b.cbeg = c.take<uint32_t>(np + 1);
-  b.nch = c.take<uint32_t>(np + 1);
-  b.pair_off = c.take<uint32_t>(np + 1);
-  b.pair_owner = c.take<uint32_t>(b.np_max);
-  b.partials = c.take<float>(b.np_max * GRAD_ROW);
-  b.tau_partials = c.take<float>((size_t)ceil_div((int)np, 256) * 6);
-  size_t a = 0, d = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(ni + 1));
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, d, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(np + 1));
-  b.temp_bytes = align_up(a > d ? a : d) + 256;
-  b.temp = c.take<char>(b.temp_bytes);
-  b.rows = c.take<float>(n * GRAD_ROW);
-  b.total = c.off;
-  return b;
-}
-
-}  // namespace raster
-}  // namespace pings
-
 using namespace pings::raster;
-
-PINGS_API size_t pings_raster_backward_bytes(int P, int64_t num_instances) {
-  return carve_bwd(nullptr, P, num_instances).total;
-}
 
 PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64_t I,
                                     const float* means3D, const float* colors,
@@ -1387,8 +1321,8 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
                                     float* dL_dcolors, float* dL_dopacities, float* dL_dscales,
                                     float* dL_drotations, float* dL_dtau, int footprint_class,
                                     void* stream) {
-  PINGS_ARG_CHECK(s != nullptr, "null settings");
-  PINGS_ARG_CHECK(s->mode == PINGS_RASTER_SURFEL || s->mode == PINGS_RASTER_3DGS, "unknown mode");
+  BParams bp;
+  if (int e = fill_camera(s, P, bp)) return e;
   PINGS_ARG_CHECK(dL_dtau != nullptr, "null dL_dtau");
   hipStream_t st = pings::as_stream(stream);
   if (P == 0) {   // otherwise tau_reduce_kernel writes all six
@@ -1401,38 +1335,18 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
                   "null pointer");
   PINGS_ARG_CHECK(I >= 0 && I < (int64_t)0x7FFFFFF0, "instance count out of range");
   (void)out_color; (void)out_normal; (void)out_alpha;
-  BParams bp;
-  bp.P = P;
-  bp.W = s->image_width;
-  bp.H = s->image_height;
-  bp.gx = pings::ceil_div(bp.W, TILE);
-  bp.gy = pings::ceil_div(bp.H, TILE);
-  bp.front_only = s->front_only;
-  bp.fx = (float)((double)bp.W / (2.0 * s->tanfovx));
-  bp.fy = (float)((double)bp.H / (2.0 * s->tanfovy));
-  bp.limx = (float)(1.3 * s->tanfovx);
-  bp.limy = (float)(1.3 * s->tanfovy);
-  bp.scale_mod = (float)s->scale_modifier;
-  bp.view = s->viewmatrix;
-  bp.proj_raw = s->projmatrix_raw;
-  bp.bg = s->bg;
-  bp.prcp = s->prcppoint;
+  const RasterKnobs knobs = read_knobs();
   const int num_tiles = bp.gx * bp.gy;
+  const BlendPlan plan = blend_plan(knobs, footprint_class, I, num_tiles);
   GeomState gs = carve_geom(const_cast<void*>(geom_blob), P, num_tiles);
-  BinState bs = carve_binning(const_cast<void*>(binning_blob), I, num_tiles);
+  BinState bs = carve_binning(const_cast<void*>(binning_blob), I, num_tiles, knobs.blend_seg);
   ImageState im = carve_image(const_cast<void*>(image_blob), bp.W, bp.H);
   BwdState bw = carve_bwd(bwd_blob, P, I);
   const dim3 gridP(pings::ceil_div(P + 1, 256)), block(256);
-  // Blend backward kernel: Gaussian-per-lane wave scans when footprints are small (lanes of the pixel-per-lane kernel
-  // would idle: 2.25x faster on a street-like surfel scene), pixel-per-lane with two pixels per lane when they are
-  // large (chunks of the scan kernel would stay half empty and every instance would need four rows: 25 % faster on
-  // the Metric-1 cloud).  `footprint_class` comes from pings_raster_preprocess; PINGS_BLEND_BWD=pixel|scan overrides.
-  bool scan_mode = footprint_class != 2;
-  if (const char* e = getenv("PINGS_BLEND_BWD")) scan_mode = strcmp(e, "pixel") != 0;
 
   {
     pings::prof::Scope ps("live_scan", st);
-    if (I > 0 && scan_mode) {
+    if (I > 0 && plan.bwd_scan) {
       // one row per (instance, quadrant it blended in): inst_qmask has I+1 entries, the last one zero
       hipcub::TransformInputIterator<uint32_t, PopOp, const uint8_t*> cnt(bs.inst_qmask, PopOp());
       size_t tb = bw.temp_bytes;
@@ -1462,42 +1376,34 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
                        bs.tile_work);
     PINGS_LAUNCH_CHECK();
     if (int e = launch_tile_order(bs.tile_work, num_tiles, bs.tile_order + num_tiles, st,
-                                  bs.tile_order + 2 * (size_t)num_tiles, long_list_threshold(), LONG_TILES_MAX))
+                                  bs.tile_order + 2 * (size_t)num_tiles, plan.long_thr, LONG_TILES_MAX))
       return e;
   }
-  if (I > 0 && scan_mode) {
+  if (I > 0) {
     pings::prof::Scope ps("blend_bwd", st);
-    // one workgroup per ordinary tile, four per long tile (their number lives on the device: the grid is sized for
-    // the cap, workgroups past the last tile leave at once)
     const uint32_t* order = bs.tile_order + num_tiles;
-    const uint32_t* n_long = bs.tile_order + 2 * (size_t)num_tiles;
-    const unsigned grid_s = (unsigned)(num_tiles + 3 * std::min<long long>(num_tiles, LONG_TILES_MAX));
-#define PINGS_BWD_SCAN(M)                                                                                             \
-  hipLaunchKernelGGL((blend_bwd_scan_kernel<M>), dim3(grid_s), dim3(256), 0, st, bp, bs.ranges,                       \
-                     bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor, dL_dnormal,     \
-                     dL_ddepth, dL_dalpha, bs.inst_qmask, bw.cidx, bw.rows, order, n_long)
-    if (s->mode == PINGS_RASTER_SURFEL) PINGS_BWD_SCAN(MODE_SURFEL);
-    else PINGS_BWD_SCAN(MODE_3DGS);
-#undef PINGS_BWD_SCAN
-    PINGS_LAUNCH_CHECK();
-  } else if (I > 0) {
-    pings::prof::Scope ps("blend_bwd", st);
-    int ppl = footprint_class == 2 ? 4 : 1;   // class 2: one wave per tile, four pixels per lane (0.40 -> 0.35 ms on Metric-1 vs two)
-    if (const char* e = getenv("PINGS_BLEND_BWD_PPL")) ppl = atoi(e);
-#define PINGS_BLEND_BWD(M, L)                                                                            \
-  hipLaunchKernelGGL((blend_bwd_kernel<M, L>), dim3(num_tiles), dim3(BLOCK / L), 0, st, bp, bs.ranges,    \
-                     bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor,     \
-                     dL_dnormal, dL_ddepth, dL_dalpha, bs.inst_w, bw.cidx, bw.rows, bs.tile_order + num_tiles)
-    if (s->mode == PINGS_RASTER_SURFEL) {
-      if (ppl == 1) PINGS_BLEND_BWD(MODE_SURFEL, 1);
-      else if (ppl == 4) PINGS_BLEND_BWD(MODE_SURFEL, 4);
-      else PINGS_BLEND_BWD(MODE_SURFEL, 2);
-    } else {
-      if (ppl == 1) PINGS_BLEND_BWD(MODE_3DGS, 1);
-      else if (ppl == 4) PINGS_BLEND_BWD(MODE_3DGS, 4);
-      else PINGS_BLEND_BWD(MODE_3DGS, 2);
-    }
-#undef PINGS_BLEND_BWD
+    with_mode(s->mode, [&](auto m) {
+      constexpr int M = m();
+      if (plan.bwd_scan) {
+        // one workgroup per ordinary tile, four per long tile (their number lives on the device: the grid is sized
+        // for the cap, workgroups past the last tile leave at once)
+        const uint32_t* n_long = bs.tile_order + 2 * (size_t)num_tiles;
+        const unsigned grid_s = (unsigned)(num_tiles + 3 * std::min<long long>(num_tiles, LONG_TILES_MAX));
+        hipLaunchKernelGGL((blend_bwd_scan_kernel<M>), dim3(grid_s), dim3(256), 0, st, bp, bs.ranges,
+                           bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor, dL_dnormal,
+                           dL_ddepth, dL_dalpha, bs.inst_qmask, bw.cidx, bw.rows, order, n_long);
+      } else {
+        auto pixel = [&](auto ppl) {
+          constexpr int L = ppl();
+          hipLaunchKernelGGL((blend_bwd_kernel<M, L>), dim3(num_tiles), dim3(BLOCK / L), 0, st, bp, bs.ranges,
+                             bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor,
+                             dL_dnormal, dL_ddepth, dL_dalpha, bs.inst_w, bw.cidx, bw.rows, order);
+        };
+        if (plan.bwd_ppl == 1) pixel(std::integral_constant<int, 1>{});
+        else if (plan.bwd_ppl == 4) pixel(std::integral_constant<int, 4>{});
+        else pixel(std::integral_constant<int, 2>{});
+      }
+    });
     PINGS_LAUNCH_CHECK();
   }
   {
@@ -1511,16 +1417,12 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
   const int nblocks = pings::ceil_div(P, 256);
   {
     pings::prof::Scope ps_g("gaussian_bwd", st);
-    if (s->mode == PINGS_RASTER_SURFEL)
-      hipLaunchKernelGGL(gaussian_bwd_kernel<MODE_SURFEL>, dim3(nblocks), block, 0, st, bp, means3D,
+    with_mode(s->mode, [&](auto m) {
+      hipLaunchKernelGGL(gaussian_bwd_kernel<m()>, dim3(nblocks), block, 0, st, bp, means3D,
                          scales, rotations, gs.rect, gs.rank_of, gs.tiles_sorted, bw.pair_off, bw.partials,
                          dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
                          dL_drotations, bw.tau_partials);
-    else
-      hipLaunchKernelGGL(gaussian_bwd_kernel<MODE_3DGS>, dim3(nblocks), block, 0, st, bp, means3D,
-                         scales, rotations, gs.rect, gs.rank_of, gs.tiles_sorted, bw.pair_off, bw.partials,
-                         dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
-                         dL_drotations, bw.tau_partials);
+    });
     PINGS_LAUNCH_CHECK();
     hipLaunchKernelGGL(tau_reduce_kernel, dim3(1), block, 0, st, bw.tau_partials, nblocks, dL_dtau);
     PINGS_LAUNCH_CHECK();

@@ -16,6 +16,7 @@
 // 64-bit (tile<<32 | depth) key sort gives, at a quarter of the sort traffic.
 #pragma once
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.hpp"
 
@@ -51,6 +52,7 @@ constexpr int RECT_TIGHT = 0, RECT_3SIGMA = 1, RECT_ELLIPSE = 2;
 // (one 64-B row per (tile, Gaussian) instance, summed per Gaussian afterwards).
 // G_CONX/Y/Z hold dL/d(cov2D xx, xy, yy) — NOT the gradient w.r.t. the conic (see blend_bwd_kernel).
 constexpr int GRAD_ROW = 16;
+constexpr int CH = 64;  // rows per first-level chunk of the per-Gaussian sum
 enum GradSlot {
   G_MX = 0, G_MY = 1, G_CONX = 2, G_CONY = 3, G_CONZ = 4, G_OPAC = 5,
   G_R = 6, G_G = 7, G_B = 8, G_NX = 9, G_NY = 10, G_NZ = 11, G_Q = 12, G_PZ = 13,
@@ -114,7 +116,7 @@ struct BinState {
   uint32_t* tile_order;  // [2][num_tiles] tiles by descending work: [0] by list length (forward), [1] by the largest
                          // per-pixel contributor count (backward) — longest-processing-time-first dispatch order
   uint32_t* tile_work;   // [num_tiles] scratch of the two orderings
-  // segmented blend of long tile lists (raster_fwd.hip, "forward of LONG tile lists")
+  // segmented blend of long tile lists (raster_blend_fwd.hip, "forward of LONG tile lists")
   uint32_t seg_max_units;      // capacity: every list of more than 2 * SEG entries cut into SEG-entry units
   uint32_t *seg_head, *seg_unit_tile, *seg_unit_seg, *seg_tile_unit0;
   float *seg_P, *seg_slab;
@@ -131,15 +133,132 @@ struct ImageState {
   size_t total;
 };
 
-uint32_t blend_segment_entries();
+// Camera and image parameters of a frame, passed BY VALUE to the kernels: field order and layout are part of every
+// kernel's argument block.  BParams (backward kernels) is KParams (forward kernels) without the binning-only fields;
+// fill_camera fills what they share.
+struct KParams {
+  int P, W, H, gx, gy;
+  int front_only;
+  float occ_amin;    // smallest per-tile alpha bound that is worth an occlusion-budget entry (see preprocess_kernel)
+  int rect_rule;     // RECT_TIGHT (default) | RECT_3SIGMA | RECT_ELLIPSE, see preprocess_kernel (PINGS_RASTER_RECT)
+  float fx, fy, limx, limy, scale_mod;
+  const float* view;
+  const float* proj_raw;
+  const float* bg;
+  const float* prcp;
+  const int32_t* live;   // device word: of the first `dyn_rows` Gaussians only rows [0, *live) exist (nullable)
+  int dyn_rows;
+};
+
+struct BParams {
+  int P, W, H, gx, gy;
+  int front_only;
+  float fx, fy, limx, limy, scale_mod;
+  const float* view;
+  const float* proj_raw;
+  const float* bg;
+  const float* prcp;
+};
+
+// Checks the settings and fills the fields KParams and BParams have in common.
+template <typename Params>
+int fill_camera(const pings_raster_settings* s, int P, Params& kp) {
+  PINGS_ARG_CHECK(s != nullptr, "null settings");
+  PINGS_ARG_CHECK(s->image_height > 0 && s->image_width > 0, "empty image");
+  PINGS_ARG_CHECK(s->image_height < 65536 * TILE / 16 && s->image_width < 65536, "image too large");
+  PINGS_ARG_CHECK(s->mode == PINGS_RASTER_SURFEL || s->mode == PINGS_RASTER_3DGS, "unknown mode");
+  PINGS_ARG_CHECK(s->viewmatrix && s->projmatrix_raw && s->bg, "null camera pointer");
+  PINGS_ARG_CHECK(s->tanfovx > 0 && s->tanfovy > 0, "non-positive tanfov");
+  kp.P = P;
+  kp.W = s->image_width;
+  kp.H = s->image_height;
+  kp.gx = ceil_div(kp.W, TILE);
+  kp.gy = ceil_div(kp.H, TILE);
+  kp.front_only = s->front_only;
+  kp.fx = (float)((double)kp.W / (2.0 * s->tanfovx));
+  kp.fy = (float)((double)kp.H / (2.0 * s->tanfovy));
+  kp.limx = (float)(1.3 * s->tanfovx);
+  kp.limy = (float)(1.3 * s->tanfovy);
+  kp.scale_mod = (float)s->scale_modifier;
+  kp.view = s->viewmatrix;
+  kp.proj_raw = s->projmatrix_raw;
+  kp.bg = s->bg;
+  kp.prcp = s->prcppoint;
+  return PINGS_OK;
+}
+
+// f(std::integral_constant<int, MODE_...>{}) for the settings' mode: the one place a run-time mode becomes a kernel
+// template argument (`[&](auto m) { ... kernel<m()> ... }`).
+template <typename F>
+decltype(auto) with_mode(int mode, F&& f) {
+  if (mode == PINGS_RASTER_SURFEL) return f(std::integral_constant<int, MODE_SURFEL>{});
+  return f(std::integral_constant<int, MODE_3DGS>{});
+}
+
+// Every PINGS_* environment knob of the rasteriser, parsed (raster_layout.hip: the table above read_knobs documents
+// each, defaults included).  Read on every call, never cached: tests switch knobs between calls of one process.
+struct RasterKnobs {
+  enum Bwd { BWD_AUTO, BWD_PIXEL, BWD_SCAN };
+  int blend_ppl = 0;             // PINGS_BLEND_PPL
+  Bwd blend_bwd = BWD_AUTO;      // PINGS_BLEND_BWD
+  int blend_bwd_ppl = 0;         // PINGS_BLEND_BWD_PPL: 0 (unset) | 1 | 2 | 4
+  uint32_t blend_seg = 512u;     // PINGS_BLEND_SEG
+  bool seg_reuse = true;         // PINGS_BLEND_SEG_REUSE
+  uint32_t bwd_long = 3072u;     // PINGS_BWD_LONG: the threshold itself (never = 0xFFFFFFF0)
+  bool occlusion = true;         // PINGS_RASTER_OCCLUSION
+  bool library_sort = false;     // PINGS_DEPTH_SORT
+  float occ_amin = 0.15f;        // PINGS_OCC_AMIN
+  int rect_rule = RECT_TIGHT;    // PINGS_RASTER_RECT
+  bool mark_depth_only = false;  // PINGS_MARK_VISIBLE
+};
+RasterKnobs read_knobs();
+
+// Which blend kernels a view runs.  pings_raster_render and pings_raster_backward both derive it from the same
+// arguments and branch on nothing else: the forward writes the exact quadrant masks iff the backward will scan them.
+struct BlendPlan {
+  enum Fwd { FWD_WG1, FWD_WG2, FWD_TILE, FWD_WAVE } fwd;  // workgroup per tile with 1 | 2 pixels per lane, wave per tile, wave per quadrant
+  bool want_qmask;     // forward writes exact quadrant masks
+  bool bwd_scan;       // Gaussian-per-lane backward; else pixel-per-lane
+  int bwd_ppl;         // 1 | 2 | 4, pixel-per-lane backward only
+  uint32_t seg;        // entries per segment of the segmented forward of long tile lists
+  bool seg_on, seg_reuse;
+  uint32_t long_thr;   // four-wave split threshold of the scan backward
+};
+BlendPlan blend_plan(const RasterKnobs& k, int footprint_class, int64_t I, int num_tiles);
+
+struct BwdState {
+  uint32_t* cidx;        // [I+2] exclusive scan of live flags over instance slots (cidx[I] = #live)
+  float* rows;           // [I][16] gradient rows of live instances (upper bound; only #live used)
+  uint32_t *cbeg, *nch, *pair_off, *pair_owner;
+  float* partials;       // [NPmax][16]
+  float* tau_partials;   // [ceil(P/256)][6]
+  char* temp;
+  size_t temp_bytes, np_max, total;
+};
+
 GeomState carve_geom(void* blob, int P, int num_tiles);
 // tile_order[i] = i-th tile in descending `work` (ties in any order: scheduling only, results do not depend on it)
 // n_long (optional): receives min(number of tiles with work >= long_thr, long_max) — they lead the order
 int launch_tile_order(const uint32_t* work, int num_tiles, uint32_t* order, hipStream_t st, uint32_t* n_long = nullptr,
                       uint32_t long_thr = 0, uint32_t long_max = 0);
 int occlusion_buckets(int num_tiles);
-BinState carve_binning(void* blob, int64_t I, int num_tiles);
+// `seg` = RasterKnobs::blend_seg of the call: the capacity of the segment tables depends on it
+BinState carve_binning(void* blob, int64_t I, int num_tiles, uint32_t seg);
 ImageState carve_image(void* blob, int W, int H);
+BwdState carve_bwd(void* blob, int P, int64_t I);
+
+// raster_blend_fwd.hip: the blend half of pings_raster_render — the forward kernels of `plan`, then the per-Gaussian sums
+int launch_blend_fwd(int mode, const KParams& kp, const BlendPlan& plan, int P, int64_t I, const GeomState& gs,
+                     const BinState& bs, const ImageState& im, float* out_color, float* out_normal, float* out_depth,
+                     float* out_alpha, void* per_gaussian, hipStream_t st);
+
+// value of `v` in lane `src`, `src` wave-uniform: v_readlane_b32 (scalar path) instead of the ds_bpermute_b32 a
+// general __shfl compiles to — no LDS round trip, no lgkmcnt wait in the per-rectangle loops below
+__device__ inline int lane_value(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
+__device__ inline uint32_t lane_value(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
+__device__ inline float lane_value(float v, int src) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
+}
 
 // Two fp32 values in one VGPR pair: + - * on f2 compile to v_pk_add_f32 / v_pk_mul_f32, fma2 to v_pk_fma_f32.  Each
 // component is rounded exactly as the scalar instruction rounds it, so a packed multiply or add may stand in for a

@@ -971,7 +971,7 @@ def test_bucket_depth_sort_is_the_library_sort(scene, monkeypatch):
 @pytest.mark.parametrize("mode", ["surfel", "3dgs"])
 def test_long_lists_blended_in_parallel_segments(mode, monkeypatch):
     """Long tile lists are cut into segments blended by separate waves and composed with the over operator
-    (csrc/raster_fwd.hip, blend_fwd_seg_kernel).  Forced here with 64-entry segments on lists of several hundred
+    (csrc/raster_blend_fwd.hip, blend_fwd_seg_kernel).  Forced here with 64-entry segments on lists of several hundred
     entries: images, per-Gaussian outputs and every gradient equal those of the serial walk up to fp32 association
     (1e-5), n_contrib differs on at most a handful of pixels (a stop decision within rounding of T = 1e-4), and both
     match the fp64 oracle."""

@@ -1,4 +1,4 @@
-"""Long tile lists at the thresholds the product uses: the segmented forward (csrc/raster_fwd.hip, seg_plan_kernel,
+"""Long tile lists at the thresholds the product uses: the segmented forward (csrc/raster_blend_fwd.hip, seg_plan_kernel,
 blend_fwd_wave_segT_kernel / blend_fwd_seg_kernel / blend_fwd_seg_combine_kernel) and the four-wave split of long
 tiles in the Gaussian-per-lane backward (csrc/raster_bwd.hip, blend_bwd_scan_kernel), against the fp64 / fp32 oracle
 with no threshold forced.  Every default-threshold test first proves from `debug_lists` that the path it targets ran
@@ -15,10 +15,10 @@ from test_raster import (_assert_grad_gate, _hip_forward, _hip_grads, _last_cont
                          _undecidable)
 
 # ------------------------------------------------------------------ the library's predicates, restated
-SEG_ENTRIES = 512        # raster_fwd.hip blend_segment_entries(): entries per unit (PINGS_BLEND_SEG overrides, 0 = off)
+SEG_ENTRIES = 512        # raster_layout.hip read_knobs(): entries per unit (PINGS_BLEND_SEG overrides, 0 = off)
 SEG_FRAME_DIV = 4        # seg_on: I > num_tiles * (seg / 4) and I > 2 * seg
 SEG_TILE_UNITS = 2       # seg_plan_kernel: a list longer than 2 * seg is cut into ceil(L / seg) units
-BWD_LONG = 3072          # raster_bwd.hip long_list_threshold() (PINGS_BWD_LONG overrides, <= 0 = never), rounded up to 16
+BWD_LONG = 3072          # raster_layout.hip read_knobs() (PINGS_BWD_LONG overrides, <= 0 = never), rounded up to 16
 LONG_TILES_MAX = 2048    # raster_bwd.hip: cap on split tiles, taken in whole bins of tile_order_kernel
 TOP_BIN = 1023           # tile_order_kernel: bin = min(work >> 4, 1023)
 
