@@ -832,13 +832,15 @@ __global__ __launch_bounds__(256) void blend_fwd_seg_combine_kernel(
 // is final — no per-quadrant partials, no 16-byte-per-instance memset, no combine pass.  Pixel arithmetic is the
 // quadrant kernel's, op for op (images bit-identical); the per-instance weight sum adds the same terms in another
 // order.  inst_qmask is NOT produced: only the pixel-per-lane backward (which this class uses) may follow.
+// tile_maxc[tile] = the largest n_contrib of the tile's pixels inside the image, which the wave holds when it stores
+// them: the work estimate of the backward dispatch order (tile_max_contrib_kernel computes it for the other forwards).
 template <int MODE>
 __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
     KParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
     const float4* __restrict__ rec, const uint32_t* __restrict__ gval, float* __restrict__ out_color,
     float* __restrict__ out_normal, float* __restrict__ out_depth, float* __restrict__ out_alpha,
     float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ inst_w,
-    uint32_t* __restrict__ inst_cnt, const uint32_t* __restrict__ tile_order) {
+    uint32_t* __restrict__ inst_cnt, const uint32_t* __restrict__ tile_order, uint32_t* __restrict__ tile_maxc) {
   constexpr int PPL = 4;
   __shared__ float4 sA[64], sB[64], sC[64], sD[64];
   __shared__ uint32_t sSlot[64];
@@ -1078,6 +1080,12 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
       out_depth[pix_id] = D[r][h];
     }
   }
+  uint32_t mc = 0u;
+#pragma unroll
+  for (int k = 0; k < PPL; ++k) mc = max(mc, inside[k] ? last[k] : 0u);
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) mc = max(mc, (uint32_t)__shfl_xor((int)mc, off, 64));
+  if (lane == 0) tile_maxc[tile] = mc;
 }
 
 // inst_w[slot] = sum over the quadrants in fixed order, inst_cnt likewise, inst_qmask = quadrants that blended
@@ -1225,7 +1233,7 @@ int launch_blend_fwd(int mode, const KParams& kp, const BlendPlan& plan, int P, 
         case BlendPlan::FWD_TILE:
           hipLaunchKernelGGL((blend_fwd_tile_kernel<M>), dim3(num_tiles), dim3(64), 0, st, kp, bs.ranges,
                              bs.point_list, gs.rec, bs.gval, o.color, o.normal, o.depth, o.alpha,
-                             im.final_T, im.n_contrib, bs.inst_w, bs.inst_cnt, bs.tile_order);
+                             im.final_T, im.n_contrib, bs.inst_w, bs.inst_cnt, bs.tile_order, bs.tile_maxc);
           break;
         case BlendPlan::FWD_WAVE:
           if (int e = launch_blend_fwd_wave<M>(kp, plan, I, num_tiles, gs, bs, im, o, st)) return e;

@@ -16,7 +16,10 @@
 //   gaussian_bwd_kernel   per Gaussian (in index order, rows located through its depth rank): adds its chunk partials, then chains
 //                         through conic / EWA projection / quaternion / scale / camera transform to
 //                         the input gradients and the pose-tangent terms (block-reduced, fixed order).
-//   tau_reduce_kernel     final fixed-order reduction of the pose-tangent partials.
+//   tau_reduce_kernel     final fixed-order reduction of the pose-tangent partials.  (Run by the last workgroup of
+//                         gaussian_bwd_kernel instead, behind a device-scope fence and a ticket, it saved the launch
+//                         and cost 640 us: the release writes back the L2 of the workgroup's XCD, once per workgroup,
+//                         while the gradient stores of the others keep it dirty.)
 //
 // Gradient definitions are those torch autograd derives from oracle/raster_cpu.py (clamps have
 // zero gradient where active, min(0.99, .) included).
@@ -1014,20 +1017,19 @@ struct LiveOp {
   __host__ __device__ uint32_t operator()(const float& w) const { return w > 0.f ? 1u : 0u; }
 };
 
-// per depth rank: compact row range of the Gaussian and its number of <= CH-row chunks
-__global__ __launch_bounds__(256) void row_ranges_kernel(int P, const uint32_t* __restrict__ offsets_sorted,
-                                                          const uint32_t* __restrict__ tiles_sorted,
-                                                          const uint32_t* __restrict__ cidx,
-                                                          uint32_t* __restrict__ cbeg,
-                                                          uint32_t* __restrict__ nch) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r > P) return;
-  if (r == P) { nch[P] = 0u; return; }
-  const uint32_t se = offsets_sorted[r], sb = se - tiles_sorted[r];
-  const uint32_t cb = cidx[sb], ce = cidx[se];
-  cbeg[r] = cb;
-  nch[r] = (ce - cb + (uint32_t)CH - 1u) / (uint32_t)CH;
-}
+// per depth rank r: the Gaussian's rows are the compact range [cidx[first slot], cidx[end slot]); its number of
+// <= CH-row chunks is the input of the pair_off scan, computed as the scan reads it (entry P = 0) instead of by a
+// pass of its own through an array
+struct RowRanges {
+  int P;
+  const uint32_t *offsets_sorted, *tiles_sorted, *cidx;
+  __host__ __device__ uint32_t row_begin(uint32_t r) const { return cidx[offsets_sorted[r] - tiles_sorted[r]]; }
+  __host__ __device__ uint32_t row_end(uint32_t r) const { return cidx[offsets_sorted[r]]; }
+  __host__ __device__ uint32_t operator()(const uint32_t& r) const {
+    if (r >= (uint32_t)P) return 0u;
+    return (row_end(r) - row_begin(r) + (uint32_t)CH - 1u) / (uint32_t)CH;
+  }
+};
 
 __global__ __launch_bounds__(256) void pair_owner_kernel(int P, const uint32_t* __restrict__ pair_off,
                                                           uint32_t* __restrict__ pair_owner) {
@@ -1038,20 +1040,17 @@ __global__ __launch_bounds__(256) void pair_owner_kernel(int P, const uint32_t* 
 }
 
 // one 16-lane group per (Gaussian, chunk) pair; lane = column of the 16-float row
-__global__ __launch_bounds__(256) void row_chunk_sum_kernel(int P, const uint32_t* __restrict__ pair_off,
+__global__ __launch_bounds__(256) void row_chunk_sum_kernel(RowRanges rr, const uint32_t* __restrict__ pair_off,
                                                              const uint32_t* __restrict__ pair_owner,
-                                                             const uint32_t* __restrict__ cbeg,
-                                                             const uint32_t* __restrict__ offsets_sorted,
-                                                             const uint32_t* __restrict__ cidx,
                                                              const float* __restrict__ rows,
                                                              float* __restrict__ partials) {
   const uint32_t q = (uint32_t)((blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 4);
   const int c = threadIdx.x & 15;
-  if (q >= pair_off[P]) return;
+  if (q >= pair_off[rr.P]) return;
   const uint32_t r = pair_owner[q];
   const uint32_t j = q - pair_off[r];
-  const uint32_t row_end = cidx[offsets_sorted[r]];
-  uint32_t row = cbeg[r] + j * (uint32_t)CH;
+  const uint32_t row_end = rr.row_end(r);
+  uint32_t row = rr.row_begin(r) + j * (uint32_t)CH;
   const uint32_t stop = min(row + (uint32_t)CH, row_end);
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
   for (; row + 4 <= stop; row += 4) {
@@ -1343,6 +1342,7 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
   ImageState im = carve_image(const_cast<void*>(image_blob), bp.W, bp.H);
   BwdState bw = carve_bwd(bwd_blob, P, I);
   const dim3 gridP(pings::ceil_div(P + 1, 256)), block(256);
+  const RowRanges rr{P, gs.offsets_sorted, gs.tiles_sorted, bw.cidx};
 
   {
     pings::prof::Scope ps("live_scan", st);
@@ -1359,11 +1359,10 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
     } else {
       PINGS_HIP_CHECK(hipMemsetAsync(bw.cidx, 0, 2 * sizeof(uint32_t), st));
     }
-    hipLaunchKernelGGL(row_ranges_kernel, gridP, block, 0, st, P, gs.offsets_sorted, gs.tiles_sorted,
-                       bw.cidx, bw.cbeg, bw.nch);
-    PINGS_LAUNCH_CHECK();
+    hipcub::TransformInputIterator<uint32_t, RowRanges, hipcub::CountingInputIterator<uint32_t>> nch(
+        hipcub::CountingInputIterator<uint32_t>(0u), rr);
     size_t tb = bw.temp_bytes;
-    PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(bw.temp, tb, bw.nch, bw.pair_off, P + 1, st));
+    PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(bw.temp, tb, nch, bw.pair_off, P + 1, st));
     hipLaunchKernelGGL(pair_owner_kernel, gridP, block, 0, st, P, bw.pair_off, bw.pair_owner);
     PINGS_LAUNCH_CHECK();
   }
@@ -1372,10 +1371,13 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
     // (On a side stream next to the row scans above — two chains of small launches that share nothing — the step came
     // out 0.008 - 0.025 ms SLOWER on Metric-1 / C2: the fork and join cost more than the 16 us they could hide.)
     pings::prof::Scope ps("tile_order", st);
-    hipLaunchKernelGGL(tile_max_contrib_kernel, dim3(num_tiles), dim3(64), 0, st, bp.W, bp.H, bp.gx, im.n_contrib,
-                       bs.tile_work);
-    PINGS_LAUNCH_CHECK();
-    if (int e = launch_tile_order(bs.tile_work, num_tiles, bs.tile_order + num_tiles, st,
+    const bool fwd_left_it = plan.fwd == BlendPlan::FWD_TILE;   // blend_fwd_tile_kernel's epilogue: the same numbers
+    if (!fwd_left_it) {
+      hipLaunchKernelGGL(tile_max_contrib_kernel, dim3(num_tiles), dim3(64), 0, st, bp.W, bp.H, bp.gx, im.n_contrib,
+                         bs.tile_work);
+      PINGS_LAUNCH_CHECK();
+    }
+    if (int e = launch_tile_order(fwd_left_it ? bs.tile_maxc : bs.tile_work, num_tiles, bs.tile_order + num_tiles, st,
                                   bs.tile_order + 2 * (size_t)num_tiles, plan.long_thr, LONG_TILES_MAX))
       return e;
   }
@@ -1410,8 +1412,7 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
     pings::prof::Scope ps("row_chunk_sum", st);
     const size_t groups = bw.np_max;
     hipLaunchKernelGGL(row_chunk_sum_kernel, dim3((unsigned)pings::ceil_div<size_t>(groups * 16, 256)),
-                       block, 0, st, P, bw.pair_off, bw.pair_owner, bw.cbeg, gs.offsets_sorted, bw.cidx,
-                       bw.rows, bw.partials);
+                       block, 0, st, rr, bw.pair_off, bw.pair_owner, bw.rows, bw.partials);
     PINGS_LAUNCH_CHECK();
   }
   const int nblocks = pings::ceil_div(P, 256);

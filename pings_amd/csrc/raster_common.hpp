@@ -74,8 +74,8 @@ struct Carver {
 };
 
 struct FrameSummary {   // the record of a frame's one host read-back (frame_summary_kernel)
-  uint32_t total, overflow;
-  unsigned long long stats[3];
+  uint32_t overflow, pad0;
+  unsigned long long stats[3];   // pairs before occlusion culling, visible Gaussians, kept pairs (= instances)
   int32_t aux[8];
   uint32_t seq;   // written last (system-scope release): the host polls it instead of blocking in the runtime
   uint32_t pad;
@@ -115,7 +115,8 @@ struct BinState {
   uint32_t* inst_cnt;  // [I]   per-instance pixel count with transmittance > 0.5 (3DGS)
   uint32_t* tile_order;  // [2][num_tiles] tiles by descending work: [0] by list length (forward), [1] by the largest
                          // per-pixel contributor count (backward) — longest-processing-time-first dispatch order
-  uint32_t* tile_work;   // [num_tiles] scratch of the two orderings
+  uint32_t* tile_work;   // [num_tiles] work of the backward ordering: a tile's largest per-pixel contributor count,
+  uint32_t* tile_maxc;   //             from tile_max_contrib_kernel | left by blend_fwd_tile_kernel (BlendPlan::FWD_TILE)
   // segmented blend of long tile lists (raster_blend_fwd.hip, "forward of LONG tile lists")
   uint32_t seg_max_units;      // capacity: every list of more than 2 * SEG entries cut into SEG-entry units
   uint32_t *seg_head, *seg_unit_tile, *seg_unit_seg, *seg_tile_unit0;
@@ -229,7 +230,7 @@ BlendPlan blend_plan(const RasterKnobs& k, int footprint_class, int64_t I, int n
 struct BwdState {
   uint32_t* cidx;        // [I+2] exclusive scan of live flags over instance slots (cidx[I] = #live)
   float* rows;           // [I][16] gradient rows of live instances (upper bound; only #live used)
-  uint32_t *cbeg, *nch, *pair_off, *pair_owner;
+  uint32_t *pair_off, *pair_owner;   // [P+1] exclusive scan of the Gaussians' chunk counts (by depth rank), [NPmax] owner rank of a chunk
   float* partials;       // [NPmax][16]
   float* tau_partials;   // [ceil(P/256)][6]
   char* temp;

@@ -50,14 +50,13 @@ __global__ __launch_bounds__(256) void mark_visible_kernel(const float* __restri
   present[i] = (pz > NEAR_Z) && (depth_only || ((nx >= -1.3f) && (nx <= 1.3f) && (ny >= -1.3f) && (ny <= 1.3f)));
 }
 
+// One Gaussian of preprocess_kernel; returns its depth key (CULLED_KEY if it was culled).
 template <int MODE>
-__global__ __launch_bounds__(256) void preprocess_kernel(
-    KParams p, const float* __restrict__ means3D, const float* __restrict__ colors,
+__device__ inline uint32_t preprocess_gaussian(
+    const KParams& p, int g, const float* __restrict__ means3D, const float* __restrict__ colors,
     const float* __restrict__ opacities, const float* __restrict__ scales,
     const float* __restrict__ rotations, float4* __restrict__ rec, uint4* __restrict__ rect,
     uint32_t* __restrict__ depth_key, uint32_t* __restrict__ gidx, int32_t* __restrict__ radii) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= p.P) return;
   const float* V = p.view;
   const float* Pm = p.proj_raw;
 
@@ -233,6 +232,42 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
     rec[4 * g + 2] = make_float4(colors[3 * g], colors[3 * g + 1], colors[3 * g + 2], q);
     rec[4 * g + 3] = make_float4(nx, ny, nz, 0.0f);
   }
+  return key;
+}
+
+// `ds_head` (bucket depth sort only, else null): the key range of the survivors, as the largest key and the largest
+// ~key of every workgroup, each into one of DS_SHARDS words — the keys are in registers here; a pass of its own would
+// read them back from HBM.  The header must have been cleared before this launch.
+template <int MODE>
+__global__ __launch_bounds__(256) void preprocess_kernel(
+    KParams p, const float* __restrict__ means3D, const float* __restrict__ colors,
+    const float* __restrict__ opacities, const float* __restrict__ scales,
+    const float* __restrict__ rotations, float4* __restrict__ rec, uint4* __restrict__ rect,
+    uint32_t* __restrict__ depth_key, uint32_t* __restrict__ gidx, int32_t* __restrict__ radii,
+    uint32_t* __restrict__ ds_head) {
+  __shared__ uint32_t sm[8];
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t key = CULLED_KEY;
+  if (g < p.P)
+    key = preprocess_gaussian<MODE>(p, g, means3D, colors, opacities, scales, rotations, rec, rect, depth_key, gidx, radii);
+  if (!ds_head) return;
+  uint32_t mx = key != CULLED_KEY ? key : 0u, mn = key != CULLED_KEY ? ~key : 0u;  // max key, max ~key over valid entries
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
+    mn = max(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) { sm[wave] = mx; sm[4 + wave] = mn; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    mx = max(max(sm[0], sm[1]), max(sm[2], sm[3]));
+    mn = max(max(sm[4], sm[5]), max(sm[6], sm[7]));
+    if (mx | mn) {
+      atomicMax(&ds_head[blockIdx.x % DS_SHARDS], mx);
+      atomicMax(&ds_head[DS_SHARDS + blockIdx.x % DS_SHARDS], mn);
+    }
+  }
 }
 
 // Depth ranks -> lanes.  The nearest Gaussians cover the most tiles and sit at neighbouring ranks: dealt out in rank
@@ -353,48 +388,30 @@ __device__ inline float tile_min_alpha(float mx, float my, float o, float cx, fl
 // sort redoes the frame.
 struct DsRange { uint32_t kmin, shift; };
 
+// what ds_hist_kernel published (ds_scatter_kernel, ds_rank_kernel)
 __device__ inline DsRange ds_range(const uint32_t* __restrict__ head) { return DsRange{head[DS_KMIN], head[DS_SHIFT]}; }
 
-__global__ __launch_bounds__(256) void ds_minmax_kernel(int P, const uint32_t* __restrict__ key, uint32_t* __restrict__ head) {
-  __shared__ uint32_t sm[8];
-  uint32_t mx = 0u, mn = 0u;  // max key, max ~key over valid entries
-  for (int g = blockIdx.x * 256 + threadIdx.x; g < P; g += gridDim.x * 256) {
-    const uint32_t k = key[g];
-    if (k != CULLED_KEY) { mx = max(mx, k); mn = max(mn, ~k); }
-  }
+// The range from preprocess_kernel's shards: every workgroup of ds_hist_kernel folds the 2 x DS_SHARDS words itself
+// (L2-resident; a one-wave kernel in between cost a launch) — its first wave, the others get the result through LDS.
+__device__ inline DsRange ds_range_from_shards(const uint32_t* __restrict__ head, uint32_t (&sr)[2]) {
+  if (threadIdx.x < 64) {
+    uint32_t mx = head[threadIdx.x], mn = head[DS_SHARDS + threadIdx.x];
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
-    mn = max(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
-  }
-  const int wave = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) { sm[wave] = mx; sm[4 + wave] = mn; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    mx = max(max(sm[0], sm[1]), max(sm[2], sm[3]));
-    mn = max(max(sm[4], sm[5]), max(sm[6], sm[7]));
-    if (mx | mn) {
-      atomicMax(&head[blockIdx.x % DS_SHARDS], mx);
-      atomicMax(&head[DS_SHARDS + blockIdx.x % DS_SHARDS], mn);
+    for (int o = 32; o > 0; o >>= 1) {
+      mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
+      mn = max(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
+    }
+    if (threadIdx.x == 0) {
+      const uint32_t kmin = ~mn;
+      uint32_t shift = 0u;
+      if (mx > kmin)
+        while (((mx - kmin) >> shift) >= (uint32_t)DS_NB) ++shift;
+      sr[0] = kmin;
+      sr[1] = shift;
     }
   }
-}
-
-__global__ __launch_bounds__(64) void ds_range_kernel(uint32_t* __restrict__ head) {
-  uint32_t mx = head[threadIdx.x], mn = head[DS_SHARDS + threadIdx.x];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    mx = max(mx, (uint32_t)__shfl_xor((int)mx, o, 64));
-    mn = max(mn, (uint32_t)__shfl_xor((int)mn, o, 64));
-  }
-  if (threadIdx.x == 0) {
-    const uint32_t kmin = ~mn;
-    uint32_t shift = 0u;
-    if (mx > kmin)
-      while (((mx - kmin) >> shift) >= (uint32_t)DS_NB) ++shift;
-    head[DS_KMIN] = kmin;
-    head[DS_SHIFT] = shift;
-  }
+  __syncthreads();
+  return DsRange{sr[0], sr[1]};
 }
 
 // bucket histogram of the survivors; culled Gaussians are counted per workgroup (cnt[DS_NB + block]) so that the one
@@ -404,15 +421,18 @@ __global__ __launch_bounds__(64) void ds_range_kernel(uint32_t* __restrict__ hea
 // bucket, all in flight together, and every lane derives its arrival slot inside the bucket (`pos`) from the leader's
 // return value.  A wall of surfels at one depth — a quarter of a million Gaussians in one bucket — would otherwise
 // serialise on one address (~12 ns per atomic: 3 ms); the scatter pass needs no atomics at all.
-__global__ __launch_bounds__(256) void ds_hist_kernel(int P, const uint32_t* __restrict__ key, const uint32_t* __restrict__ head,
+// Workgroup 0 also publishes the key range (head[DS_KMIN], head[DS_SHIFT]) for the two passes that follow.
+__global__ __launch_bounds__(256) void ds_hist_kernel(int P, const uint32_t* __restrict__ key, uint32_t* __restrict__ head,
                                                        uint32_t* __restrict__ cnt, uint32_t* __restrict__ pos) {
   __shared__ uint32_t sc[4];
+  __shared__ uint32_t sr[2];
   const int g = blockIdx.x * 256 + threadIdx.x;
   const int lane = threadIdx.x & 63;
   const uint32_t k = g < P ? key[g] : 0u;
   const bool culled = g < P && k == CULLED_KEY;
   const bool active = g < P && !culled;
-  const DsRange r = ds_range(head);
+  const DsRange r = ds_range_from_shards(head, sr);
+  if (blockIdx.x == 0 && threadIdx.x == 0) { head[DS_KMIN] = r.kmin; head[DS_SHIFT] = r.shift; }
   const uint32_t b = active ? (k - r.kmin) >> r.shift : 0xFFFFFFFFu;
   unsigned long long todo = __ballot(active);
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -714,16 +734,23 @@ __global__ __launch_bounds__(256) void duplicate_kernel(int P, int gx, int nb,
 // A tile's blend time is proportional to its list; the lists are very uneven (Metric-1: 0..374 blended records,
 // mean 127), and workgroups are dispatched in grid order: with tiles in image order the long ones that start late
 // run on an otherwise idle chip.  Dispatching tiles in descending work order fills the tail with short ones.
-// One workgroup: counting sort of the tiles by min(work / 16, 1023), descending.
-__global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* __restrict__ work, int num_tiles,
+// One workgroup: counting sort of the tiles by min(work / 16, 1023), descending.  FROM_RANGES: a tile's work is the
+// length of its list, taken from `ranges` directly (forward order) instead of from a `work` array.
+template <bool FROM_RANGES>
+__global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* __restrict__ work_in,
+                                                          const uint2* __restrict__ ranges, int num_tiles,
                                                           uint32_t* __restrict__ order, uint32_t* __restrict__ n_long,
                                                           uint32_t long_thr, uint32_t long_max) {
   __shared__ uint32_t hist[1024];
   __shared__ uint32_t base[1024];
   const int tid = threadIdx.x;
+  auto work = [&](int t) -> uint32_t {
+    if constexpr (FROM_RANGES) { const uint2 r = ranges[t]; return r.y - r.x; }
+    else return work_in[t];
+  };
   hist[tid] = 0u;
   __syncthreads();
-  for (int t = tid; t < num_tiles; t += 1024) atomicAdd(&hist[min(work[t] >> 4, 1023u)], 1u);
+  for (int t = tid; t < num_tiles; t += 1024) atomicAdd(&hist[min(work(t) >> 4, 1023u)], 1u);
   __syncthreads();
   // exclusive scan over the bins in DESCENDING bin order (bin 1023 first); 1024 threads, one bin each
   uint32_t v = hist[1023 - tid];
@@ -739,7 +766,7 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* __rest
   __syncthreads();
   hist[1023 - tid] = excl;   // hist[bin] = first output position of the bin
   __syncthreads();
-  for (int t = tid; t < num_tiles; t += 1024) order[atomicAdd(&hist[min(work[t] >> 4, 1023u)], 1u)] = (uint32_t)t;
+  for (int t = tid; t < num_tiles; t += 1024) order[atomicAdd(&hist[min(work(t) >> 4, 1023u)], 1u)] = (uint32_t)t;
   // tiles with work >= long_thr (a multiple of 16: whole bins) are the first entries of the order: their number.
   // The order WITHIN a bin is the arrival order of the LDS atomics above, so a cap that cut through a bin would make
   // the set of tiles the backward splits depend on timing.  The cap therefore takes whole bins only: the longest
@@ -759,15 +786,10 @@ __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* __rest
   }
 }
 
-__global__ __launch_bounds__(256) void range_len_kernel(const uint2* __restrict__ ranges, int num_tiles,
-                                                        uint32_t* __restrict__ work) {
-  const int t = blockIdx.x * 256 + threadIdx.x;
-  if (t < num_tiles) work[t] = ranges[t].y - ranges[t].x;
-}
-
 int launch_tile_order(const uint32_t* work, int num_tiles, uint32_t* order, hipStream_t st, uint32_t* n_long,
                       uint32_t long_thr, uint32_t long_max) {
-  hipLaunchKernelGGL(tile_order_kernel, dim3(1), dim3(1024), 0, st, work, num_tiles, order, n_long, long_thr, long_max);
+  hipLaunchKernelGGL(tile_order_kernel<false>, dim3(1), dim3(1024), 0, st, work, (const uint2*)nullptr, num_tiles, order,
+                     n_long, long_thr, long_max);
   PINGS_LAUNCH_CHECK();
   return PINGS_OK;
 }
@@ -782,14 +804,13 @@ __global__ __launch_bounds__(256) void tile_ranges_kernel(int64_t I, const KeyT*
   if (i == I - 1 || key[i + 1] != t) ranges[t].y = (uint32_t)(i + 1);
 }
 
-// One wave folds everything the host reads at the frame's one synchronisation into a 64-byte record: instance total,
-// depth-sort overflow flag, the three sharded statistics and up to 8 caller words (counts other kernels of the frame
+// One wave folds everything the host reads at the frame's one synchronisation into a 64-byte record: depth-sort
+// overflow flag, the three sharded statistics and up to 8 caller words (counts other kernels of the frame
 // left on the device: pings_raster_preprocess_dyn).
 struct AuxPtrs {
   const int32_t* p[8];
 };
-__global__ __launch_bounds__(64) void frame_summary_kernel(const uint32_t* __restrict__ last_offset,
-                                                           const uint32_t* __restrict__ overflow,
+__global__ __launch_bounds__(64) void frame_summary_kernel(const uint32_t* __restrict__ overflow,
                                                            const unsigned long long* __restrict__ shards, AuxPtrs aux,
                                                            int aux_words, FrameSummary* __restrict__ out, uint32_t seq) {
   __shared__ unsigned long long part[3][64];
@@ -805,7 +826,6 @@ __global__ __launch_bounds__(64) void frame_summary_kernel(const uint32_t* __res
     for (int i = 0; i < 64; ++i) t += part[lane][i];
     out->stats[lane] = t;
   }
-  if (lane == 3) out->total = *last_offset;
   if (lane == 4) out->overflow = overflow ? *overflow : 0u;
   if (lane >= 8 && lane < 16) out->aux[lane - 8] = (lane - 8 < aux_words && aux.p[lane - 8]) ? *aux.p[lane - 8] : 0;
   // `out` is pinned HOST memory: every field first, then the sequence number with system-scope release semantics
@@ -881,16 +901,21 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
   const int num_tiles = kp.gx * kp.gy;
   GeomState gs = carve_geom(geom_blob, P, num_tiles);
   const dim3 grid(pings::ceil_div(P, 256)), block(256);
+  const bool occlusion = knobs.occlusion;
+  bool library_sort = knobs.library_sort;   // also the retry path of a depth-bucket overflow
+  // the occlusion budget, the frame statistics and the depth-sort header in one clear (adjacent in the blob), ahead of
+  // the preprocess pass, which leaves the key range in the header; a retry (depth-bucket overflow) clears again what it
+  // reuses
+  PINGS_HIP_CHECK(hipMemsetAsync(gs.zero_begin, 0, gs.zero_bytes, st));
   {
     pings::prof::Scope ps("preprocess", st);
     with_mode(s->mode, [&](auto m) {
       hipLaunchKernelGGL(preprocess_kernel<m()>, grid, block, 0, st, kp, means3D, colors,
-                         opacities, scales, rotations, gs.rec, gs.rect, gs.depth_key, gs.gidx, radii);
+                         opacities, scales, rotations, gs.rec, gs.rect, gs.depth_key, gs.gidx, radii,
+                         library_sort ? (uint32_t*)nullptr : gs.ds_head);
     });
     PINGS_LAUNCH_CHECK();
   }
-  const bool occlusion = knobs.occlusion;
-  bool library_sort = knobs.library_sort;   // also the retry path of a depth-bucket overflow
   // The record of the frame's one read-back is written by the summary kernel straight into pinned, device-mapped host
   // memory and the host POLLS its sequence number: no copy, and no blocking wait inside the runtime.  (Three pageable
   // copies, each a wait of its own, in round 2.  A blocking hipStreamSynchronize wakes through an interrupt; on one box
@@ -906,10 +931,6 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
   }
   AuxPtrs aux;
   for (int i = 0; i < 8; ++i) aux.p[i] = i < aux_words ? aux_dev[i] : nullptr;
-  uint32_t total = 0;
-  // the occlusion budget, the frame statistics and the depth-sort header in one clear (adjacent in the blob); a retry
-  // (depth-bucket overflow) clears again what it reuses
-  PINGS_HIP_CHECK(hipMemsetAsync(gs.zero_begin, 0, gs.zero_bytes, st));
   for (int attempt = 0;; ++attempt) {
     size_t tb = gs.temp_bytes;
     if (library_sort) {
@@ -921,13 +942,8 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
       hipLaunchKernelGGL(invert_perm_kernel, grid, block, 0, st, P, gs.gidx_sorted, gs.rank_of);
       PINGS_LAUNCH_CHECK();
     } else {
+      // first attempt only (a retry is the library sort): the header holds what preprocess_kernel left in it
       pings::prof::Scope ps("depth_sort", st);
-      if (attempt > 0) PINGS_HIP_CHECK(hipMemsetAsync(gs.ds_head, 0, sizeof(uint32_t) * gs.ds_words, st));
-      hipLaunchKernelGGL(ds_minmax_kernel, dim3(std::min(pings::ceil_div(P, 256), 512)), block, 0, st, P,
-                         gs.depth_key, gs.ds_head);
-      PINGS_LAUNCH_CHECK();
-      hipLaunchKernelGGL(ds_range_kernel, dim3(1), dim3(64), 0, st, gs.ds_head);
-      PINGS_LAUNCH_CHECK();
       // arrival slots of the survivors live in rank_of until ds_rank_kernel overwrites it with the final ranks
       hipLaunchKernelGGL(ds_hist_kernel, grid, block, 0, st, P, gs.depth_key, gs.ds_head, gs.ds_cnt, gs.rank_of);
       PINGS_LAUNCH_CHECK();
@@ -967,15 +983,21 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
       hipLaunchKernelGGL(count_kept_kernel, grid, block, 0, st, P, kp.gx, gs.occ_nb, gs.gidx_sorted, gs.rect,
                          gs.occ_bsat, gs.nvalid, gs.tiles_sorted, gs.stats);
       PINGS_LAUNCH_CHECK();
+    }
+    // The summary needs nothing of the instance scan (the kept total is one of count_kept_kernel's 64-bit statistics),
+    // so it goes first and the scan runs while the host wakes up, sizes the binning blob and issues the render.  After
+    // a depth-bucket overflow the frame is redone and this scan was for nothing.
+    const uint32_t seq = ++frame_seq ? frame_seq : ++frame_seq;   // never 0
+    hipLaunchKernelGGL(frame_summary_kernel, dim3(1), dim3(64), 0, st,
+                       library_sort ? (const uint32_t*)nullptr : gs.ds_head + DS_FLAG, gs.stats, aux, aux_words,
+                       host_sum_dev, seq);
+    PINGS_LAUNCH_CHECK();
+    {
+      pings::prof::Scope ps("tile_count_scan", st);
       tb = gs.temp_bytes;
       PINGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(gs.temp, tb, gs.tiles_sorted, gs.offsets_sorted,
                                                        P, st));
     }
-    const uint32_t seq = ++frame_seq ? frame_seq : ++frame_seq;   // never 0
-    hipLaunchKernelGGL(frame_summary_kernel, dim3(1), dim3(64), 0, st, gs.offsets_sorted + (P - 1),
-                       library_sort ? (const uint32_t*)nullptr : gs.ds_head + DS_FLAG, gs.stats, aux, aux_words,
-                       host_sum_dev, seq);
-    PINGS_LAUNCH_CHECK();
     {
       const auto t_start = std::chrono::steady_clock::now();
       unsigned spins = 0;
@@ -993,15 +1015,15 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
         __builtin_ia32_pause();
       }
     }
-    total = host_sum->total;
     if (host_sum->overflow == 0) break;
     library_sort = true;  // a depth bucket overflowed: redo the frame with the library sort
   }
-  *num_instances = (int64_t)total;
   const unsigned long long stats[3] = {host_sum->stats[0], host_sum->stats[1], host_sum->stats[2]};
   for (int i = 0; i < aux_words; ++i) aux_host[i] = host_sum->aux[i];
-  PINGS_ARG_CHECK(stats[2] == (unsigned long long)total && stats[2] < 0x7FFFFFFFull,
-                  "more than 2^31 - 1 (Gaussian, tile) instances in this frame");
+  // stats[2] is the 64-bit sum of the per-rank counts the 32-bit scan runs over: below 2^31 the scan cannot have
+  // wrapped, and its last entry is this number
+  PINGS_ARG_CHECK(stats[2] < 0x7FFFFFFFull, "more than 2^31 - 1 (Gaussian, tile) instances in this frame");
+  *num_instances = (int64_t)stats[2];
   // Footprints of many tiles keep most lanes of a wave busy: two pixels per lane then amortise the per-record
   // work; small footprints leave lanes idle and one pixel per lane (four 8x8 waves with their own culled lists)
   // wins (measured: 52 tiles per Gaussian -> PPL 2 is 6 % faster, 5.6 tiles per Gaussian -> PPL 1 is 19 % faster).
@@ -1028,12 +1050,13 @@ PINGS_API int pings_raster_render(const pings_raster_settings* s, int P, int64_t
   ImageState im = carve_image(image_blob, kp.W, kp.H);
 
   {
-    // tile ranges, per-instance weights and quadrant masks (3DGS: contributor counts too) in one clear
+    // tile ranges, per-instance weights and quadrant masks (3DGS: contributor counts too) in one clear, up to the
+    // 256-byte boundary at which the next field starts (one fill launch; an odd size costs a second one for the tail)
     const char* z0 = reinterpret_cast<const char*>(bs.ranges);
     const char* z1 = I > 0 ? (s->mode == PINGS_RASTER_3DGS ? reinterpret_cast<const char*>(bs.inst_cnt + I)
                                                              : reinterpret_cast<const char*>(bs.inst_qmask + I + 1))
                            : reinterpret_cast<const char*>(bs.ranges + num_tiles);
-    PINGS_HIP_CHECK(hipMemsetAsync(bs.ranges, 0, (size_t)(z1 - z0), st));
+    PINGS_HIP_CHECK(hipMemsetAsync(bs.ranges, 0, align_up((size_t)(z1 - z0)), st));
   }
   if (I > 0) {
     // tile ids fit 16 bits for every image up to 4096x4096: a 2-byte key cuts the sort traffic by a quarter
@@ -1067,10 +1090,9 @@ PINGS_API int pings_raster_render(const pings_raster_settings* s, int P, int64_t
   {
     // forward dispatch order: tiles by descending list length
     pings::prof::Scope ps_o("tile_order", st);
-    hipLaunchKernelGGL(range_len_kernel, dim3(pings::ceil_div(num_tiles, 256)), dim3(256), 0, st, bs.ranges, num_tiles,
-                       bs.tile_work);
+    hipLaunchKernelGGL(tile_order_kernel<true>, dim3(1), dim3(1024), 0, st, (const uint32_t*)nullptr, bs.ranges, num_tiles,
+                       bs.tile_order, (uint32_t*)nullptr, 0u, 0u);
     PINGS_LAUNCH_CHECK();
-    if (int e = launch_tile_order(bs.tile_work, num_tiles, bs.tile_order, st)) return e;
   }
   return launch_blend_fwd(s->mode, kp, blend_plan(knobs, footprint_class, I, num_tiles), P, I, gs, bs, im, out_color,
                           out_normal, out_depth, out_alpha, per_gaussian, st);

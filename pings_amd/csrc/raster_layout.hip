@@ -57,7 +57,9 @@ GeomState carve_geom(void* blob, int P, int num_tiles) {
   g.ds_head = c.take<uint32_t>(g.ds_words);
   g.ds_cnt = g.ds_head ? g.ds_head + DS_HEAD : nullptr;
   g.zero_begin = reinterpret_cast<char*>(g.occ_bucket);
-  g.zero_bytes = g.ds_head ? (size_t)(reinterpret_cast<char*>(g.ds_head + g.ds_words) - g.zero_begin) : 0;
+  // up to the 256-byte boundary the next field starts at: a clear whose size is not a multiple of 16 bytes costs the
+  // runtime a second fill launch for the tail
+  g.zero_bytes = g.ds_head ? align_up((size_t)(reinterpret_cast<char*>(g.ds_head + g.ds_words) - g.zero_begin)) : 0;
   g.occ_bsat = c.take<uint16_t>(nt);
   g.nvalid = c.take<uint32_t>(1);
   g.ds_off = c.take<uint32_t>((size_t)DS_NB + nblk + 1);
@@ -87,6 +89,7 @@ BinState carve_binning(void* blob, int64_t I, int num_tiles, uint32_t seg) {
   b.slot_val = c.take<uint32_t>(n);
   b.tile_order = c.take<uint32_t>(2 * (size_t)num_tiles + 4);   // + the backward pass' long-list tile count
   b.tile_work = c.take<uint32_t>((size_t)num_tiles);
+  b.tile_maxc = c.take<uint32_t>((size_t)num_tiles);
   // units of SEG entries for lists beyond 2 SEG: at most I / SEG + I / (2 SEG) of them
   const size_t sg = (size_t)seg;
   b.seg_max_units = sg ? (uint32_t)(n / sg + n / (2 * sg) + 64) : 1u;
@@ -122,8 +125,6 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
   const size_t ni = (size_t)(I > 0 ? I : 1), n = 4 * ni, np = (size_t)(P > 0 ? P : 1);
   b.np_max = n / CH + np + 1;
   b.cidx = c.take<uint32_t>(ni + 2);
-  b.cbeg = c.take<uint32_t>(np + 1);
-  b.nch = c.take<uint32_t>(np + 1);
   b.pair_off = c.take<uint32_t>(np + 1);
   b.pair_owner = c.take<uint32_t>(b.np_max);
   b.partials = c.take<float>(b.np_max * GRAD_ROW);
