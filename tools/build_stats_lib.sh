@@ -12,7 +12,7 @@ for f in $R/pings_amd/csrc/*.hip; do
   o=$R/pings_amd/csrc/_obj/$b.o
   stale=0
   for d in $f $R/pings_amd/csrc/*.hpp $R/include/*.h; do [ -f $o ] && [ $o -nt $d ] || stale=1; done
-  if [ "$b" = "raster_bwd" ] || [ "$b" = "mlp" ] || [ $stale = 1 ]; then
+  if [ "$b" = "raster_bwd" ] || [ "$b" = "mlp_wave128" ] || [ $stale = 1 ]; then
     /opt/rocm/bin/hipcc $FLAGS -c $f -o $O/$b.o &
   else
     cp $R/pings_amd/csrc/_obj/$b.o $O/$b.o
