@@ -89,6 +89,7 @@ struct GeomState {
   uint32_t *tiles_sorted, *offsets_sorted;  // per depth rank: KEPT tiles of the Gaussian and their inclusive scan
   uint32_t* occ_bucket;                     // [occ_nb][num_tiles] fixed-point opacity budget per (rank bucket, tile)
   uint16_t* occ_bsat;                       // [num_tiles] last rank bucket a tile still needs (0xFFFF = all)
+  unsigned long long* occ_mask;             // [occ_nb][occ_words] bit (tile % 64) of word tile / 64: bucket <= occ_bsat[tile]
   uint32_t* nvalid;                         // [1] Gaussians that survived culling (= ranks with a real depth key)
   uint32_t* ds_head;                        // depth sort: header (key range shards, range, overflow flag), then
   uint32_t *ds_cnt, *ds_fill, *ds_off;      //   [DS_NB + blocks] bucket / per-block culled counts, [DS_NB] fill cursors,
@@ -97,7 +98,7 @@ struct GeomState {
   uint32_t* ds_idx;                         //   [P] Gaussian ids in bucket order (keys go to depth_key_sorted)
   unsigned long long* stats;                // [2] pairs before occlusion culling, visible Gaussians
   FrameSummary* summary;
-  int occ_nb;
+  int occ_nb, occ_words;                    // rank buckets per tile; 64-bit words per bucket of occ_mask
   char* temp;
   size_t temp_bytes;
   size_t total;
@@ -105,8 +106,8 @@ struct GeomState {
 
 struct BinState {
   // pre-sort, slot order (= depth rank, then tile order inside the Gaussian's rectangle): tile_key[slot],
-  // gval[slot] = Gaussian id, slot_val[slot] = slot;  sorted by tile: point_list[i] = slot
-  uint32_t *tile_key, *tile_key_sorted, *gval, *slot_val, *point_list;
+  // gval[slot] = Gaussian id;  sorted by tile: point_list[i] = slot (the sort's value input is a counting iterator)
+  uint32_t *tile_key, *tile_key_sorted, *gval, *point_list;
   uint2* ranges;
   float* inst_w;       // [I+1] per-instance sum of blend weights (0 = instance never blended)
   uint8_t* inst_qmask; // [I+1] 8x8 quadrants of the tile in which the instance blended something (bit q = qx + 2 qy)

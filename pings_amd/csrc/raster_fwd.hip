@@ -293,7 +293,7 @@ constexpr int STAT_SHARDS = 256;
 // own tile number k of the source lane's rectangle), the others serially by their lane (`serial(tile)`).
 struct RectLane {
   uint32_t g, n;
-  int xmin, ymin, wdt;
+  int xmin, ymin, wdt, hgt;
 };
 template <typename Serial, typename CoopBegin, typename Coop>
 __device__ inline void walk_rects(const RectLane& me, int gx, Serial serial, CoopBegin coop_begin, Coop coop) {
@@ -329,7 +329,7 @@ __device__ inline void walk_rects(const RectLane& me, int gx, Serial serial, Coo
 // ranks from nvalid on are the culled Gaussians (no tiles): their index and rectangle are not even loaded
 __device__ inline RectLane rect_lane(int r, const uint32_t* __restrict__ gidx_sorted, const uint4* __restrict__ rect,
                                      uint32_t nvalid) {
-  RectLane me{0u, 0u, 0, 0, 1};
+  RectLane me{0u, 0u, 0, 0, 1, 1};
   if (r >= 0 && (uint32_t)r < nvalid) {
     me.g = gidx_sorted[r];
     const uint4 rc = rect[me.g];
@@ -337,8 +337,98 @@ __device__ inline RectLane rect_lane(int r, const uint32_t* __restrict__ gidx_so
     me.xmin = (int)(rc.y & 0xFFFF);
     me.ymin = (int)(rc.y >> 16);
     me.wdt = max((int)(rc.z & 0xFFFF) - me.xmin, 1);
+    me.hgt = max((int)(rc.z >> 16) - me.ymin, 1);
   }
   return me;
+}
+
+// ---------------------------------------------------------------- kept tiles of a rectangle, from the tile bitmasks
+// Whether a (Gaussian, tile) pair is kept depends on the Gaussian's rank bucket and the tile alone, and a footprint is
+// a full rectangle: occl_scan_kernel writes, for every bucket, the set of tiles that still need it as a bitmask over
+// tile ids (GeomState::occ_mask), and the kept tiles of a rectangle row are a bit range of the bucket's mask.  The
+// unit of work is an ITEM: up to 64 consecutive tiles of one row (a row wider than 64 tiles is several items), read
+// as two neighbouring 8-byte words — one popcount counts them, a walk over the set bits emits them.  Items in
+// ascending order, bits in ascending order inside an item: row-major over the rectangle, x ascending — the slot order.
+constexpr int SMALL_ITEMS = 16;   // up to this many items a lane walks its rectangle itself, four loads in flight
+constexpr uint32_t SMALL_KEPT = 16u;  // duplicate_kernel: up to this many kept tiles the lane also emits them itself
+
+// bit i = tile s + i of the bucket whose mask row is `m` is kept, 0 <= i < w <= 64.  The second word may belong to the
+// next bucket's row, or be the one spare word behind the table: only bits of tiles below s + w survive the cut.
+__device__ inline unsigned long long kept_bits(const unsigned long long* __restrict__ m, int s, int w) {
+  const int i = s >> 6, sh = s & 63;
+  const unsigned long long lo = m[i], hi = m[i + 1];
+  const unsigned long long v = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+  return v & (~0ull >> (64 - w));
+}
+
+struct RowItems {
+  int s0, gx, wdt, cpr;   // first tile id of the rectangle, tiles per image row, rectangle width, items per row
+  float inv_cpr;
+  __device__ RowItems(int xmin, int ymin, int wdt_, int gx_)
+      : s0(ymin * gx_ + xmin), gx(gx_), wdt(wdt_), cpr((wdt_ + 63) >> 6), inv_cpr(1.0f / (float)((wdt_ + 63) >> 6)) {}
+  // first tile id and width of item k
+  __device__ void at(uint32_t k, int& s, int& w) const {
+    int y = (int)k, c = 0;
+    if (cpr > 1) {   // k / cpr without an integer division (k < 2^24: the float quotient is off by at most one)
+      y = (int)((float)k * inv_cpr);
+      c = (int)k - y * cpr;
+      if (c < 0) { --y; c += cpr; }
+      if (c >= cpr) { ++y; c -= cpr; }
+    }
+    s = s0 + y * gx + 64 * c;
+    w = min(64, wdt - 64 * c);
+  }
+};
+
+__device__ inline uint32_t rect_items(const RectLane& me) {
+  return me.n != 0u ? (uint32_t)(me.hgt * ((me.wdt + 63) >> 6)) : 0u;
+}
+
+// `serial(s, bits)` for every item of this lane's own rectangle, in order
+template <typename Serial>
+__device__ inline void walk_items_serial(const RectLane& me, uint32_t items, int gx,
+                                         const unsigned long long* __restrict__ mrow, Serial serial) {
+  const RowItems ri(me.xmin, me.ymin, me.wdt, gx);
+  for (uint32_t k0 = 0; k0 < items; k0 += 4) {
+    int s[4];
+    unsigned long long b[4];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+      int w;
+      ri.at(min(k0 + (uint32_t)u, items - 1u), s[u], w);
+      b[u] = kept_bits(mrow, s[u], w);
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u)
+      if (k0 + (uint32_t)u < items) serial(s[u], b[u]);
+  }
+}
+
+// The rectangles of the lanes in `big`, one after the other, by the whole wave: lane l takes items l, l + 64, ... of
+// the source lane's rectangle.  `begin(src)` once per rectangle, then `step(s, bits)` in every lane for every 64
+// items (bits = 0 in a lane without an item).
+template <typename Begin, typename Step>
+__device__ inline void walk_items_coop(unsigned long long big, const RectLane& me, uint32_t items, int gx, uint32_t bk,
+                                       const unsigned long long* __restrict__ mask, int words, Begin begin, Step step) {
+  const int lane = threadIdx.x & 63;
+  while (big) {
+    const int src = __ffsll((long long)big) - 1;
+    big &= big - 1;
+    const uint32_t n = lane_value(items, src);
+    const RowItems ri(lane_value(me.xmin, src), lane_value(me.ymin, src), lane_value(me.wdt, src), gx);
+    const unsigned long long* mrow = mask + (size_t)lane_value(bk, src) * words;
+    begin(src);
+    for (uint32_t k0 = 0; k0 < n; k0 += 64) {
+      const uint32_t k = k0 + (uint32_t)lane;
+      int sk = 0, w = 1;
+      unsigned long long bits = 0ull;
+      if (k < n) {
+        ri.at(k, sk, w);
+        bits = kept_bits(mrow, sk, w);
+      }
+      step(sk, bits);
+    }
+  }
 }
 
 // ---------------------------------------------------------------- occlusion culling of instances
@@ -569,7 +659,7 @@ __global__ __launch_bounds__(256) void occl_budget_kernel(int P, int gx, int nb,
     const int x0 = me.xmin + (int)(rc.x & 255u), x1 = (int)(rc.z & 0xFFFF) - (int)((rc.x >> 8) & 255u);
     const int y0 = me.ymin + (int)((rc.x >> 16) & 255u), y1 = (int)(rc.z >> 16) - (int)(rc.x >> 24);
     if (x1 > x0 && y1 > y0) {
-      me.xmin = x0; me.ymin = y0; me.wdt = x1 - x0; me.n = (uint32_t)((x1 - x0) * (y1 - y0));
+      me.xmin = x0; me.ymin = y0; me.wdt = x1 - x0; me.hgt = y1 - y0; me.n = (uint32_t)((x1 - x0) * (y1 - y0));
     } else {
       me.n = 0u;
     }
@@ -602,9 +692,15 @@ __global__ __launch_bounds__(256) void occl_budget_kernel(int P, int gx, int nb,
 // Running budget over the rank buckets -> last bucket a tile needs.  A 512-thread workgroup takes 64 tiles x 8
 // bucket groups: thread (tile, g) loads its group's buckets (coalesced across the 64 tiles, all loads independent),
 // the group sums meet in LDS, and the group in which the running sum crosses the threshold finds the bucket.
+// Epilogue: the tile bitmasks of the row walks.  The workgroup's 64 tiles are one word of every bucket's mask
+// (word blockIdx.x of `words` = gridDim.x): wave g ballots `bucket <= bsat` for each bucket of its group and lane u
+// stores the word of the group's bucket u.  Bits of tiles from num_tiles on are 0.  With the budget all zero (the
+// occlusion bound switched off) every tile comes out as OCC_ALL and every mask as all ones.
 __global__ __launch_bounds__(512) void occl_scan_kernel(int num_tiles, int nb, const uint32_t* __restrict__ bucket,
-                                                        uint16_t* __restrict__ bsat) {
+                                                        uint16_t* __restrict__ bsat,
+                                                        unsigned long long* __restrict__ mask) {
   __shared__ uint32_t sSum[8][64];
+  __shared__ uint32_t sSat[64];
   const int t = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int tile = blockIdx.x * 64 + t;
   const int per = nb / 8;  // nb is a power of two >= 32
@@ -622,7 +718,10 @@ __global__ __launch_bounds__(512) void occl_scan_kernel(int num_tiles, int nb, c
   for (int k = 0; k < g; ++k) before += sSum[k][t];
   const uint32_t total = before + sSum[g][t];
   if (tile < num_tiles) {
-    if (g == 7 && total < thr) bsat[tile] = OCC_ALL;  // never saturates: the last group sees the full sum
+    if (g == 7 && total < thr) {  // never saturates: the last group sees the full sum
+      bsat[tile] = OCC_ALL;
+      sSat[t] = OCC_ALL;
+    }
     if (before < thr && total >= thr) {               // exactly one group crosses the threshold
       uint32_t run = before;
       int res = -1;
@@ -632,15 +731,24 @@ __global__ __launch_bounds__(512) void occl_scan_kernel(int num_tiles, int nb, c
         if (res < 0 && run >= thr) res = u;
       }
       bsat[tile] = (uint16_t)(g * per + res);
+      sSat[t] = (uint32_t)(g * per + res);
     }
   }
+  __syncthreads();
+  const uint32_t sat = tile < num_tiles ? sSat[t] : 0u;
+  unsigned long long word = 0ull;
+  for (int u = 0; u < per; ++u) {
+    const unsigned long long w = __ballot(tile < num_tiles && (uint32_t)(g * per + u) <= sat);
+    if (t == u) word = w;
+  }
+  if (t < per) mask[(size_t)(g * per + t) * gridDim.x + blockIdx.x] = word;
 }
 
 // kept tiles per depth rank (the Gaussian's rank bucket must not exceed the tile's last needed bucket)
-__global__ __launch_bounds__(256) void count_kept_kernel(int P, int gx, int nb,
+__global__ __launch_bounds__(256) void count_kept_kernel(int P, int gx, int nb, int words,
                                                          const uint32_t* __restrict__ gidx_sorted,
                                                          const uint4* __restrict__ rect,
-                                                         const uint16_t* __restrict__ bsat,
+                                                         const unsigned long long* __restrict__ mask,
                                                          const uint32_t* __restrict__ nvalid,
                                                          uint32_t* __restrict__ tiles_sorted,
                                                          unsigned long long* __restrict__ pairs_full) {
@@ -649,20 +757,23 @@ __global__ __launch_bounds__(256) void count_kept_kernel(int P, int gx, int nb,
   const uint32_t nv = *nvalid;
   const RectLane me = rect_lane(r, gidx_sorted, rect, nv);
   const uint32_t bk = rank_bucket(r, nb, nv);
-  uint32_t kept = 0, sb = 0, acc = 0;
+  const uint32_t items = rect_items(me);
+  uint32_t kept = 0, acc = 0;
+  if (items != 0u && items <= (uint32_t)SMALL_ITEMS)
+    walk_items_serial(me, items, gx, mask + (size_t)bk * words,
+                      [&](int, unsigned long long bits) { kept += (uint32_t)__popcll(bits); });
   int cur = -1;
-  walk_rects(
-      me, gx, [&](int tx, int ty) { kept += (bk <= (uint32_t)bsat[ty * gx + tx]) ? 1u : 0u; },
-      [&](int src) {
-        if (cur >= 0 && lane == cur) kept = acc;
-        cur = src;
-        acc = 0;
-        sb = lane_value(bk, src);
-      },
-      [&](int, int tx, int ty, bool act) {
-        acc += (uint32_t)__popcll(__ballot(act && sb <= (uint32_t)bsat[ty * gx + tx]));
-      });
-  if (cur >= 0 && lane == cur) kept = acc;
+  auto flush = [&]() {   // the finished rectangle's count, summed over the wave, to its lane
+    if (cur < 0) return;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) acc += (uint32_t)__shfl_xor((int)acc, off, 64);
+    if (lane == cur) kept = acc;
+  };
+  walk_items_coop(
+      __ballot(items > (uint32_t)SMALL_ITEMS), me, items, gx, bk, mask, words,
+      [&](int src) { flush(); cur = src; acc = 0; },
+      [&](int, unsigned long long bits) { acc += (uint32_t)__popcll(bits); });
+  flush();
   if (r >= 0) tiles_sorted[r] = kept;
   // footprint statistic for the blend kernels' pixels-per-lane choice: all (Gaussian, tile) pairs before culling
   uint32_t tot = me.n;
@@ -682,51 +793,59 @@ __global__ __launch_bounds__(256) void count_kept_kernel(int P, int gx, int nb,
   }
 }
 
-// Emits the kept (tile id, slot) instances in depth order; gval[slot] = Gaussian id, slot_val[slot] = slot.
+// Emits the kept (tile id, slot) instances in depth order; gval[slot] = Gaussian id.  A Gaussian that keeps nothing
+// (count_kept_kernel's count) is not walked at all; one that keeps more than SMALL_KEPT tiles, or has more than
+// SMALL_ITEMS items, is emitted by the whole wave: the items' bits in parallel, then one store step per non-empty
+// item, lane i taking bit i (consecutive slots: the stores of a step are contiguous).
 template <typename KeyT>
-__global__ __launch_bounds__(256) void duplicate_kernel(int P, int gx, int nb,
+__global__ __launch_bounds__(256) void duplicate_kernel(int P, int gx, int nb, int words,
                                                          const uint32_t* __restrict__ gidx_sorted,
                                                          const uint32_t* __restrict__ offsets_sorted,
                                                          const uint32_t* __restrict__ tiles_sorted,
                                                          const uint4* __restrict__ rect,
-                                                         const uint16_t* __restrict__ bsat,
+                                                         const unsigned long long* __restrict__ mask,
                                                          const uint32_t* __restrict__ nvalid,
                                                          KeyT* __restrict__ tile_key,
-                                                         uint32_t* __restrict__ gval,
-                                                         uint32_t* __restrict__ slot_val) {
+                                                         uint32_t* __restrict__ gval) {
   const int r = strided_rank(P);
+  const int lane = threadIdx.x & 63;
   const uint32_t nv = *nvalid;
   const RectLane me = rect_lane(r, gidx_sorted, rect, nv);
   const uint32_t bk = rank_bucket(r, nb, nv);
-  uint32_t o = r >= 0 ? offsets_sorted[r] - tiles_sorted[r] : 0u;  // first slot of this Gaussian
-  uint32_t sb = 0, so = 0, sg = 0;
-  walk_rects(
-      me, gx,
-      [&](int tx, int ty) {
-        const int tile = ty * gx + tx;
-        if (bk <= (uint32_t)bsat[tile]) {
-          tile_key[o] = (KeyT)tile;
-          gval[o] = me.g;
-          slot_val[o] = o;
-          ++o;
-        }
-      },
+  const uint32_t kept = r >= 0 ? tiles_sorted[r] : 0u;
+  uint32_t o = r >= 0 ? offsets_sorted[r] - kept : 0u;  // first slot of this Gaussian
+  const uint32_t items = kept != 0u ? rect_items(me) : 0u;
+  const bool coop = items > (uint32_t)SMALL_ITEMS || kept > SMALL_KEPT;
+  if (items != 0u && !coop)
+    walk_items_serial(me, items, gx, mask + (size_t)bk * words, [&](int s, unsigned long long bits) {
+      while (bits) {
+        tile_key[o] = (KeyT)(s + __builtin_ctzll(bits));
+        gval[o] = me.g;
+        ++o;
+        bits &= bits - 1;
+      }
+    });
+  uint32_t so = 0, sg = 0;
+  walk_items_coop(
+      __ballot(items != 0u && coop), me, items, gx, bk, mask, words,
       [&](int src) {
-        sb = lane_value(bk, src);
         so = lane_value(o, src);
         sg = lane_value(me.g, src);
       },
-      [&](int, int tx, int ty, bool act) {
-        const int tile = ty * gx + tx;
-        const bool keep = act && sb <= (uint32_t)bsat[tile];
-        const unsigned long long bal = __ballot(keep);
-        if (keep) {
-          const uint32_t pos = so + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
-          tile_key[pos] = (KeyT)tile;
-          gval[pos] = sg;
-          slot_val[pos] = pos;
+      [&](int s, unsigned long long bits) {
+        unsigned long long todo = __ballot(bits != 0ull);
+        while (todo) {
+          const int j = __ffsll((long long)todo) - 1;
+          todo &= todo - 1;
+          const uint32_t blo = lane_value((uint32_t)bits, j), bhi = lane_value((uint32_t)(bits >> 32), j);
+          const int sj = lane_value(s, j);
+          if (((lane < 32 ? blo : bhi) >> (lane & 31)) & 1u) {
+            const uint32_t pos = so + __builtin_amdgcn_mbcnt_hi(bhi, __builtin_amdgcn_mbcnt_lo(blo, 0u));
+            tile_key[pos] = (KeyT)(sj + lane);
+            gval[pos] = sg;
+          }
+          so += (uint32_t)(__popc(blo) + __popc(bhi));
         }
-        so += (uint32_t)__popcll(bal);
       });
 }
 
@@ -967,21 +1086,20 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
                            gs.rec, gs.nvalid, num_tiles, gs.occ_bucket);
         PINGS_LAUNCH_CHECK();
       }
-      {
-        pings::prof::Scope ps("occl_scan", st);
-        hipLaunchKernelGGL(occl_scan_kernel, dim3(pings::ceil_div(num_tiles, 64)), dim3(512), 0, st, num_tiles,
-                           gs.occ_nb, gs.occ_bucket, gs.occ_bsat);
-        PINGS_LAUNCH_CHECK();
-      }
-    } else {
-      // every tile keeps every rank bucket (OCC_ALL); nvalid stays: rect_lane skips the culled ranks with it
-      PINGS_HIP_CHECK(hipMemsetAsync(gs.occ_bsat, 0xFF, sizeof(uint16_t) * (size_t)num_tiles, st));
+    }
+    {
+      // with the bound off the budget is still all zero: every tile keeps every rank bucket (OCC_ALL, masks all ones);
+      // nvalid stays: rect_lane skips the culled ranks with it
+      pings::prof::Scope ps("occl_scan", st);
+      hipLaunchKernelGGL(occl_scan_kernel, dim3(gs.occ_words), dim3(512), 0, st, num_tiles, gs.occ_nb, gs.occ_bucket,
+                         gs.occ_bsat, gs.occ_mask);
+      PINGS_LAUNCH_CHECK();
     }
     {
       pings::prof::Scope ps("tile_count_scan", st);
       if (attempt > 0) PINGS_HIP_CHECK(hipMemsetAsync(gs.stats, 0, 3 * STAT_SHARDS * sizeof(unsigned long long), st));
-      hipLaunchKernelGGL(count_kept_kernel, grid, block, 0, st, P, kp.gx, gs.occ_nb, gs.gidx_sorted, gs.rect,
-                         gs.occ_bsat, gs.nvalid, gs.tiles_sorted, gs.stats);
+      hipLaunchKernelGGL(count_kept_kernel, grid, block, 0, st, P, kp.gx, gs.occ_nb, gs.occ_words, gs.gidx_sorted,
+                         gs.rect, gs.occ_mask, gs.nvalid, gs.tiles_sorted, gs.stats);
       PINGS_LAUNCH_CHECK();
     }
     // The summary needs nothing of the instance scan (the kept total is one of count_kept_kernel's 64-bit statistics),
@@ -1065,15 +1183,16 @@ PINGS_API int pings_raster_render(const pings_raster_settings* s, int P, int64_t
       {
         pings::prof::Scope ps("duplicate", st);
         hipLaunchKernelGGL(duplicate_kernel<KeyT>, dim3(pings::ceil_div(P, 256)), dim3(256), 0, st, P,
-                           kp.gx, gs.occ_nb, gs.gidx_sorted, gs.offsets_sorted, gs.tiles_sorted, gs.rect,
-                           gs.occ_bsat, gs.nvalid, key, bs.gval, bs.slot_val);
+                           kp.gx, gs.occ_nb, gs.occ_words, gs.gidx_sorted, gs.offsets_sorted, gs.tiles_sorted,
+                           gs.rect, gs.occ_mask, gs.nvalid, key, bs.gval);
         PINGS_LAUNCH_CHECK();
       }
       {
         pings::prof::Scope ps("tile_sort", st);
         size_t tb = bs.temp_bytes;
-        PINGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(bs.temp, tb, key, key_sorted, bs.slot_val, bs.point_list,
-                                                           (int)I, 0, tile_bits(num_tiles), st));
+        // the values are the slots themselves: a counting iterator, not an array of I words written to be read once
+        PINGS_HIP_CHECK(rocprim::radix_sort_pairs(bs.temp, tb, key, key_sorted, rocprim::counting_iterator<uint32_t>(0u),
+                                                  bs.point_list, (size_t)I, 0u, (unsigned)tile_bits(num_tiles), st));
       }
       {
         pings::prof::Scope ps("tile_ranges", st);

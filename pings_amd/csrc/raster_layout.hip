@@ -24,6 +24,14 @@ static size_t sort_temp_bytes(int64_t n) {
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, c, (uint16_t*)nullptr, (uint16_t*)nullptr,
                                            (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 16);
   if (c > a) a = c;
+  // the tile sort's values come from a counting iterator (pings_raster_render): same algorithm, asked for its own size
+  size_t d = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, d, (uint32_t*)nullptr, (uint32_t*)nullptr,
+                                  rocprim::counting_iterator<uint32_t>(0u), (uint32_t*)nullptr, (size_t)n, 0u, 32u);
+  size_t e = 0;
+  (void)rocprim::radix_sort_pairs(nullptr, e, (uint16_t*)nullptr, (uint16_t*)nullptr,
+                                  rocprim::counting_iterator<uint32_t>(0u), (uint32_t*)nullptr, (size_t)n, 0u, 16u);
+  a = std::max(a, std::max(d, e));
   return align_up(a > b ? a : b) + 256;
 }
 
@@ -61,6 +69,9 @@ GeomState carve_geom(void* blob, int P, int num_tiles) {
   // runtime a second fill launch for the tail
   g.zero_bytes = g.ds_head ? align_up((size_t)(reinterpret_cast<char*>(g.ds_head + g.ds_words) - g.zero_begin)) : 0;
   g.occ_bsat = c.take<uint16_t>(nt);
+  // + 1: the row walks read a bit range as two neighbouring words, the second of which may lie one past the table
+  g.occ_words = (int)((nt + 63) / 64);
+  g.occ_mask = c.take<unsigned long long>((size_t)g.occ_nb * (size_t)g.occ_words + 1);
   g.nvalid = c.take<uint32_t>(1);
   g.ds_off = c.take<uint32_t>((size_t)DS_NB + nblk + 1);
   g.ds_idx = c.take<uint32_t>(n);
@@ -86,7 +97,9 @@ BinState carve_binning(void* blob, int64_t I, int num_tiles, uint32_t seg) {
   b.tile_key = c.take<uint32_t>(n);
   b.tile_key_sorted = c.take<uint32_t>(n);
   b.gval = c.take<uint32_t>(n);
-  b.slot_val = c.take<uint32_t>(n);
+  // 4 n bytes nobody uses (the tile sort's value input until it became a counting iterator): the fields behind keep
+  // their offsets, which tests/test_raster_glue.py reads straight out of the blob
+  (void)c.take<uint32_t>(n);
   b.tile_order = c.take<uint32_t>(2 * (size_t)num_tiles + 4);   // + the backward pass' long-list tile count
   b.tile_work = c.take<uint32_t>((size_t)num_tiles);
   b.tile_maxc = c.take<uint32_t>((size_t)num_tiles);
