@@ -97,7 +97,8 @@ inline Plan mlp_plan(int IN, int HID, int OUT) {
   // classes per thread count); the tile of gY is 32 x 32 floats whatever OUT is: 4, 6 (5.3), 8, 16 for 4 .. 1 waves
   const int nthr = 64 * (HID / 32), need = (TR * ((IN + 1) & ~1) + nthr - 1) / nthr;
   p.fwd_pfx = need <= 5 ? 5 : need <= 10 ? 10 : need <= 18 ? 18 : 32;
-  p.bwd_pfx = HID == 128 ? (need <= 5 ? 5 : need <= 9 ? 9 : 16) : HID == 96 ? (need <= 6 ? 6 : 11)
+  // (HID = 128 comes here with IN > 32 only: need = ceil(INP / 8) is 5 .. 8)
+  p.bwd_pfx = HID == 128 ? (need <= 5 ? 5 : 9) : HID == 96 ? (need <= 6 ? 6 : 11)
             : HID == 64 ? (need <= 9 ? 9 : 16) : (need <= 18 ? 18 : 32);
   p.bwd_pfg = HID == 128 ? 4 : HID == 96 ? 6 : HID == 64 ? 8 : 16;
   return p;

@@ -329,7 +329,7 @@ int launch_bwd_wg(const Plan& p, int grid, hipStream_t st, const Dims& d, const 
   };
   using std::integral_constant;   // the <PF_X, PF_G> classes that exist: PF_G follows the thread count (mlp_plan)
   switch (p.bwd_pfg) {
-    case 4: return with_class<5, 9, 16>(p.bwd_pfx, [&](auto px) { return launch(px, integral_constant<int, 4>{}); });
+    case 4: return with_class<5, 9>(p.bwd_pfx, [&](auto px) { return launch(px, integral_constant<int, 4>{}); });
     case 6: return with_class<6, 11>(p.bwd_pfx, [&](auto px) { return launch(px, integral_constant<int, 6>{}); });
     case 8: return with_class<9, 16>(p.bwd_pfx, [&](auto px) { return launch(px, integral_constant<int, 8>{}); });
     default: return with_class<18, 32>(p.bwd_pfx, [&](auto px) { return launch(px, integral_constant<int, 16>{}); });
