@@ -5,8 +5,8 @@
 //   gather_kernel    rows `sel` of the map tensors -> dense per-view inputs: position, orientation,
 //                    base colour, geo feature (+ horizontal view distance when dist_concat_on),
 //                    colour feature (+ view direction in the neural point's frame when view_concat_on)
-//                    (:551-597, :672-675, :692-699).  One wave per 2 rows of up to 64+64 floats: the feature
-//                    rows are read and written as whole coalesced rows.
+//                    (:551-597, :672-675, :692-699).  One 16-lane group per row (four rows per wave): the
+//                    feature rows are read and written 16 consecutive floats at a time.
 //   plan_kernel      keep flag per Gaussian (alpha > 0, optional scale filter, :727-761), then an
 //                    exclusive scan (rocPRIM) gives every kept Gaussian its compacted row.
 //   forward_kernel   one lane per Gaussian: activations + quaternion algebra (:605-716) written straight
@@ -209,7 +209,9 @@ __global__ __launch_bounds__(256) void forward_kernel(SpawnArgs a, int64_t nk, f
   {
     float r0 = a.rot_raw[g * 4 + 0], r1 = a.rot_raw[g * 4 + 1], r2 = a.rot_raw[g * 4 + 2],
           r3 = a.rot_raw[g * 4 + 3];
-    const float nrm = fmaxf(sqrtf(((r0 * r0 + r1 * r1) + r2 * r2) + r3 * r3), kNormEps);
+    // clamp_min(eps) keeps a NaN norm (fmaxf would return eps): one NaN component zeroes the whole row, as in torch
+    const float nr = sqrtf(((r0 * r0 + r1 * r1) + r2 * r2) + r3 * r3);
+    const float nrm = nr < kNormEps ? kNormEps : nr;
     r0 /= nrm; r1 /= nrm; r2 /= nrm; r3 /= nrm;
     if (r0 != r0) r0 = 0.f;
     if (r1 != r1) r1 = 0.f;

@@ -129,9 +129,15 @@ class _Activate(torch.autograd.Function):
         alpha, color = torch.empty(count, 1, **f32), torch.empty(count, 3, **f32)
         alpha_all = torch.empty(nk, 1, **f32)
         gfree = torch.empty(count, dtype=torch.uint8, device=dev) if free is not None else None
+        outs = (xyz, scale, rot, alpha, color)
+        if count == 0 and nk > 0:
+            # every Gaussian filtered out: the [0, d] outputs have no storage, and a null output is an argument error.
+            # `alpha_all` is still to be written, so the kernel runs with one row nobody writes (all dest are -1).
+            spare = torch.empty(4, **f32)
+            outs = (spare,) * 5
         st = L.pings_spawn_forward(C.byref(p), *[_lib.ptr(t) for t in raws], _lib.ptr(pos), _lib.ptr(quat),
                                    _lib.ptr(base), _lib.ptr(dist_ratio), _lib.ptr(free), _lib.ptr(dest),
-                                   _lib.ptr(xyz), _lib.ptr(scale), _lib.ptr(rot), _lib.ptr(alpha), _lib.ptr(color),
+                                   *[_lib.ptr(o) for o in outs],
                                    _lib.ptr(alpha_all), _lib.ptr(gfree), _lib.stream_ptr(dev))
         _lib.check(st, "pings_spawn_forward")
         ctx.save_for_backward(*raws, quat, *([base] if base is not None else []),
