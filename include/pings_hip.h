@@ -35,7 +35,7 @@
 
 /* ABI version of this header (bumped on any signature change).  A binding compares pings_abi_version() of the
  * library it loaded with the PINGS_ABI_VERSION of the header it was written against (pings_amd/_lib.py does). */
-#define PINGS_ABI_VERSION 9
+#define PINGS_ABI_VERSION 10
 PINGS_API int pings_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). Host string. */
 PINGS_API const char* pings_last_error(void);
@@ -432,6 +432,14 @@ PINGS_API int pings_sdf_forward(const pings_knn_map* m, const pings_sdf_decoder*
  * neighbours as rows of m->neural_points (what the weights were measured to), kept for pings_sdf_double_backward.  sdf_std[B] (optional): spread of the
  * per-neighbour predictions sqrt(sum_m w_m (s_m - sdf)^2), the tracker's validity filter
  * (utils/tracker.py:303-313,408); 0 in weighted_first mode. */
+
+/* Which kernel a fused query of this shape runs: out[0] = family (0 vector ALU, lane per hidden unit; 1 matrix core,
+ * four queries per wave step), out[1] = the kernel's padded input width class.  `order`: 0 pings_sdf_forward,
+ * 1 pings_sdf_backward, 2 pings_sdf_double_backward.  `misaligned`: the feature table (for the backward also its
+ * scratch) is not 16-byte aligned.  Honours PINGS_SDF_FWD / PINGS_SDF_BWD = vector like the launches themselves, which
+ * follow the same plan.  Needs no device and launches nothing. */
+PINGS_API int pings_sdf_plan(int nn_k, int feat_dim, int hidden, int weighted_first, int order, int misaligned,
+                             int32_t* out);
 
 /* First-order backward of the fused query w.r.t. the feature table and the decoder
  * (the training path of Mapper.sdf_mapping, utils/mapper.py:822-970: loss(sdf).backward()).

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 9                                                   # PINGS_ABI_VERSION
+ABI_VERSION = 10                                                  # PINGS_ABI_VERSION
 
 RASTER_SURFEL, RASTER_3DGS, RASTER_2DGS = 0, 1, 2                 # PINGS_RASTER_*: pings_raster_settings.mode
 HEAD_COLOR, HEAD_SEMANTIC = 0, 1                                  # PINGS_HEAD_*: pings_head_reduce mode
@@ -174,6 +174,7 @@ SIGNATURES = {
     "pings_rows_plan_apply": (i32, [vp, i64, i64, vp, i64, i32, vp, vp, vp]),
     "pings_sdf_forward": (i32, [C.POINTER(KnnMap), C.POINTER(SdfDecoder), vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp,
                                 vp, vp, vp, vp, vp]),
+    "pings_sdf_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]),
     "pings_sdf_backward_scratch_bytes": (sz, [i64, i32, i32, i32, i64]),
     "pings_sdf_double_backward": (i32, [C.POINTER(SdfDecoder), vp, i64, vp, vp, vp, i32, vp, i64, i32, vp, vp, vp, vp,
                                         vp, vp, vp, vp, vp, vp, vp]),

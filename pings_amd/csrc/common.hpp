@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include <cstdio>
+#include <type_traits>
 
 #include "pings_hip.h"
 
@@ -62,3 +63,30 @@ struct Scope {
       return PINGS_ERR_ARG;                                                          \
     }                                                                                \
   } while (0)
+
+namespace pings {
+
+// Returns f(std::integral_constant<int, V>{}), a PINGS status, for the V among Vs that equals v: where a planned class
+// becomes a kernel template argument (`[&](auto ks) { ... kernel<ks()> ... }`).  Only the listed classes are
+// instantiated; a class with no kernel is an error, never another kernel.  `what` names the path in the error text.
+template <int... Vs, typename F>
+int with_class(int v, const char* what, F&& f) {
+  int e = PINGS_ERR_ARG;
+  if (!((v == Vs ? (e = f(std::integral_constant<int, Vs>{}), true) : false) || ...))
+    set_error("%s: no kernel is built for class %d", what, v);
+  return e;
+}
+
+// the same for a flag that is a kernel template argument: f(std::true_type{}) or f(std::false_type{})
+template <typename F>
+int with_flag(bool v, F&& f) { return v ? f(std::true_type{}) : f(std::false_type{}); }
+
+// hipLaunchKernelGGL and the launch check, as a PINGS status
+template <typename... KA, typename... A>
+int launch(void (*kernel)(KA...), dim3 grid, int nthreads, size_t lds, hipStream_t st, A... args) {
+  hipLaunchKernelGGL(kernel, grid, dim3(nthreads), lds, st, args...);
+  PINGS_LAUNCH_CHECK();
+  return PINGS_OK;
+}
+
+}  // namespace pings

@@ -21,9 +21,7 @@
 // Distances are evaluated as ((dx*dx + dy*dy) + dz*dz) without fused multiply-adds
 // (-ffp-contract=off), which reproduces the reference's fp32 values bit for bit, so the
 // neighbour order is index-exact.
-#include <string>
-
-#include "knn_common.hpp"
+#include "sdf_plan.hpp"
 
 namespace {
 using namespace pings_knn;
@@ -401,7 +399,7 @@ PINGS_API int pings_knn_search(const pings_knn_map* m, const float* queries, int
   PINGS_ARG_CHECK(B > 0 && queries && idx && d2 && nn_counts, "null pointer");
   hipStream_t st = pings::as_stream(stream);
   pings::prof::Scope ps("knn_search", st);
-  hipLaunchKernelGGL(knn_search_kernel, dim3(grid_for(B)), dim3(64 * WAVES_PER_BLOCK), 0, st, *m, queries,
+  hipLaunchKernelGGL(knn_search_kernel, dim3(capped_grid(B)), dim3(64 * WAVES_PER_BLOCK), 0, st, *m, queries,
                      (long long)B, (long long*)idx, d2, (long long*)nn_counts, (long long*)global_idx);
   PINGS_LAUNCH_CHECK();
   return PINGS_OK;
@@ -477,24 +475,31 @@ PINGS_API int pings_sdf_forward(const pings_knn_map* m, const pings_sdf_decoder*
   PINGS_ARG_CHECK(B > 0 && features && points && queries && sdf, "null pointer");
   hipStream_t st = pings::as_stream(stream);
   pings::prof::Scope ps("sdf_forward", st);
-  // per-neighbour decoder, nn_k <= 8: the matrix-core kernel (sdf_fwd_mfma.hip); PINGS_SDF_FWD=vector keeps this file's
-  const char* fwd_env = getenv("PINGS_SDF_FWD");   // read per call: the tests switch it in-process
-  const bool force_vector = fwd_env && std::string(fwd_env) == "vector";
-  if (!force_vector && sdf_forward_mfma_supported(m, dec, features))
-    return sdf_forward_mfma_launch(m, dec, features, points, orientations, certainties, after_pgo, queries, B, sdf,
-                                   grad_x, nn_counts, certainty, idx_out, w_out, sdf_std, gidx_out, st);
-  const int in_dim = dec->feat_dim + 3;
-#define PINGS_SDF_LAUNCH_G(PAD, G)                                                                          \
-  hipLaunchKernelGGL((sdf_forward_kernel<PAD, G>), dim3(grid_for(B, (const void*)sdf_forward_kernel<PAD, G>)), dim3(64 * WAVES_PER_BLOCK), 0, st, *m, \
-                     *dec, features, points, orientations, certainties, (int)after_pgo, queries,       \
-                     (long long)B, sdf, grad_x, (long long*)nn_counts, certainty, (long long*)idx_out, w_out, sdf_std, \
-                     (long long*)gidx_out)
-#define PINGS_SDF_LAUNCH(PAD) do { if (grad_x) PINGS_SDF_LAUNCH_G(PAD, true); else PINGS_SDF_LAUNCH_G(PAD, false); } while (0)
-  if (in_dim <= 12) PINGS_SDF_LAUNCH(12);
-  else if (in_dim <= 36) PINGS_SDF_LAUNCH(36);
-  else PINGS_SDF_LAUNCH(64);
-#undef PINGS_SDF_LAUNCH
-#undef PINGS_SDF_LAUNCH_G
-  PINGS_LAUNCH_CHECK();
+  const SdfPlan p = sdf_plan(m->nn_k, dec->feat_dim, dec->hidden, dec->weighted_first != 0, SDF_FORWARD,
+                             misaligned16(features));
+  if (p.family == SDF_MATRIX_CORE)
+    return sdf_forward_mfma_launch(p.in_pad, m, dec, features, points, orientations, certainties, after_pgo, queries,
+                                   B, sdf, grad_x, nn_counts, certainty, idx_out, w_out, sdf_std, gidx_out, st);
+  return pings::with_class<12, 36, 64>(p.in_pad, "SDF forward", [&](auto pad) {
+    return pings::with_flag(grad_x != nullptr, [&](auto grad) {
+      const auto kernel = sdf_forward_kernel<decltype(pad)::value, decltype(grad)::value>;
+      return pings::launch(kernel, dim3(resident_grid(B, (const void*)kernel)), 64 * WAVES_PER_BLOCK, 0, st, *m, *dec,
+                           features, points, orientations, certainties, (int)after_pgo, queries, (long long)B, sdf,
+                           grad_x, (long long*)nn_counts, certainty, (long long*)idx_out, w_out, sdf_std,
+                           (long long*)gidx_out);
+    });
+  });
+}
+
+// {family, class} of the kernel a query of this shape and order runs (enums of sdf_plan.hpp); no device is touched
+PINGS_API int pings_sdf_plan(int nn_k, int feat_dim, int hidden, int weighted_first, int order, int misaligned,
+                             int32_t* out) {
+  PINGS_ARG_CHECK(nn_k > 0 && nn_k <= MAX_NNK, "nn_k must be in 1..16");
+  PINGS_ARG_CHECK(hidden > 0 && hidden <= 64, "hidden must be in 1..64");
+  PINGS_ARG_CHECK(feat_dim > 0 && feat_dim + 3 <= MAX_IN, "feature dim must be <= 61");
+  PINGS_ARG_CHECK(order >= SDF_FORWARD && order <= SDF_DOUBLE_BACKWARD && out, "order must be 0, 1 or 2");
+  const SdfPlan p = sdf_plan(nn_k, feat_dim, hidden, weighted_first != 0, (SdfOrder)order, misaligned != 0);
+  out[0] = p.family;
+  out[1] = p.in_pad;
   return PINGS_OK;
 }

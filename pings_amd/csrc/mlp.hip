@@ -79,7 +79,7 @@ int check_dims(int64_t N, int IN, int HID, int OUT) {
 // Sums a launch's per-workgroup partials in fixed order into the four weight gradients.
 int launch_reduce(hipStream_t st, const float* partials, int nblocks, size_t per_block, int IN, int HID, int OUT,
                   float* gW1, float* gb1, float* gW2, float* gb2) {
-  return launch(mlp_reduce_kernel, dim3((unsigned)pings::ceil_div<size_t>(per_block, 256)), 256, 0, st, partials,
+  return pings::launch(mlp_reduce_kernel, dim3((unsigned)pings::ceil_div<size_t>(per_block, 256)), 256, 0, st, partials,
                 nblocks, per_block, IN, HID, OUT, gW1, gb1, gW2, gb2);
 }
 
@@ -254,6 +254,6 @@ PINGS_API int pings_mlp_backward_grouped(const pings_mlp_job* jobs, int njobs, i
   J.wg0[0] = 0;
   for (int g = 0; g < njobs; ++g) J.wg0[g + 1] = J.wg0[g] + share[g];
   if (int e = launch_bwd_wave_grouped(J.wg0[njobs], njobs, st, N, J)) return e;
-  return launch(mlp_reduce_grouped_kernel, dim3((unsigned)pings::ceil_div<size_t>(max_pb, 256), njobs), 256, 0, st, J,
+  return pings::launch(mlp_reduce_grouped_kernel, dim3((unsigned)pings::ceil_div<size_t>(max_pb, 256), njobs), 256, 0, st, J,
                 128);
 }

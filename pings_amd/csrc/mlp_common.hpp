@@ -6,8 +6,6 @@
 //   mlp_h64o1.hip     the SDF decoder shape, HID = 64, OUT = 1: forward, backward, backward of the backward
 //   mlp_wg.hip        a workgroup of HID / 32 waves per tile, weights in LDS: every other shape check_dims admits
 #pragma once
-#include <type_traits>
-
 #include "common.hpp"
 
 namespace pings {
@@ -102,25 +100,6 @@ inline Plan mlp_plan(int IN, int HID, int OUT) {
             : HID == 64 ? (need <= 9 ? 9 : 16) : (need <= 18 ? 18 : 32);
   p.bwd_pfg = HID == 128 ? 4 : HID == 96 ? 6 : HID == 64 ? 8 : 16;
   return p;
-}
-
-// Returns f(std::integral_constant<int, V>{}), a PINGS status, for the V among Vs that equals v: where a planned class
-// becomes a kernel template argument (`[&](auto ks) { ... kernel<ks()> ... }`).  Only the listed classes are
-// instantiated; a class with no kernel is an error, never another kernel.
-template <int... Vs, typename F>
-int with_class(int v, F&& f) {
-  int e = PINGS_ERR_ARG;
-  if (!((v == Vs ? (e = f(std::integral_constant<int, Vs>{}), true) : false) || ...))
-    set_error("decoder MLP: no kernel is built for class %d", v);
-  return e;
-}
-
-// hipLaunchKernelGGL and the launch check, as a PINGS status
-template <typename... KA, typename... A>
-int launch(void (*kernel)(KA...), dim3 grid, int nthreads, size_t lds, hipStream_t st, A... args) {
-  hipLaunchKernelGGL(kernel, grid, dim3(nthreads), lds, st, args...);
-  PINGS_LAUNCH_CHECK();
-  return PINGS_OK;
 }
 
 // ---------------------------------------------------------------- grids

@@ -405,15 +405,15 @@ __global__ __launch_bounds__(256, 1) void mlp_dbl_wave_h64o1_kernel(long long N,
 template <typename F>
 int with_h64o1_class(const Plan& p, F&& f) {
   using std::integral_constant;
-  if (p.h64_ib == 1) return with_class<6, 16>(p.h64_ns, [&](auto ns) { return f(ns, integral_constant<int, 1>{}); });
-  return with_class<18, 32>(p.h64_ns, [&](auto ns) { return f(ns, integral_constant<int, 2>{}); });
+  if (p.h64_ib == 1) return with_class<6, 16>(p.h64_ns, "decoder MLP", [&](auto ns) { return f(ns, integral_constant<int, 1>{}); });
+  return with_class<18, 32>(p.h64_ns, "decoder MLP", [&](auto ns) { return f(ns, integral_constant<int, 2>{}); });
 }
 
 }  // namespace
 
 int launch_fwd_h64o1(const Plan& p, int grid, hipStream_t st, long long N, int IN, const float* x, const float* W1,
                      const float* b1, const float* W2, const float* b2, float* y) {
-  return with_class<6, 10, 18>(p.fwd_ks, [&](auto ks) {
+  return with_class<6, 10, 18>(p.fwd_ks, "decoder MLP", [&](auto ks) {
     return launch(mlp_fwd_h64o1_kernel<ks()>, dim3(grid), 256, 0, st, N, IN, x, W1, b1, W2, b2, y);
   });
 }

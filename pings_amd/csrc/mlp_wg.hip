@@ -317,7 +317,7 @@ int launch_wg(void (*kernel)(KA...), int grid, size_t lds, hipStream_t st, const
 
 int launch_fwd_wg(const Plan& p, int grid, hipStream_t st, const Dims& d, const float* x, const float* W1,
                   const float* b1, const float* W2, const float* b2, float* y) {
-  return with_class<5, 10, 18, 32>(p.fwd_pfx, [&](auto px) {
+  return with_class<5, 10, 18, 32>(p.fwd_pfx, "decoder MLP", [&](auto px) {
     return launch_wg(mlp_fwd_kernel<px()>, grid, fwd_lds_bytes(d), st, d, x, W1, b1, W2, b2, y);
   });
 }
@@ -329,10 +329,10 @@ int launch_bwd_wg(const Plan& p, int grid, hipStream_t st, const Dims& d, const 
   };
   using std::integral_constant;   // the <PF_X, PF_G> classes that exist: PF_G follows the thread count (mlp_plan)
   switch (p.bwd_pfg) {
-    case 4: return with_class<5, 9>(p.bwd_pfx, [&](auto px) { return launch(px, integral_constant<int, 4>{}); });
-    case 6: return with_class<6, 11>(p.bwd_pfx, [&](auto px) { return launch(px, integral_constant<int, 6>{}); });
-    case 8: return with_class<9, 16>(p.bwd_pfx, [&](auto px) { return launch(px, integral_constant<int, 8>{}); });
-    default: return with_class<18, 32>(p.bwd_pfx, [&](auto px) { return launch(px, integral_constant<int, 16>{}); });
+    case 4: return with_class<5, 9>(p.bwd_pfx, "decoder MLP", [&](auto px) { return launch(px, integral_constant<int, 4>{}); });
+    case 6: return with_class<6, 11>(p.bwd_pfx, "decoder MLP", [&](auto px) { return launch(px, integral_constant<int, 6>{}); });
+    case 8: return with_class<9, 16>(p.bwd_pfx, "decoder MLP", [&](auto px) { return launch(px, integral_constant<int, 8>{}); });
+    default: return with_class<18, 32>(p.bwd_pfx, "decoder MLP", [&](auto px) { return launch(px, integral_constant<int, 16>{}); });
   }
 }
 

@@ -19,7 +19,7 @@
 // With upstream gn_j (w.r.t. n_j) and gw_j (w.r.t. w_j):  gx = sum_j R_j gn_j + sum_j gu_j (-2 u_j^2) e_j,
 // gu_j = (gw_j - sum_i gw_i w_i) / s.  The second order terms are the directional derivatives of these along gg_x.
 // Squared distances use ((x*x + y*y) + z*z) without FMA like the search, so weights are those of the forward bit for bit.
-#include "knn_common.hpp"
+#include "knn_host.hpp"
 #include "row_scatter.hpp"
 
 namespace {
@@ -411,7 +411,7 @@ PINGS_API int pings_query_feature_forward(const pings_knn_map* m, const pings_qf
   PINGS_ARG_CHECK(B > 0 && queries && w_out && idx_out && gidx_out && nn_counts, "null pointer");
   hipStream_t st = pings::as_stream(stream);
   pings::prof::Scope ps("qf_forward", st);
-  hipLaunchKernelGGL(qf_forward_kernel, dim3(grid_for(B)), dim3(64 * WAVES_PER_BLOCK), 0, st, *m, *t, queries,
+  hipLaunchKernelGGL(qf_forward_kernel, dim3(capped_grid(B)), dim3(64 * WAVES_PER_BLOCK), 0, st, *m, *t, queries,
                      (long long)B, geo_out, color_out, w_out, (long long*)idx_out, (long long*)gidx_out,
                      (long long*)nn_counts, certainty, certainty_accum, (const int*)query_ts, (int*)ts_update,
                      n_out);

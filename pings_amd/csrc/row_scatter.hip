@@ -1,8 +1,6 @@
 // Deterministic scatter-add of rows (see row_scatter.hpp): counting sort by destination row + one gather pass.
 #include <hipcub/hipcub.hpp>
 
-#include <cstdlib>
-
 #include "row_scatter.hpp"
 
 namespace pings_rows {
@@ -175,44 +173,20 @@ int gather_sum(const Plan& p, int64_t rows, int F, const float* src, int64_t ld,
   const int groups = (F + 3) / 4;
   int G = 1;
   while (G < groups) G <<= 1;
-  static const int force = [] {   // PINGS_ROWS_GATHER=table|buckets (A/B runs)
-    const char* e = getenv("PINGS_ROWS_GATHER");
-    return !e ? 0 : (e[0] == 't' ? 1 : 2);
-  }();
-  if ((force == 2 || (force == 0 && 4 * p.n < rows)) && p.n >= 0) {   // measured: 98k pairs / 1M rows 37 -> 30 us, 786k pairs 109 -> 112 us
+  if (4 * p.n < rows && p.n >= 0) {   // measured: 98k pairs / 1M rows 37 -> 30 us, 786k pairs 109 -> 112 us
     PINGS_HIP_CHECK(hipMemsetAsync(out, 0, sizeof(float) * (size_t)rows * F, st));
     if (p.n == 0) return PINGS_OK;
-    const long long bt = (long long)p.n * G;
-    const unsigned bgrid = (unsigned)((bt + 255) / 256);
-#define PINGS_GB(GG)                                                                                                 \
-  hipLaunchKernelGGL(gather_bucket_kernel<GG>, dim3(bgrid), dim3(256), 0, st, p.offset, sorted, p.first, (long long)p.n, \
-                     F, src, (long long)ld, src_row, w, out)
-    switch (G) {
-      case 1: PINGS_GB(1); break;
-      case 2: PINGS_GB(2); break;
-      case 4: PINGS_GB(4); break;
-      case 8: PINGS_GB(8); break;
-      default: PINGS_GB(16); break;
-    }
-#undef PINGS_GB
-    PINGS_LAUNCH_CHECK();
-    return PINGS_OK;
+    const unsigned bgrid = (unsigned)(((long long)p.n * G + 255) / 256);
+    return pings::with_class<1, 2, 4, 8, 16>(G, "row gather over the buckets", [&](auto g) {
+      return pings::launch(gather_bucket_kernel<g()>, dim3(bgrid), 256, 0, st, p.offset, sorted, p.first,
+                           (long long)p.n, F, src, (long long)ld, src_row, w, out);
+    });
   }
-  const long long threads = (long long)rows * G;
-  const unsigned grid = (unsigned)((threads + 255) / 256);
-#define PINGS_GS(GG)                                                                                              \
-  hipLaunchKernelGGL(gather_sum_kernel<GG>, dim3(grid), dim3(256), 0, st, p.offset, sorted, (long long)rows, F, src, \
-                     (long long)ld, src_row, w, out)
-  switch (G) {
-    case 1: PINGS_GS(1); break;
-    case 2: PINGS_GS(2); break;
-    case 4: PINGS_GS(4); break;
-    case 8: PINGS_GS(8); break;
-    default: PINGS_GS(16); break;
-  }
-#undef PINGS_GS
-  PINGS_LAUNCH_CHECK();
-  return PINGS_OK;
+  const unsigned grid = (unsigned)(((long long)rows * G + 255) / 256);
+  return pings::with_class<1, 2, 4, 8, 16>(G, "row gather over the table", [&](auto g) {
+    return pings::launch(gather_sum_kernel<g()>, dim3(grid), 256, 0, st, p.offset, sorted, (long long)rows, F, src,
+                         (long long)ld, src_row, w, out);
+  });
 }
 }  // namespace pings_rows
 

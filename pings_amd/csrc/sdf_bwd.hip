@@ -27,9 +27,8 @@
 // the [B k, F+3] input rows and their gradients materialised in HBM and three more launches.
 // Bitwise reproducible: no float atomics, fixed summation orders.
 #include <algorithm>
-#include <string>
-#include "knn_common.hpp"
 #include "row_scatter.hpp"
+#include "sdf_plan.hpp"
 
 namespace {
 using namespace pings_knn;
@@ -546,14 +545,6 @@ __global__ __launch_bounds__(64 * WPB, IN_PAD > 32 ? 2 : 3) void sdf_grad_mfma_k
   }
 }
 
-bool grad_mfma_supported(bool second, const pings_sdf_decoder* dec, int nn_k, const float* features, const float* rows) {
-  const int F = dec->feat_dim, F4 = F >> 2;
-  const char* e = getenv("PINGS_SDF_BWD");
-  if (e && std::string(e) == "vector") return false;
-  return !second && !dec->weighted_first && nn_k <= GNB && (F & 3) == 0 && F4 > 0 && (F4 & (F4 - 1)) == 0 && F <= 32 &&
-         dec->hidden <= 64 && ((reinterpret_cast<uintptr_t>(features) | reinterpret_cast<uintptr_t>(rows)) & 15u) == 0;
-}
-
 // out[e] = sum over the per-workgroup partials, one wave per output element: lane l adds partials l, l + 64, ... in
 // order (independent loads, all in flight), the wave then adds its 64 lane sums in a fixed tree: the same bits every
 // run.  dW1 [H, IN] | db1 [H] | dW2 [H] | db2 [1]
@@ -621,20 +612,8 @@ int run(bool second, const pings_sdf_decoder* dec, const float* features, int64_
   hipStream_t st = pings::as_stream(stream);
   const int F = dec->feat_dim, H = dec->hidden, IN = F + 3;
   Scratch s = carve(scratch, B, nn_k, F, H, feature_rows);
-  // one resident round (knn_common.hpp grid_for); grad_blocks(B) is what the scratch was sized for
-  const bool mfma = grad_mfma_supported(second, dec, nn_k, features, s.rows);
-  const int need = F + 4;
-  const void* kfn = nullptr;
-  if (mfma) {
-    kfn = need <= 12 ? (const void*)sdf_grad_mfma_kernel<12>
-                     : (need <= 20 ? (const void*)sdf_grad_mfma_kernel<20> : (const void*)sdf_grad_mfma_kernel<36>);
-  } else if (IN <= 12) kfn = second ? (const void*)sdf_grad_kernel<12, true> : (const void*)sdf_grad_kernel<12, false>;
-  else if (IN <= 20) kfn = second ? (const void*)sdf_grad_kernel<20, true> : (const void*)sdf_grad_kernel<20, false>;
-  else if (IN <= 36) kfn = second ? (const void*)sdf_grad_kernel<36, true> : (const void*)sdf_grad_kernel<36, false>;
-  else kfn = second ? (const void*)sdf_grad_kernel<64, true> : (const void*)sdf_grad_kernel<64, false>;
-  const long long work = mfma ? (B + GQ - 1) / GQ : B;   // wave-steps: four queries each on the matrix-core kernel
-  int nblocks = std::max(1, std::min(grad_blocks(B), (int)grid_for(work > 0 ? work : 1, kfn)));
-  if (const char* e = getenv("PINGS_SDF_GRAD_BLOCKS")) nblocks = std::max(1, std::min(nblocks, atoi(e)));   // A/B runs
+  const SdfPlan p = sdf_plan(nn_k, F, H, dec->weighted_first != 0, second ? SDF_DOUBLE_BACKWARD : SDF_BACKWARD,
+                             misaligned16(features, s.rows));
   const int PSZ = H * (IN + 2) + 1;
   GradArgs a;
   a.W1 = dec->W1; a.b1 = dec->b1; a.W2 = dec->W2;
@@ -647,25 +626,24 @@ int run(bool second, const pings_sdf_decoder* dec, const float* features, int64_
   a.table_rows = feature_rows; a.partials = s.partials;
   {
     pings::prof::Scope ps(second ? "sdf_bwd2_grad" : "sdf_bwd_grad", st);
-    if (B == 0) PINGS_HIP_CHECK(hipMemsetAsync(s.partials, 0, sizeof(float) * (size_t)nblocks * PSZ, st));
-#define PINGS_SDF_GRAD(PAD)                                                                                   \
-  do {                                                                                                       \
-    if (second) hipLaunchKernelGGL((sdf_grad_kernel<PAD, true>), dim3(nblocks), dim3(64 * WPB), 0, st, a);    \
-    else hipLaunchKernelGGL((sdf_grad_kernel<PAD, false>), dim3(nblocks), dim3(64 * WPB), 0, st, a);         \
-  } while (0)
-    if (B > 0 && mfma) {
-      if (need <= 12) hipLaunchKernelGGL(sdf_grad_mfma_kernel<12>, dim3(nblocks), dim3(64 * WPB), 0, st, a);
-      else if (need <= 20) hipLaunchKernelGGL(sdf_grad_mfma_kernel<20>, dim3(nblocks), dim3(64 * WPB), 0, st, a);
-      else hipLaunchKernelGGL(sdf_grad_mfma_kernel<36>, dim3(nblocks), dim3(64 * WPB), 0, st, a);
-      PINGS_LAUNCH_CHECK();
-    } else if (B > 0) {
-      if (IN <= 12) PINGS_SDF_GRAD(12);
-      else if (IN <= 20) PINGS_SDF_GRAD(20);
-      else if (IN <= 36) PINGS_SDF_GRAD(36);
-      else PINGS_SDF_GRAD(64);
-      PINGS_LAUNCH_CHECK();
-    }
-#undef PINGS_SDF_GRAD
+    // the planned kernel: one resident round of it (knn_host.hpp), at most the grad_blocks(B) the scratch was sized for
+    const long long work = p.family == SDF_MATRIX_CORE ? (B + GQ - 1) / GQ : B;   // wave steps: four queries each there
+    int nblocks = 1;
+    auto go = [&](auto kernel) -> int {
+      nblocks = std::max(1, std::min(grad_blocks(B), (int)resident_grid(work > 0 ? work : 1, (const void*)kernel)));
+      if (B > 0) return pings::launch(kernel, dim3(nblocks), 64 * WPB, 0, st, a);
+      PINGS_HIP_CHECK(hipMemsetAsync(s.partials, 0, sizeof(float) * (size_t)nblocks * PSZ, st));
+      return PINGS_OK;
+    };
+    const int e = p.family == SDF_MATRIX_CORE
+        ? pings::with_class<12, 20, 36>(p.in_pad, "SDF backward, matrix core",
+                                        [&](auto pad) { return go(sdf_grad_mfma_kernel<pad()>); })
+        : pings::with_class<12, 20, 36, 64>(p.in_pad, "SDF backward", [&](auto pad) {
+            return pings::with_flag(second, [&](auto so) {
+              return go(sdf_grad_kernel<decltype(pad)::value, decltype(so)::value>);
+            });
+          });
+    if (e) return e;
     hipLaunchKernelGGL(sdf_param_reduce_kernel, dim3((PSZ + 3) / 4), dim3(256), 0, st, s.partials, nblocks, PSZ,
                        dW1, db1, dW2, db2, H, IN);
     PINGS_LAUNCH_CHECK();

@@ -17,7 +17,7 @@
 //       layer and the three direction-input gradient sums are 4-5 vector ops per register, then one half-swap add.
 // Everything after that — IDW weights, the weighted prediction, its spread, the analytic gradient through the direction
 // input and through the weights — is lane-parallel over the 32 columns with 8-lane group sums (3 DPP adds).
-#include "knn_common.hpp"
+#include "sdf_plan.hpp"
 
 namespace {
 using namespace pings_knn;
@@ -42,7 +42,7 @@ struct XLayout {
 };
 
 template <int IN_PAD, bool GRAD>
-__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, IN_PAD > 36 ? 2 : 4) void sdf_forward_mfma_kernel(
+__global__ __launch_bounds__(64 * WAVES_PER_BLOCK, 4) void sdf_forward_mfma_kernel(
     pings_knn_map m, pings_sdf_decoder dec, const float* __restrict__ features,
     const float* __restrict__ points, const float* __restrict__ orientations,
     const float* __restrict__ certainties, int after_pgo, const float* __restrict__ queries,
@@ -285,35 +285,21 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK, IN_PAD > 36 ? 2 : 4) void sdf
 
 namespace pings_knn {
 
-bool sdf_forward_mfma_supported(const pings_knn_map* m, const pings_sdf_decoder* dec, const float* features) {
-  const int F = dec->feat_dim;
-  const int F4 = F >> 2;
-  return !dec->weighted_first && m->nn_k <= NBR && (F & 3) == 0 && F4 > 0 && (F4 & (F4 - 1)) == 0 &&
-         F + 4 <= 64 && dec->hidden <= 64 && ((reinterpret_cast<uintptr_t>(features) & 15u) == 0);
-}
-
-int sdf_forward_mfma_launch(const pings_knn_map* m, const pings_sdf_decoder* dec, const float* features,
+int sdf_forward_mfma_launch(int in_pad, const pings_knn_map* m, const pings_sdf_decoder* dec, const float* features,
                             const float* points, const float* orientations, const float* certainties,
                             int32_t after_pgo, const float* queries, int64_t B, float* sdf, float* grad_x,
                             int64_t* nn_counts, float* certainty, int64_t* idx_out, float* w_out, float* sdf_std,
                             int64_t* gidx_out, hipStream_t st) {
-  const int need = dec->feat_dim + 4;   // inputs + the bias column
-  const long long groups = (B + QPW - 1) / QPW;
-#define PINGS_SDF_MFMA_G(PAD, G)                                                                                     \
-  hipLaunchKernelGGL((sdf_forward_mfma_kernel<PAD, G>),                                                              \
-                     dim3(grid_for(groups, (const void*)sdf_forward_mfma_kernel<PAD, G>)),                           \
-                     dim3(64 * WAVES_PER_BLOCK), 0, st, *m, *dec, features, points, orientations, certainties,       \
-                     (int)after_pgo, queries, (long long)B, sdf, grad_x, (long long*)nn_counts, certainty,           \
-                     (long long*)idx_out, w_out, sdf_std, (long long*)gidx_out)
-#define PINGS_SDF_MFMA(PAD) do { if (grad_x) PINGS_SDF_MFMA_G(PAD, true); else PINGS_SDF_MFMA_G(PAD, false); } while (0)
-  if (need <= 12) PINGS_SDF_MFMA(12);
-  else if (need <= 20) PINGS_SDF_MFMA(20);
-  else if (need <= 36) PINGS_SDF_MFMA(36);
-  else PINGS_SDF_MFMA(64);
-#undef PINGS_SDF_MFMA
-#undef PINGS_SDF_MFMA_G
-  PINGS_LAUNCH_CHECK();
-  return PINGS_OK;
+  const long long groups = (B + QPW - 1) / QPW;   // wave steps
+  return pings::with_class<12, 20, 36>(in_pad, "SDF forward, matrix core", [&](auto pad) {
+    return pings::with_flag(grad_x != nullptr, [&](auto grad) {
+      const auto kernel = sdf_forward_mfma_kernel<decltype(pad)::value, decltype(grad)::value>;
+      return pings::launch(kernel, dim3(resident_grid(groups, (const void*)kernel)), 64 * WAVES_PER_BLOCK, 0, st, *m,
+                           *dec, features, points, orientations, certainties, (int)after_pgo, queries, (long long)B,
+                           sdf, grad_x, (long long*)nn_counts, certainty, (long long*)idx_out, w_out, sdf_std,
+                           (long long*)gidx_out);
+    });
+  });
 }
 
 }  // namespace pings_knn

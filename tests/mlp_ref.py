@@ -250,3 +250,16 @@ def built_classes(csrc=CSRC):
     return {"wg_fwd": lists.get("fwd_pfx", set()), "wg_bwd": lists.get("bwd_pfx", set()),
             "h64o1_fwd": lists.get("fwd_ks", set()), "h64o1_bwd": lists.get("h64_ns", set()),
             "wave128_bwd": {(oh, vx, vg) for oh, vg in bodies for vx in vxs}}
+
+
+_WITH_CLASS_WHAT = re.compile(r'with_class<([\d,\s]+)>\(\s*[\w.]+,\s*"([^"]+)"')
+
+
+def with_class_lists(*names, csrc=CSRC):
+    """{what: classes} of every `with_class<...>(v, "what", ...)` call in the named kernel files, keyed by the string
+    the call names itself with (the fused SDF query's four launches; the decoder MLP's all say "decoder MLP")."""
+    out = {}
+    for name in names:
+        for vals, what in _WITH_CLASS_WHAT.findall((csrc / name).read_text()):
+            out.setdefault(what, set()).update(int(v) for v in vals.split(","))
+    return out

@@ -1,12 +1,29 @@
 """Neural-point SDF query: oracle vs the reference's golden vectors (CPU), HIP vs oracle (GPU)."""
+import ctypes
+import itertools
+
 import numpy as np
 import pytest
 import torch
 
+import mlp_ref
 from conftest import rel_err
 from oracle import sdf_cpu
 
 CASES = ["gs_f32", "pin_f8", "pgo_f32"]
+
+# pings_sdf_plan (csrc/sdf_plan.hpp): kernel family, order of differentiation
+VECTOR, MATRIX = 0, 1
+FWD, BWD, BWD2 = 0, 1, 2
+
+
+def _plan(nn_k, F, H, weighted_first=False, order=FWD, misaligned=False):
+    """(family, IN_PAD class) of the kernel the library runs for this shape and order; needs no GPU."""
+    from pings_amd import _lib
+
+    out = (ctypes.c_int32 * 2)()
+    assert _lib.lib().pings_sdf_plan(nn_k, F, H, int(weighted_first), order, int(misaligned), out) == 0
+    return out[0], out[1]
 
 
 def load(golden_dir, name):
@@ -228,9 +245,17 @@ def test_hip_fused_sdf_vector_and_matrix_core_kernels_agree(golden_dir, name, mo
     gpu = _gpu_map(st)
     x = T(st["x"]).cuda()
     dec = _Dec(st)
+    # the comparison means something only where the default plan is the matrix-core kernel: pin_f8 is weighted_first
+    # and plans the vector kernel either way
+    monkeypatch.delenv("PINGS_SDF_FWD", raising=False)
+    F, H = gpu.local_geo_features.shape[1], dec.layers[0].weight.shape[0]
+    assert gpu.local_geo_features.data_ptr() % 16 == 0
+    want = {"gs_f32": (MATRIX, 36), "pin_f8": (VECTOR, 12), "pgo_f32": (MATRIX, 36)}[name]
+    assert _plan(gpu.nn_k, F, H, gpu.weighted_first, FWD) == want
     out = {}
     for mode in ("mfma", "vector"):
         monkeypatch.setenv("PINGS_SDF_FWD", mode)
+        assert _plan(gpu.nn_k, F, H, gpu.weighted_first, FWD)[0] == (want[0] if mode == "mfma" else VECTOR)
         out[mode] = hnp.sdf_fused(gpu, dec, x, need_grad=True, need_certainty=True, need_std=True)
     for a, b in zip(out["mfma"], out["vector"]):
         if a.dtype == torch.int64:
@@ -859,6 +884,10 @@ def test_matrix_core_sdf_kernels_other_decoder_shapes(F, H, nn_k, monkeypatch):
     for mode in ("mfma", "vector"):
         monkeypatch.setenv("PINGS_SDF_FWD", mode)
         monkeypatch.setenv("PINGS_SDF_BWD", mode)
+        # the default plan of these shapes is the matrix-core family: the two runs are two different kernels
+        assert gpu.local_geo_features.data_ptr() % 16 == 0
+        for order in (FWD, BWD):
+            assert _plan(nn_k, F, H, False, order)[0] == (MATRIX if mode == "mfma" else VECTOR)
         out = hnp.sdf_fused(gpu, _Dec({**dec}), x.cuda(), need_grad=True, need_std=True,
                             use_only_measured_points=False)
         feats = gpu.local_geo_features.detach().clone().requires_grad_(True)
@@ -885,3 +914,193 @@ def test_matrix_core_sdf_kernels_other_decoder_shapes(F, H, nn_k, monkeypatch):
         s_small, _, cnt_small, _ = hnp.sdf_fused(gpu, _Dec({**dec}), x[:nb].cuda(), use_only_measured_points=False)
         assert torch.equal(s_small, res["mfma"][0][0][:nb]) and rel_err(s_small, ref_s[:nb]) <= 2e-5
         assert torch.equal(cnt_small, res["mfma"][0][2][:nb])
+
+
+# ------------------------------------------------------------------ the launch plan of the fused query (csrc/sdf_plan.hpp)
+def _expected_plan(nn_k, F, H, weighted_first, order, misaligned):
+    """The plan as DESIGN states it: matrix core for the per-neighbour decoder with nn_k <= 8 and 4, 8, 16 or 32 aligned
+    features, forward and first-order backward only; classes by padded input width."""
+    if order != BWD2 and not weighted_first and not misaligned and nn_k <= 8 and H <= 64 and F in (4, 8, 16, 32):
+        need = F + 4
+        return MATRIX, 12 if need <= 12 else 20 if need <= 20 else 36
+    n = F + 3
+    if order == FWD:
+        return VECTOR, 12 if n <= 12 else 36 if n <= 36 else 64
+    return VECTOR, 12 if n <= 12 else 20 if n <= 20 else 36 if n <= 36 else 64
+
+
+@pytest.mark.parametrize("F,fwd,bwd,bwd2", [
+    (9, (VECTOR, 12), (VECTOR, 12), (VECTOR, 12)), (10, (VECTOR, 36), (VECTOR, 20), (VECTOR, 20)),
+    (17, (VECTOR, 36), (VECTOR, 20), (VECTOR, 20)), (18, (VECTOR, 36), (VECTOR, 36), (VECTOR, 36)),
+    (33, (VECTOR, 36), (VECTOR, 36), (VECTOR, 36)), (34, (VECTOR, 64), (VECTOR, 64), (VECTOR, 64)),
+    (61, (VECTOR, 64), (VECTOR, 64), (VECTOR, 64)),
+    (4, (MATRIX, 12), (MATRIX, 12), (VECTOR, 12)), (8, (MATRIX, 12), (MATRIX, 12), (VECTOR, 12)),
+    (16, (MATRIX, 20), (MATRIX, 20), (VECTOR, 20)), (32, (MATRIX, 36), (MATRIX, 36), (VECTOR, 36)),
+    (12, (VECTOR, 36), (VECTOR, 20), (VECTOR, 20)),          # F / 4 = 3 is not a power of two
+])
+def test_sdf_plan_at_both_sides_of_every_threshold(F, fwd, bwd, bwd2, monkeypatch):
+    monkeypatch.delenv("PINGS_SDF_FWD", raising=False)
+    monkeypatch.delenv("PINGS_SDF_BWD", raising=False)
+    assert [_plan(6, F, 64, False, o) for o in (FWD, BWD, BWD2)] == [fwd, bwd, bwd2]
+    vec = [(VECTOR, c) for c in (_expected_plan(6, F, 64, True, o, False)[1] for o in (FWD, BWD, BWD2))]
+    assert vec[2] == bwd2                                      # the second order is always the vector kernel
+    assert [_plan(8, F, 64, False, o) for o in (FWD, BWD, BWD2)] == [fwd, bwd, bwd2]     # nn_k 8 | 9
+    assert [_plan(9, F, 64, False, o) for o in (FWD, BWD, BWD2)] == vec
+    assert [_plan(6, F, 64, True, o) for o in (FWD, BWD, BWD2)] == vec                   # weighted_first
+    assert [_plan(6, F, 64, False, o, misaligned=True) for o in (FWD, BWD, BWD2)] == vec
+    assert [_plan(6, F, 1, False, o) for o in (FWD, BWD, BWD2)] == [fwd, bwd, bwd2]      # hidden 1 .. 64 alike
+    monkeypatch.setenv("PINGS_SDF_FWD", "vector")
+    assert [_plan(6, F, 64, False, o) for o in (FWD, BWD, BWD2)] == [vec[0], bwd, bwd2]
+    monkeypatch.setenv("PINGS_SDF_BWD", "vector")
+    assert [_plan(6, F, 64, False, o) for o in (FWD, BWD, BWD2)] == vec
+    monkeypatch.setenv("PINGS_SDF_FWD", "mfma")
+    assert [_plan(6, F, 64, False, o) for o in (FWD, BWD, BWD2)] == [fwd, vec[1], vec[2]]
+
+
+def test_sdf_plan_refuses_shapes_the_kernels_do_not_take():
+    from pings_amd import _lib
+
+    L, out = _lib.lib(), (ctypes.c_int32 * 2)()
+    assert _plan(6, 32, 64) == (MATRIX, 36)                    # feat_dim 32 forward: class 36, never 64
+    for nn_k, F, H, order in [(0, 32, 64, 0), (17, 32, 64, 0), (6, 0, 64, 0), (6, 62, 64, 0), (6, 32, 0, 0),
+                              (6, 32, 65, 0), (6, 32, 64, 3), (6, 32, 64, -1)]:
+        assert L.pings_sdf_plan(nn_k, F, H, 0, order, 0, out) == 1, (nn_k, F, H, order)
+    assert L.pings_sdf_plan(6, 32, 64, 0, 0, 0, None) == 1
+
+
+def _reachable_sdf_classes():
+    """{(order, family): classes} of `pings_sdf_plan` swept over every admitted shape, each plan also checked against
+    `_expected_plan`."""
+    got = {}
+    for F, nn_k, wf, mis, order, H in itertools.product(range(1, 62), range(1, 17), (False, True), (False, True),
+                                                        (FWD, BWD, BWD2), (1, 37, 64)):
+        fam, cls = _plan(nn_k, F, H, wf, order, mis)
+        assert (fam, cls) == _expected_plan(nn_k, F, H, wf, order, mis), (nn_k, F, H, wf, order, mis)
+        got.setdefault((order, fam), set()).add(cls)
+    return got
+
+
+def test_sdf_classes_built_are_the_classes_the_plan_can_return(monkeypatch):
+    """The `with_class<...>` lists of the four SDF launches against the plan swept over every admitted shape: a class
+    nobody can ask for fails, and so does a class asked for and not built."""
+    monkeypatch.delenv("PINGS_SDF_FWD", raising=False)
+    monkeypatch.delenv("PINGS_SDF_BWD", raising=False)
+    built = mlp_ref.with_class_lists("knn_sdf.hip", "sdf_fwd_mfma.hip", "sdf_bwd.hip")
+    assert sorted(built) == ["SDF backward", "SDF backward, matrix core", "SDF forward", "SDF forward, matrix core"]
+    want = _reachable_sdf_classes()
+    assert (BWD2, MATRIX) not in want                          # the second order has no matrix-core kernel
+    assert want[(BWD, VECTOR)] == want[(BWD2, VECTOR)]         # one list, two instantiations (SECOND)
+    assert built == {"SDF forward": want[(FWD, VECTOR)], "SDF forward, matrix core": want[(FWD, MATRIX)],
+                     "SDF backward": want[(BWD, VECTOR)], "SDF backward, matrix core": want[(BWD, MATRIX)]}
+    # and the GPU test below runs every one of them
+    ran = {}
+    for fam, F, H, nn_k, wf in PLAN_CASES:
+        for order in (FWD, BWD, BWD2):
+            for forced in ((False, True) if fam == MATRIX else (False,)):
+                f, c = _expected_plan(nn_k, F, H, wf or forced, order, False)
+                ran.setdefault((order, f), set()).add(c)
+    assert ran == want
+
+
+PLAN_CASES = [(VECTOR, 9, 64, 6, False), (VECTOR, 10, 33, 9, False), (VECTOR, 17, 64, 6, False),
+              (VECTOR, 18, 64, 6, False), (VECTOR, 33, 64, 6, False), (VECTOR, 34, 17, 16, False),
+              (VECTOR, 61, 64, 6, False), (VECTOR, 32, 64, 6, True),
+              (MATRIX, 4, 16, 3, False), (MATRIX, 8, 32, 6, False), (MATRIX, 16, 64, 8, False),
+              (MATRIX, 32, 48, 6, False)]
+
+
+def _plan_case(F, H, nn_k, weighted_first):
+    """Map, decoder, queries and the oracle's answers for one shape: forward (sdf, dS/dx, spread, counts), first-order
+    gradients of sum(s * gw) and second-order gradients of the Eikonal loss w.r.t. (features, W1, b1, W2, b2).
+
+    6,000 points.  The stock queries sit on the sheet and nearly all have MORE than nn_k candidates, so every third one
+    is lifted off the sheet by 0.3 .. 1.3 (the search radius): their candidate counts run from many down to none, which
+    gives every case queries with exactly nn_k candidates, with fewer, and with none."""
+    st, dec = sdf_cpu.synthetic_map(6000, feat_dim=F, hidden=H, nn_k=nn_k, weighted_first=weighted_first, seed=F + H)
+    x = sdf_cpu.synthetic_queries(st, 1501)          # not a multiple of four: the last wave step is ragged
+    x[::3, 2] += torch.linspace(0.3, 1.3, x[::3].shape[0])
+    cpu, d = sdf_cpu.NeuralPointMap({**st}), sdf_cpu.MLP.from_state({**dec})
+    P = [cpu.local_geo_features] + d.parameters()
+    for p in P:
+        p.requires_grad_(True)
+    xg = x.clone().requires_grad_(True)
+    geo, _, w, cnt, _ = cpu.query_feature(xg, accumulate_stability=False)
+    s = d.sdf(geo)
+    std = torch.zeros_like(x[:, 0])
+    if not weighted_first:
+        std = torch.sqrt(torch.sum(w * (s - torch.sum(s * w, dim=1, keepdim=True)) ** 2, dim=1)).squeeze(1).detach()
+        s = torch.sum(s * w, dim=1).squeeze(1)
+    gw = torch.randn(x.shape[0], generator=torch.Generator().manual_seed(1))
+    first = torch.autograd.grad((s * gw).sum(), P, retain_graph=True)
+    g = sdf_cpu.get_gradient(xg, s)
+    second = torch.autograd.grad(((g.norm(dim=-1) - 1.0) ** 2).mean() + s.abs().mean(), P)
+    return st, dec, x, gw, dict(sdf=s.detach(), grad=g.detach(), std=std, cnt=cnt, first=first, second=second)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("family,F,H,nn_k,weighted_first", PLAN_CASES,
+                         ids=[f"{'matrix' if c[0] else 'vector'}-F{c[1]}-H{c[2]}-k{c[3]}{'-wf' if c[4] else ''}"
+                              for c in PLAN_CASES])
+def test_every_sdf_kernel_class_against_the_oracle(family, F, H, nn_k, weighted_first, monkeypatch):
+    """Every (family, class, order) `pings_sdf_plan` can return, on the shape at the edge of its class: forward with
+    dS/dx and the spread, first-order training gradients, and the Eikonal loss's second-order pass, each against the
+    oracle (1e-4) and, where the shape has a matrix-core kernel, against the vector kernel (2e-5 forward, 5e-5
+    gradients; integer outputs equal).  Each run first asserts the kernel it claims to run."""
+    from types import SimpleNamespace as NS
+
+    from pings_amd import mapper_ops
+    from pings_amd import neural_points as hnp
+
+    st, dec, x, gw, ref = _plan_case(F, H, nn_k, weighted_first)
+    assert (ref["cnt"] == nn_k).any() and ((ref["cnt"] > 0) & (ref["cnt"] < nn_k)).any()
+    gpu = _gpu_map({**st})
+    xc, gwc = x.cuda(), gw.cuda()
+    names = ["features", "W1", "b1", "W2", "b2"]
+    res, errs = {}, {}
+    for mode in (("mfma", "vector") if family == MATRIX else ("mfma",)):
+        monkeypatch.setenv("PINGS_SDF_FWD", mode)
+        monkeypatch.setenv("PINGS_SDF_BWD", mode)
+        fam = family if mode == "mfma" else VECTOR
+        assert gpu.local_geo_features.data_ptr() % 16 == 0
+        for order in (FWD, BWD, BWD2):
+            assert _plan(nn_k, F, H, weighted_first, order) == \
+                _expected_plan(nn_k, F, H, weighted_first or fam == VECTOR, order, False)
+            assert _plan(nn_k, F, H, weighted_first, order)[0] == (fam if order != BWD2 else VECTOR)
+        out = hnp.sdf_fused(gpu, _Dec({**dec}), xc, need_grad=True, need_std=True)
+        feats = gpu.local_geo_features.detach().clone().requires_grad_(True)
+        gpu.local_geo_features = feats
+        P = [torch.nn.Parameter(torch.as_tensor(dec["dec." + k]).cuda().clone()) for k in
+             ("layers.0.weight", "layers.0.bias", "lout.weight", "lout.bias")]
+        d = NS(layers=[NS(weight=P[0], bias=P[1])], lout=NS(weight=P[2], bias=P[3]), sdf_scale=float(dec["sdf_scale"]),
+               use_leaky_relu=False)
+        s, _ = hnp.sdf_train(gpu, d, xc)
+        first = torch.autograd.grad((s * gwc).sum(), [feats] + P)
+        xg = xc.clone().requires_grad_(True)
+        s2, _, _ = mapper_ops.sdf(_FakeMapper(gpu, d), xg, min_nn_count=1)
+        g2 = sdf_cpu.get_gradient(xg, s2)
+        second = torch.autograd.grad(((g2.norm(dim=-1) - 1.0) ** 2).mean() + s2.abs().mean(), [feats] + P)
+        small = [hnp.sdf_fused(gpu, _Dec({**dec}), xc[:nb], need_grad=True, need_std=True) for nb in (1, 2, 3, 5)]
+        res[mode] = (out, s.detach(), first, second, small)
+        errs[mode] = dict(sdf=rel_err(out[0], ref["sdf"]), grad=rel_err(out[1], ref["grad"]),
+                          std=rel_err(out[4], ref["std"]) if not weighted_first else float(out[4].abs().max()),
+                          train_sdf=rel_err(s, ref["sdf"]), grad2_x=rel_err(g2, ref["grad"]),
+                          **{"d1_" + n: rel_err(a.reshape(b.shape), b) for n, a, b in zip(names, first, ref["first"])},
+                          **{"d2_" + n: rel_err(a.reshape(b.shape), b) for n, a, b in zip(names, second, ref["second"])})
+    if family == MATRIX:
+        a, b = res["mfma"], res["vector"]
+        errs["families"] = dict(sdf=rel_err(a[0][0], b[0][0]), grad=rel_err(a[0][1], b[0][1]),
+                                std=rel_err(a[0][4], b[0][4]), train_sdf=rel_err(a[1], b[1]),
+                                **{"d1_" + n: rel_err(u, v) for n, u, v in zip(names, a[2], b[2])})
+    print(f"F={F} H={H} nn_k={nn_k} weighted_first={weighted_first}: {errs}")
+    for mode, (out, _, _, _, small) in res.items():
+        assert torch.equal(out[2].cpu(), ref["cnt"])
+        assert all(v <= 1e-4 for v in errs[mode].values()), (mode, errs[mode])
+        # every fill level of the last four-query wave step: a query's result does not depend on its batch
+        for nb, sm in zip((1, 2, 3, 5), small):
+            for u, v in zip(sm, out):
+                assert u is None and v is None or torch.equal(u, v[:nb]), (mode, nb)
+    if family == MATRIX:
+        assert torch.equal(res["mfma"][0][2], res["vector"][0][2])
+        e = errs["families"]
+        assert max(e["sdf"], e["grad"], e["std"], e["train_sdf"]) <= 2e-5, e
+        assert all(e["d1_" + n] <= 5e-5 for n in names), e
