@@ -985,4 +985,39 @@ PINGS_API int pings_mc_emit(const float* vol, const uint8_t* mask, int64_t nx, i
                             int flags, const void* scratch, int64_t nv, int64_t nf, int64_t* keys, float* verts,
                             int64_t* faces, void* stream);
 
+/* ------------------------------------------------------ fused AdamW (csrc/optim.hip)
+ * One optimiser step of every tensor of every parameter group in ONE launch.  A job is one fp32
+ * tensor; its scalars are computed by the host in double and rounded to fp32 once, as torch's single-tensor AdamW
+ * rounds them when it hands Python floats to fp32 tensor ops (torch/optim/adam.py `_single_tensor_adam`), t being the
+ * tensor's OWN step count after this step:
+ *   decay = 1 - lr*wd, one_minus_beta1 = 1 - beta1, one_minus_beta2 = 1 - beta2 (NOT 1.0f - (float)beta: that differs
+ *   in the last bits of a number near 0.01), step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t).
+ * Per element, in torch's operation order, IEEE division and square root, no contraction, no atomics:
+ *   p *= decay;  m += (g - m)*one_minus_beta1;  v = v*beta2 + one_minus_beta2*g*g;
+ *   p -= step_size*m / (sqrt(v)/bc2_sqrt + eps)
+ * The job table travels by value as a kernel argument, PINGS_ADAMW_MAX_JOBS tensors per launch; more jobs are split
+ * into ceil(njobs / PINGS_ADAMW_MAX_JOBS) launches (a launch whose jobs are all empty is not made), and launches_out
+ * (HOST, may be NULL) receives the number made.  A workgroup takes (tensor, chunk) items of PINGS_ADAMW_CHUNK elements;
+ * a tensor whose four pointers are 16-byte aligned moves as 16-byte words, any other 4-byte aligned one as scalars.
+ * n == 0 jobs do nothing.  No copy, no allocation and no synchronisation: the call only enqueues on `stream`.
+ * p, m and v of one job must not overlap each other, g, or another job's tensors. */
+#define PINGS_ADAMW_MAX_JOBS 48
+#define PINGS_ADAMW_CHUNK 4096
+typedef struct pings_adamw_job {
+  float* p;                      /* [n] parameter, updated in place                                               */
+  const float* g;                /* [n] gradient                                                                  */
+  float* m;                      /* [n] exp_avg, updated in place                                                 */
+  float* v;                      /* [n] exp_avg_sq, updated in place                                              */
+  int64_t n;
+  float decay;
+  float beta1;
+  float beta2;
+  float one_minus_beta1;
+  float one_minus_beta2;
+  float step_size;
+  float bc2_sqrt;
+  float eps;
+} pings_adamw_job;
+PINGS_API int pings_adamw_step(const pings_adamw_job* jobs, int njobs, int* launches_out, void* stream);
+
 #endif /* PINGS_HIP_H_ */

@@ -15,6 +15,7 @@ HEAD_COLOR, HEAD_SEMANTIC = 0, 1                                  # PINGS_HEAD_*
 REG_SINGULAR, REG_ILL_CONDITIONED, REG_NONFINITE = 1, 2, 4        # PINGS_REG_*: pings_reg_solve_checked status bits
 REG_F_NORMALS, REG_F_DIV_GRAD, REG_F_WEIGHTED = 1, 2, 4           # PINGS_REG_F_*: pings_reg_loop_args.flags
 MC_ALLOW_DEGENERATE, MC_ASCENT = 1, 2                             # PINGS_MC_*: pings_mc_count / pings_mc_emit flags
+ADAMW_MAX_JOBS, ADAMW_CHUNK = 48, 4096                            # PINGS_ADAMW_*: tensors per launch, elements per item
 
 vp = C.c_void_p     # device pointers and the hipStream_t travel as integers (tensor.data_ptr())
 i32, i64, f32, sz = C.c_int, C.c_int64, C.c_float, C.c_size_t
@@ -111,6 +112,12 @@ class SdfLossArgs(C.Structure):
                 ("flags", C.c_int32), ("sigma", C.c_float), ("eik_band", C.c_float), ("col_band", C.c_float)] + \
                [(n, vp) for n in ("coord", "label", "weight", "color_label", "w", "s", "c", "g", "idx", "xsel", "meta",
                                   "part", "sdf_pred", "losses", "counts", "gl", "g_pred", "d_s", "d_g", "d_c")]
+
+
+class AdamwJob(C.Structure):
+    _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", C.c_int64)] + \
+               [(n, C.c_float) for n in ("decay", "beta1", "beta2", "one_minus_beta1", "one_minus_beta2", "step_size",
+                                         "bc2_sqrt", "eps")]
 
 
 # ---------------------------------------------------------------- entry points: {name: (restype, argtypes)}
@@ -269,4 +276,6 @@ SIGNATURES = {
     "pings_mc_scratch_bytes": (sz, [i64, i64, i64]),
     "pings_mc_count": (i32, [vp, vp, i64, i64, i64, f32, i32, vp, C.POINTER(i64), vp]),
     "pings_mc_emit": (i32, [vp, vp, i64, i64, i64, f32, i32, vp, i64, i64, vp, vp, vp, vp]),
+    # fused AdamW
+    "pings_adamw_step": (i32, [C.POINTER(AdamwJob), i32, C.POINTER(i32), vp]),
 }
