@@ -1020,4 +1020,58 @@ typedef struct pings_adamw_job {
 } pings_adamw_job;
 PINGS_API int pings_adamw_step(const pings_adamw_job* jobs, int njobs, int* launches_out, void* stream);
 
+/* ------------------------------------------------------ view evaluation (csrc/eval.hip)
+ * What Mapper.gs_eval_offline and eval/eval_mesh_utils.py compute per evaluated view.  Every call only enqueues on
+ * `stream`: no allocation, no copy, no wait; results are device records the caller reads when it wants them.  A cloud
+ * is a [cap, 3] fp32 buffer whose live length is `cap`, or *x_dev (DEVICE int64, clamped into [0, cap]) when that
+ * pointer is not NULL, so a length produced by one call feeds the next without passing through the host.  Sizes are
+ * limited to 2^31 - 1 rows; a *_scratch_bytes query returns 0 for a size no call accepts.
+ *
+ * view_metrics   one pass over rgb / gt [channels, hw] (1..4 channels) and, when depth != NULL, depth / gt_depth [hw]
+ *   under the mask gt > depth_min && d > depth_min && gt < depth_max && d < depth_max (&& alpha > min_alpha with
+ *   use_alpha).  record[PINGS_EVAL_VIEW_RECORD] doubles: mean over channels of 20 log10(1 / sqrt(mse_c)), *ssim (a
+ *   DEVICE float, NaN when NULL), mean |dd|, sqrt(mean dd^2) (both NaN on an empty mask or without depth), the mask
+ *   count, mse_0..mse_3 (NaN past `channels`).
+ * backproject   pixel (u, v) of depth [height, width] gives a point iff 0 < d < depth_trunc (&& alpha > min_alpha):
+ *   cam_to_world * ((u - cx) d / fx, (v - cy) d / fy, d, 1), in row-major pixel order; colors = floor(rgb * 255) / 255
+ *   of rgb [3, hw] when rgb != NULL.  intrinsic (HOST) = fx, fy, cx, cy; cam_to_world (HOST) = the first three rows of
+ *   the 4x4, row-major.  points / colors hold height*width rows; *count (DEVICE) receives the number written.
+ * voxel_centroids   Open3D voxel_down_sample: cell floor((p - (min - voxel/2)) / voxel) per axis in fp64, out = the
+ *   mean of each occupied cell's points in ascending cell key (x fastest), sums in fp64 in input order (no atomics:
+ *   bitwise repeatable).  out holds n rows; *count (DEVICE) receives the number of cells.
+ * nn_build / nn_query   exact nearest neighbour among dst below max_dist.  build files dst by cells of size `cell`
+ *   relative to its lower bound into `scratch` (O(m) bytes); query (same scratch, m and cell; any number of times)
+ *   writes dist[n] and idx[n]: +inf / -1 where no dst point lies at distance < max_dist, ties in fp32 distance to the
+ *   smallest index, rows past the live length of src +inf / -1.  ceil(max_dist / cell) may not exceed 64.
+ * A cloud whose extent exceeds 2^21 cells on an axis cannot be filed: the extent is known on the device only, so it
+ * is reported by OR-ing PINGS_EVAL_EXTENT into *status (DEVICE int32, zeroed by the caller), and a query against such
+ * a grid writes NaN / -2 in every row.
+ * pair_reduce   record[PINGS_EVAL_PAIR_RECORD] doubles from the two distance lists: {kept, sum d, sum d^2, d <
+ *   threshold} of dist_p without its +inf rows, the same four of dist_r with +inf rows counted as truncation_com,
+ *   the live lengths np and nr, *status (0 when NULL), 0. */
+#define PINGS_EVAL_VIEW_RECORD 9
+#define PINGS_EVAL_PAIR_RECORD 12
+#define PINGS_EVAL_EXTENT 1
+PINGS_API size_t pings_eval_view_metrics_scratch_bytes(int64_t hw);
+PINGS_API int pings_eval_view_metrics(const float* rgb, const float* gt, int channels, int64_t hw, const float* depth,
+                                      const float* gt_depth, const float* alpha, float depth_min, float depth_max,
+                                      float min_alpha, int use_alpha, const float* ssim, void* scratch, double* record,
+                                      void* stream);
+PINGS_API size_t pings_eval_backproject_scratch_bytes(int64_t hw);
+PINGS_API int pings_eval_backproject(const float* depth, const float* rgb, const float* alpha, int height, int width,
+                                     const double* intrinsic, const double* cam_to_world, double depth_trunc,
+                                     float min_alpha, int use_alpha, void* scratch, float* points, float* colors,
+                                     int64_t* count, void* stream);
+PINGS_API size_t pings_eval_voxel_scratch_bytes(int64_t n);
+PINGS_API int pings_eval_voxel_centroids(const float* points, int64_t n, const int64_t* n_dev, double voxel,
+                                         void* scratch, float* out, int64_t* count, int32_t* status, void* stream);
+PINGS_API size_t pings_eval_nn_scratch_bytes(int64_t m);
+PINGS_API int pings_eval_nn_build(const float* dst, int64_t m, const int64_t* m_dev, double cell, void* scratch,
+                                  int32_t* status, void* stream);
+PINGS_API int pings_eval_nn_query(const float* src, int64_t n, const int64_t* n_dev, const void* scratch, int64_t m,
+                                  double cell, double max_dist, float* dist, int64_t* idx, void* stream);
+PINGS_API int pings_eval_pair_reduce(const float* dist_p, int64_t np, const int64_t* np_dev, const float* dist_r,
+                                     int64_t nr, const int64_t* nr_dev, double threshold, double truncation_com,
+                                     const int32_t* status, double* record, void* stream);
+
 #endif /* PINGS_HIP_H_ */

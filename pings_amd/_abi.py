@@ -16,9 +16,11 @@ REG_SINGULAR, REG_ILL_CONDITIONED, REG_NONFINITE = 1, 2, 4        # PINGS_REG_*:
 REG_F_NORMALS, REG_F_DIV_GRAD, REG_F_WEIGHTED = 1, 2, 4           # PINGS_REG_F_*: pings_reg_loop_args.flags
 MC_ALLOW_DEGENERATE, MC_ASCENT = 1, 2                             # PINGS_MC_*: pings_mc_count / pings_mc_emit flags
 ADAMW_MAX_JOBS, ADAMW_CHUNK = 48, 4096                            # PINGS_ADAMW_*: tensors per launch, elements per item
+EVAL_VIEW_RECORD, EVAL_PAIR_RECORD = 9, 12                        # PINGS_EVAL_*_RECORD: doubles per record
+EVAL_EXTENT = 1                                                   # PINGS_EVAL_EXTENT: status bit of the eval grids
 
 vp = C.c_void_p     # device pointers and the hipStream_t travel as integers (tensor.data_ptr())
-i32, i64, f32, sz = C.c_int, C.c_int64, C.c_float, C.c_size_t
+i32, i64, f32, f64, sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
 
 
 # ---------------------------------------------------------------- struct mirrors: pings_<snake_case of the class name>
@@ -278,4 +280,16 @@ SIGNATURES = {
     "pings_mc_emit": (i32, [vp, vp, i64, i64, i64, f32, i32, vp, i64, i64, vp, vp, vp, vp]),
     # fused AdamW
     "pings_adamw_step": (i32, [C.POINTER(AdamwJob), i32, C.POINTER(i32), vp]),
+    # view evaluation
+    "pings_eval_view_metrics_scratch_bytes": (sz, [i64]),
+    "pings_eval_view_metrics": (i32, [vp, vp, i32, i64, vp, vp, vp, f32, f32, f32, i32, vp, vp, vp, vp]),
+    "pings_eval_backproject_scratch_bytes": (sz, [i64]),
+    "pings_eval_backproject": (i32, [vp, vp, vp, i32, i32, C.POINTER(f64), C.POINTER(f64), f64, f32, i32, vp, vp, vp,
+                                     vp, vp]),
+    "pings_eval_voxel_scratch_bytes": (sz, [i64]),
+    "pings_eval_voxel_centroids": (i32, [vp, i64, vp, f64, vp, vp, vp, vp, vp]),
+    "pings_eval_nn_scratch_bytes": (sz, [i64]),
+    "pings_eval_nn_build": (i32, [vp, i64, vp, f64, vp, vp, vp]),
+    "pings_eval_nn_query": (i32, [vp, i64, vp, vp, i64, f64, f64, vp, vp, vp]),
+    "pings_eval_pair_reduce": (i32, [vp, i64, vp, vp, i64, vp, f64, f64, vp, vp, vp]),
 }
