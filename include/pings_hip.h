@@ -154,6 +154,15 @@ PINGS_API int pings_raster_render(const pings_raster_settings* s, int P, int64_t
                                   float* out_depth, float* out_alpha, void* per_gaussian,
                                   int footprint_class, void* stream);
 
+/* The tile sort of stage 2 on its own (tests): keys[n] of key_bytes = 2 | 4 bytes on the device -> keys_sorted[n] in
+ * stable order of their low `bits` bits and values[n] = the element index each came from.  bits <= 16 runs the
+ * project's two-pass radix sort unless `library` is non-zero; wider keys, or `library`, run rocprim::radix_sort_pairs.
+ * scratch: device memory of pings_raster_tile_sort_bytes(n, ...) bytes, which also reports the pairs a workgroup of
+ * the sort owns (block_pairs, nullable). */
+PINGS_API size_t pings_raster_tile_sort_bytes(int64_t n, int32_t* block_pairs);
+PINGS_API int pings_raster_tile_sort(const void* keys, int64_t n, int key_bytes, int bits, void* keys_sorted,
+                                     uint32_t* values, void* scratch, int library, void* stream);
+
 /* Scratch bytes pings_raster_backward needs (an upper bound in the instance count: the
  * gradient rows of the instances that actually blended are a data-dependent subset). */
 PINGS_API size_t pings_raster_backward_bytes(int P, int64_t num_instances);

@@ -106,8 +106,9 @@ struct GeomState {
 
 struct BinState {
   // pre-sort, slot order (= depth rank, then tile order inside the Gaussian's rectangle): tile_key[slot],
-  // gval[slot] = Gaussian id;  sorted by tile: point_list[i] = slot (the sort's value input is a counting iterator)
+  // gval[slot] = Gaussian id;  sorted by tile: point_list[i] = slot (the sort's values are the element indices, no iota array)
   uint32_t *tile_key, *tile_key_sorted, *gval, *point_list;
+  uint32_t* slot_val;  // [I] the tile sort's values between its two passes (tile_sort.hip)
   uint2* ranges;
   float* inst_w;       // [I+1] per-instance sum of blend weights (0 = instance never blended)
   uint8_t* inst_qmask; // [I+1] 8x8 quadrants of the tile in which the instance blended something (bit q = qx + 2 qy)
@@ -209,6 +210,7 @@ struct RasterKnobs {
   uint32_t bwd_long = 3072u;     // PINGS_BWD_LONG: the threshold itself (never = 0xFFFFFFF0)
   bool occlusion = true;         // PINGS_RASTER_OCCLUSION
   bool library_sort = false;     // PINGS_DEPTH_SORT
+  bool library_tile_sort = false;  // PINGS_TILE_SORT
   float occ_amin = 0.15f;        // PINGS_OCC_AMIN
   int rect_rule = RECT_TIGHT;    // PINGS_RASTER_RECT
   bool mark_depth_only = false;  // PINGS_MARK_VISIBLE
@@ -248,6 +250,20 @@ int occlusion_buckets(int num_tiles);
 BinState carve_binning(void* blob, int64_t I, int num_tiles, uint32_t seg);
 ImageState carve_image(void* blob, int W, int H);
 BwdState carve_bwd(void* blob, int P, int64_t I);
+
+// tile_sort.hip: stable sort of (key, element index) by the low `bits` <= 16 bits of the key, KeyT = uint16_t | uint32_t.
+// One pass (bits <= 8) goes from keys_in straight to keys_out / vals_out; two passes go through keys_tmp / vals_tmp,
+// and keys_out may then be keys_in.  `table`: tile_sort_table_bytes(n) bytes.  Workgroups of TS_THREADS own TS_BLOCK pairs.
+constexpr int TS_THREADS = 256, TS_BLOCK = 4096;
+size_t tile_sort_table_bytes(int64_t n);
+template <typename KeyT>
+int tile_sort(const KeyT* keys_in, int64_t n, int bits, KeyT* keys_tmp, uint32_t* vals_tmp, KeyT* keys_out,
+              uint32_t* vals_out, uint32_t* table, hipStream_t st);
+// rocprim::radix_sort_pairs of the same pairs, and the scratch it asks for (either key width)
+size_t tile_sort_library_bytes(int64_t n);
+template <typename KeyT>
+int tile_sort_library(const KeyT* keys_in, int64_t n, int bits, KeyT* keys_out, uint32_t* vals_out, void* temp,
+                      size_t temp_bytes, hipStream_t st);
 
 // raster_blend_fwd.hip: the blend half of pings_raster_render — the forward kernels of `plan`, then the per-Gaussian sums
 int launch_blend_fwd(int mode, const KParams& kp, const BlendPlan& plan, int P, int64_t I, const GeomState& gs,

@@ -6,8 +6,8 @@
 //   radix sort (P)      Gaussians by depth key (hipcub / rocPRIM)
 //   gather + scan       tiles-per-Gaussian in depth order -> instance offsets
 //   duplicate_kernel    emits (tile id, Gaussian id) instances in depth order  [8 B per instance]
-//   radix sort (I)      STABLE sort by tile id only (ceil(log2(tiles)) bits)    [the only multi-pass
-//                       traffic over the instance list; 32-bit keys instead of 64-bit]
+//   radix sort (I)      STABLE sort by tile id only (ceil(log2(tiles)) bits): tile_sort.hip  [the only
+//                       multi-pass traffic over the instance list; 16-bit keys instead of 64-bit]
 //   tile_ranges_kernel  [start,end) of every tile in the sorted list
 //   blend + sums        raster_blend_fwd.hip (launch_blend_fwd); blob layout, environment knobs and the
 //                       choice of blend kernels: raster_layout.hip
@@ -1187,17 +1187,24 @@ PINGS_API int pings_raster_render(const pings_raster_settings* s, int P, int64_t
                            gs.rect, gs.occ_mask, gs.nvalid, key, bs.gval);
         PINGS_LAUNCH_CHECK();
       }
+      const int bits = tile_bits(num_tiles);
+      const KeyT* sorted = key_sorted;
       {
         pings::prof::Scope ps("tile_sort", st);
-        size_t tb = bs.temp_bytes;
-        // the values are the slots themselves: a counting iterator, not an array of I words written to be read once
-        PINGS_HIP_CHECK(rocprim::radix_sort_pairs(bs.temp, tb, key, key_sorted, rocprim::counting_iterator<uint32_t>(0u),
-                                                  bs.point_list, (size_t)I, 0u, (unsigned)tile_bits(num_tiles), st));
+        if (knobs.library_tile_sort || bits > 16) {
+          if (int e = tile_sort_library<KeyT>(key, I, bits, key_sorted, bs.point_list, bs.temp, bs.temp_bytes, st)) return e;
+        } else {
+          // two passes: through key_sorted / slot_val and back into `key`; one pass: straight to key_sorted
+          if (bits > 8) sorted = key;
+          if (int e = tile_sort<KeyT>(key, I, bits, key_sorted, bs.slot_val, bits > 8 ? key : key_sorted, bs.point_list,
+                                      reinterpret_cast<uint32_t*>(bs.temp), st))
+            return e;
+        }
       }
       {
         pings::prof::Scope ps("tile_ranges", st);
         hipLaunchKernelGGL(tile_ranges_kernel<KeyT>, dim3((unsigned)pings::ceil_div<int64_t>(I, 256)), dim3(256), 0,
-                           st, I, (const KeyT*)key_sorted, bs.ranges);
+                           st, I, sorted, bs.ranges);
         PINGS_LAUNCH_CHECK();
       }
       return PINGS_OK;

@@ -24,14 +24,8 @@ static size_t sort_temp_bytes(int64_t n) {
   (void)hipcub::DeviceRadixSort::SortPairs(nullptr, c, (uint16_t*)nullptr, (uint16_t*)nullptr,
                                            (uint32_t*)nullptr, (uint32_t*)nullptr, (int)n, 0, 16);
   if (c > a) a = c;
-  // the tile sort's values come from a counting iterator (pings_raster_render): same algorithm, asked for its own size
-  size_t d = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, d, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                  rocprim::counting_iterator<uint32_t>(0u), (uint32_t*)nullptr, (size_t)n, 0u, 32u);
-  size_t e = 0;
-  (void)rocprim::radix_sort_pairs(nullptr, e, (uint16_t*)nullptr, (uint16_t*)nullptr,
-                                  rocprim::counting_iterator<uint32_t>(0u), (uint32_t*)nullptr, (size_t)n, 0u, 16u);
-  a = std::max(a, std::max(d, e));
+  // the tile sort: the library's scratch (its values come from a counting iterator: its own size) or the digit table
+  a = std::max(a, std::max(tile_sort_library_bytes(n), tile_sort_table_bytes(n)));
   return align_up(a > b ? a : b) + 256;
 }
 
@@ -97,9 +91,8 @@ BinState carve_binning(void* blob, int64_t I, int num_tiles, uint32_t seg) {
   b.tile_key = c.take<uint32_t>(n);
   b.tile_key_sorted = c.take<uint32_t>(n);
   b.gval = c.take<uint32_t>(n);
-  // 4 n bytes nobody uses (the tile sort's value input until it became a counting iterator): the fields behind keep
-  // their offsets, which tests/test_raster_glue.py reads straight out of the blob
-  (void)c.take<uint32_t>(n);
+  // the fields up to tile_maxc keep their offsets, which tests/test_raster_glue.py reads straight out of the blob
+  b.slot_val = c.take<uint32_t>(n);
   b.tile_order = c.take<uint32_t>(2 * (size_t)num_tiles + 4);   // + the backward pass' long-list tile count
   b.tile_work = c.take<uint32_t>((size_t)num_tiles);
   b.tile_maxc = c.take<uint32_t>((size_t)num_tiles);
@@ -166,6 +159,8 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
 //                                                                   waves per quadrant, rounded up to 16; <= 0 = never
 //   PINGS_RASTER_OCCLUSION  1 | 0                     tests         0 keeps every (Gaussian, tile) instance (list-parity tests)
 //   PINGS_DEPTH_SORT        bucket | l(ibrary)        tests         first letter l: rocPRIM radix sort instead of the bucket sort
+//   PINGS_TILE_SORT         radix | l(ibrary)         tests, A/B    first letter l: rocPRIM radix sort instead of the two-pass sort of
+//                                                                   tile_sort.hip (more than 65,536 tiles: always the library)
 //   PINGS_OCC_AMIN          0.15 | x                  A/B           alpha below which a tile stays out of the occlusion budget, in [1/255, 0.99]
 //   PINGS_RASTER_RECT       tight | 3(sigma) | e(llipse)  bench, tests  tile-rectangle rule of preprocess_kernel, by first letter
 //   PINGS_MARK_VISIBLE      frustum | d(epth)         tests         first letter d: mark_visible tests depth only, the variant in which
@@ -193,6 +188,7 @@ RasterKnobs read_knobs() {
   }
   if (const char* e = getenv("PINGS_RASTER_OCCLUSION")) k.occlusion = atoi(e) != 0;
   if (const char* e = getenv("PINGS_DEPTH_SORT")) k.library_sort = e[0] == 'l';
+  if (const char* e = getenv("PINGS_TILE_SORT")) k.library_tile_sort = e[0] == 'l';
   // Tiles a Gaussian covers with less than this alpha everywhere are left out of the occlusion budget: fewer entries
   // is still a lower bound of the opacity in front (conservative: the kept lists can only grow, results unchanged),
   // and the faint rim of every footprint was most of the budget pass's atomics.  Metric-1 sweep (r03): 1/255 -> 0.15
