@@ -163,6 +163,15 @@ PINGS_API size_t pings_raster_tile_sort_bytes(int64_t n, int32_t* block_pairs);
 PINGS_API int pings_raster_tile_sort(const void* keys, int64_t n, int key_bytes, int bits, void* keys_sorted,
                                      uint32_t* values, void* scratch, int library, void* stream);
 
+/* The prefix sums of stages 1, 2 and the backward on their own (tests): out[i] = f(in[0]) + .. + f(in[i - 1]) modulo
+ * 2^32, plus f(in[i]) when `inclusive` is non-zero.  kind 0: in is uint32_t[n], f the identity; 1: float[n], f(w) =
+ * w > 0; 2: uint8_t[n], f(m) = popcount(m & 15).  in and out are 16-byte aligned.  Up to 16,777,216 elements run the
+ * project's two-launch scan unless PINGS_RASTER_SCAN=l is set; longer ones, or that, run hipcub::DeviceScan.
+ * temp: device memory of pings_raster_scan_bytes(n) bytes. */
+PINGS_API size_t pings_raster_scan_bytes(int64_t n);
+PINGS_API int pings_raster_scan_u32(const void* in, int64_t n, int kind, int inclusive, uint32_t* out, void* temp,
+                                    size_t temp_bytes, void* stream);
+
 /* Scratch bytes pings_raster_backward needs (an upper bound in the instance count: the
  * gradient rows of the instances that actually blended are a data-dependent subset). */
 PINGS_API size_t pings_raster_backward_bytes(int P, int64_t num_instances);

@@ -146,6 +146,8 @@ SIGNATURES = {
     "pings_raster_render": (i32, [C.POINTER(RasterSettings), i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),
     "pings_raster_tile_sort_bytes": (sz, [i64, C.POINTER(i32)]),
     "pings_raster_tile_sort": (i32, [vp, i64, i32, i32, vp, vp, vp, i32, vp]),
+    "pings_raster_scan_bytes": (sz, [i64]),
+    "pings_raster_scan_u32": (i32, [vp, i64, i32, i32, vp, vp, sz, vp]),
     "pings_raster_backward_bytes": (sz, [i32, i64]),
     "pings_raster_backward": (i32, [C.POINTER(RasterSettings), i32, i64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                     vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, vp]),

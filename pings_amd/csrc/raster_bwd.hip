@@ -691,10 +691,6 @@ __device__ inline float grp_shr1(float x, float first, int lane) {
   return (G == 32 && lane == 32) ? first : y;
 }
 
-struct PopOp {
-  __host__ __device__ uint32_t operator()(const uint8_t& m) const { return (uint32_t)__builtin_popcount((unsigned)m & 15u); }
-};
-
 #ifdef PINGS_BWD_STATS
 #define STATS_PARAMS , unsigned long long& st_dead, unsigned long long& st_any, unsigned long long& st_exec, unsigned long long& st_valid
 #define STATS_ARGS , st_dead, st_any, st_exec, st_valid
@@ -1013,31 +1009,7 @@ __global__ __launch_bounds__(256) void blend_bwd_scan_kernel(
 }
 
 // ---------------------------------------------------------------- balanced per-Gaussian row sums
-struct LiveOp {
-  __host__ __device__ uint32_t operator()(const float& w) const { return w > 0.f ? 1u : 0u; }
-};
-
-// per depth rank r: the Gaussian's rows are the compact range [cidx[first slot], cidx[end slot]); its number of
-// <= CH-row chunks is the input of the pair_off scan, computed as the scan reads it (entry P = 0) instead of by a
-// pass of its own through an array
-struct RowRanges {
-  int P;
-  const uint32_t *offsets_sorted, *tiles_sorted, *cidx;
-  __host__ __device__ uint32_t row_begin(uint32_t r) const { return cidx[offsets_sorted[r] - tiles_sorted[r]]; }
-  __host__ __device__ uint32_t row_end(uint32_t r) const { return cidx[offsets_sorted[r]]; }
-  __host__ __device__ uint32_t operator()(const uint32_t& r) const {
-    if (r >= (uint32_t)P) return 0u;
-    return (row_end(r) - row_begin(r) + (uint32_t)CH - 1u) / (uint32_t)CH;
-  }
-};
-
-__global__ __launch_bounds__(256) void pair_owner_kernel(int P, const uint32_t* __restrict__ pair_off,
-                                                          uint32_t* __restrict__ pair_owner) {
-  const int r = blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= P) return;
-  const uint32_t a = pair_off[r], b = pair_off[r + 1];
-  for (uint32_t q = a; q < b; ++q) pair_owner[q] = (uint32_t)r;
-}
+// LiveOp, RowRanges: raster_common.hpp; pair_off and pair_owner: raster_scan_chunks
 
 // one 16-lane group per (Gaussian, chunk) pair; lane = column of the 16-float row
 __global__ __launch_bounds__(256) void row_chunk_sum_kernel(RowRanges rr, const uint32_t* __restrict__ pair_off,
@@ -1341,35 +1313,16 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
   BinState bs = carve_binning(const_cast<void*>(binning_blob), I, num_tiles, knobs.blend_seg);
   ImageState im = carve_image(const_cast<void*>(image_blob), bp.W, bp.H);
   BwdState bw = carve_bwd(bwd_blob, P, I);
-  const dim3 gridP(pings::ceil_div(P + 1, 256)), block(256);
+  const dim3 block(256);
   const RowRanges rr{P, gs.offsets_sorted, gs.tiles_sorted, bw.cidx};
 
-  {
-    pings::prof::Scope ps("live_scan", st);
-    if (I > 0 && plan.bwd_scan) {
-      // one row per (instance, quadrant it blended in): inst_qmask has I+1 entries, the last one zero
-      hipcub::TransformInputIterator<uint32_t, PopOp, const uint8_t*> cnt(bs.inst_qmask, PopOp());
-      size_t tb = bw.temp_bytes;
-      PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(bw.temp, tb, cnt, bw.cidx, (int)(I + 1), st));
-    } else if (I > 0) {
-      // inst_w has I+1 entries, the last one zero: cidx[I] = number of live instances
-      hipcub::TransformInputIterator<uint32_t, LiveOp, const float*> flags(bs.inst_w, LiveOp());
-      size_t tb = bw.temp_bytes;
-      PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(bw.temp, tb, flags, bw.cidx, (int)(I + 1), st));
-    } else {
-      PINGS_HIP_CHECK(hipMemsetAsync(bw.cidx, 0, 2 * sizeof(uint32_t), st));
-    }
-    hipcub::TransformInputIterator<uint32_t, RowRanges, hipcub::CountingInputIterator<uint32_t>> nch(
-        hipcub::CountingInputIterator<uint32_t>(0u), rr);
-    size_t tb = bw.temp_bytes;
-    PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(bw.temp, tb, nch, bw.pair_off, P + 1, st));
-    hipLaunchKernelGGL(pair_owner_kernel, gridP, block, 0, st, P, bw.pair_off, bw.pair_owner);
-    PINGS_LAUNCH_CHECK();
-  }
+  // The prelude of the blend backward: the tile order (tiles by descending largest per-pixel contributor count, the
+  // records a tile walks), the live rows' scan and the chunk scan with its owners.  The tile order shares nothing with
+  // the scans and is one workgroup: it rides in the reduce launch of the live scan.  (On a side stream next to the row
+  // scans — two chains of small launches — the step came out 0.008 - 0.025 ms SLOWER on Metric-1 / C2: the fork and
+  // join cost more than the 16 us they could hide.)
+  TileOrderJob order_job;
   if (I > 0) {
-    // backward dispatch order: tiles by descending largest per-pixel contributor count (the records a tile walks).
-    // (On a side stream next to the row scans above — two chains of small launches that share nothing — the step came
-    // out 0.008 - 0.025 ms SLOWER on Metric-1 / C2: the fork and join cost more than the 16 us they could hide.)
     pings::prof::Scope ps("tile_order", st);
     const bool fwd_left_it = plan.fwd == BlendPlan::FWD_TILE;   // blend_fwd_tile_kernel's epilogue: the same numbers
     if (!fwd_left_it) {
@@ -1377,8 +1330,27 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
                          bs.tile_work);
       PINGS_LAUNCH_CHECK();
     }
-    if (int e = launch_tile_order(fwd_left_it ? bs.tile_maxc : bs.tile_work, num_tiles, bs.tile_order + num_tiles, st,
-                                  bs.tile_order + 2 * (size_t)num_tiles, plan.long_thr, LONG_TILES_MAX))
+    order_job.work = fwd_left_it ? bs.tile_maxc : bs.tile_work;
+    order_job.num_tiles = num_tiles;
+    order_job.order = bs.tile_order + num_tiles;
+    order_job.n_long = bs.tile_order + 2 * (size_t)num_tiles;
+    order_job.long_thr = plan.long_thr;
+    order_job.long_max = LONG_TILES_MAX;
+  }
+  {
+    pings::prof::Scope ps("live_scan", st);
+    if (I > 0 && plan.bwd_scan) {
+      // one row per (instance, quadrant it blended in): inst_qmask has I+1 entries, the last one zero
+      if (int e = raster_scan_pop(bs.inst_qmask, I + 1, bw.cidx, bw.temp, bw.temp_bytes, knobs.library_scan, order_job, st))
+        return e;
+    } else if (I > 0) {
+      // inst_w has I+1 entries, the last one zero: cidx[I] = number of live instances
+      if (int e = raster_scan_live(bs.inst_w, I + 1, bw.cidx, bw.temp, bw.temp_bytes, knobs.library_scan, order_job, st))
+        return e;
+    } else {
+      PINGS_HIP_CHECK(hipMemsetAsync(bw.cidx, 0, 2 * sizeof(uint32_t), st));
+    }
+    if (int e = raster_scan_chunks(rr, bw.pair_off, bw.pair_owner, bw.temp, bw.temp_bytes, knobs.library_scan, st))
       return e;
   }
   if (I > 0) {

@@ -211,6 +211,7 @@ struct RasterKnobs {
   bool occlusion = true;         // PINGS_RASTER_OCCLUSION
   bool library_sort = false;     // PINGS_DEPTH_SORT
   bool library_tile_sort = false;  // PINGS_TILE_SORT
+  bool library_scan = false;     // PINGS_RASTER_SCAN
   float occ_amin = 0.15f;        // PINGS_OCC_AMIN
   int rect_rule = RECT_TIGHT;    // PINGS_RASTER_RECT
   bool mark_depth_only = false;  // PINGS_MARK_VISIBLE
@@ -369,6 +370,118 @@ __device__ inline float wave_sum_to_all(float v) {
   v = wave_reduce_sum_dpp(v);
   return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
 }
+
+// wave64 inclusive integer sum
+__device__ inline uint32_t wave_inclusive_sum(uint32_t v, int lane) {
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t u = __shfl_up(v, d, 64);
+    if (lane >= d) v += u;
+  }
+  return v;
+}
+
+// ---------------------------------------------------------------- longest-processing-time-first tile dispatch
+// A tile's blend time is proportional to its list; the lists are very uneven (Metric-1: 0..374 blended records,
+// mean 127), and workgroups are dispatched in grid order: with tiles in image order the long ones that start late
+// run on an otherwise idle chip.  Dispatching tiles in descending work order fills the tail with short ones.
+// One workgroup of 1,024 threads: counting sort of the tiles by min(work / 16, 1023), descending.  FROM_RANGES: a
+// tile's work is the length of its list, taken from `ranges` directly (forward order) instead of from a `work` array.
+// The body of tile_order_kernel (raster_fwd.hip) and of the extra workgroup of the backward's live-scan reduce launch
+// (raster_scan.hip).
+template <bool FROM_RANGES>
+__device__ inline void tile_order_body(const uint32_t* __restrict__ work_in, const uint2* __restrict__ ranges,
+                                       int num_tiles, uint32_t* __restrict__ order, uint32_t* __restrict__ n_long,
+                                       uint32_t long_thr, uint32_t long_max) {
+  __shared__ uint32_t hist[1024];
+  __shared__ uint32_t base[1024];
+  __shared__ uint32_t wtot[16];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  auto work = [&](int t) -> uint32_t {
+    if constexpr (FROM_RANGES) { const uint2 r = ranges[t]; return r.y - r.x; }
+    else return work_in[t];
+  };
+  hist[tid] = 0u;
+  __syncthreads();
+  for (int t = tid; t < num_tiles; t += 1024) atomicAdd(&hist[min(work(t) >> 4, 1023u)], 1u);
+  __syncthreads();
+  // scan over the bins in DESCENDING bin order (bin 1023 first); 1024 threads, one bin each: inside the wave, then
+  // the totals of the waves in front out of LDS
+  const uint32_t v = hist[1023 - tid];
+  uint32_t incl = wave_inclusive_sum(v, lane);
+  if (lane == 63) wtot[wave] = incl;
+  __syncthreads();
+#pragma unroll
+  for (int w = 0; w < 16; ++w) incl += w < wave ? wtot[w] : 0u;
+  base[tid] = incl;
+  hist[1023 - tid] = incl - v;   // hist[bin] = first output position of the bin
+  __syncthreads();
+  for (int t = tid; t < num_tiles; t += 1024) order[atomicAdd(&hist[min(work(t) >> 4, 1023u)], 1u)] = (uint32_t)t;
+  // tiles with work >= long_thr (a multiple of 16: whole bins) are the first entries of the order: their number.
+  // The order WITHIN a bin is the arrival order of the LDS atomics above, so a cap that cut through a bin would make
+  // the set of tiles the backward splits depend on timing.  The cap therefore takes whole bins only: the longest
+  // prefix of bins (from the top, down to the threshold's) whose tiles number at most long_max — if the top bin alone
+  // holds more, nothing is split.  A threshold above the top bin (work >> 4 is clamped to 1023) splits nothing either.
+  if (n_long) {
+    const uint32_t bin = long_thr >> 4;
+    if (bin > 1023u) {
+      if (tid == 0) *n_long = 0u;
+    } else {
+      // base[k] = inclusive count of bins 1023 .. 1023 - k, non-decreasing in k: exactly one thread writes
+      const uint32_t kmax = 1023u - bin;
+      const uint32_t k = (uint32_t)tid;
+      if (k <= kmax && base[k] <= long_max && (k == kmax || base[k + 1] > long_max)) *n_long = base[k];
+      if (tid == 0 && base[0] > long_max) *n_long = 0u;
+    }
+  }
+}
+
+// ---------------------------------------------------------------- prefix sums (raster_scan.hip)
+// what the scans of the backward read: the stored element -> uint32_t
+struct LiveOp {
+  __host__ __device__ uint32_t operator()(const float& w) const { return w > 0.f ? 1u : 0u; }
+};
+struct PopOp {
+  __host__ __device__ uint32_t operator()(const uint8_t& m) const { return (uint32_t)__builtin_popcount((unsigned)m & 15u); }
+};
+// per depth rank r: the Gaussian's rows are the compact range [cidx[first slot], cidx[end slot]); its number of
+// <= CH-row chunks is the input of the pair_off scan, computed as the scan reads it (entry P = 0) instead of by a
+// pass of its own through an array
+struct RowRanges {
+  int P;
+  const uint32_t *offsets_sorted, *tiles_sorted, *cidx;
+  __host__ __device__ uint32_t row_begin(uint32_t r) const { return cidx[offsets_sorted[r] - tiles_sorted[r]]; }
+  __host__ __device__ uint32_t row_end(uint32_t r) const { return cidx[offsets_sorted[r]]; }
+  __host__ __device__ uint32_t operator()(const uint32_t& r) const {
+    if (r >= (uint32_t)P) return 0u;
+    return (row_end(r) - row_begin(r) + (uint32_t)CH - 1u) / (uint32_t)CH;
+  }
+};
+
+// Sums modulo 2^32 of n elements read through the functor, exclusive unless said otherwise; out[n], 16-byte aligned
+// like every blob field.  Up to SCAN_MAX elements: two launches of the project's own (reduce, apply; one when a single
+// workgroup holds them all), beyond, or with `library` (PINGS_RASTER_SCAN=l): hipcub::DeviceScan.  temp: at least
+// raster_scan_bytes(n) bytes.
+constexpr int SCAN_THREADS = 1024, SCAN_BLOCK = 4 * SCAN_THREADS;   // elements a workgroup of the scan owns
+constexpr int64_t SCAN_MAX = (int64_t)SCAN_BLOCK * SCAN_BLOCK;      // one uint4 of totals per thread
+size_t raster_scan_bytes(int64_t n);
+int raster_scan_u32(const uint32_t* in, int64_t n, bool inclusive, uint32_t* out, void* temp, size_t temp_bytes,
+                    bool library, hipStream_t st);
+// The backward's tile order, computed by one extra workgroup of the live scan's reduce launch (unlike work in one
+// launch: it shares no data with the scan).  work == nullptr: no tile order.  With `library` it is a launch of its own.
+struct TileOrderJob {
+  const uint32_t* work = nullptr;
+  int num_tiles = 0;
+  uint32_t *order = nullptr, *n_long = nullptr;
+  uint32_t long_thr = 0, long_max = 0;
+};
+int raster_scan_live(const float* inst_w, int64_t n, uint32_t* cidx, void* temp, size_t temp_bytes, bool library,
+                     const TileOrderJob& job, hipStream_t st);
+int raster_scan_pop(const uint8_t* inst_qmask, int64_t n, uint32_t* cidx, void* temp, size_t temp_bytes, bool library,
+                    const TileOrderJob& job, hipStream_t st);
+// pair_off[0 .. P], then pair_owner[q] = r for q in [pair_off[r], pair_off[r + 1]) (pair_owner_kernel)
+int raster_scan_chunks(const RowRanges& rr, uint32_t* pair_off, uint32_t* pair_owner, void* temp, size_t temp_bytes,
+                       bool library, hipStream_t st);
 
 // ---------------------------------------------------------------- sub-tile culling
 // A record contributes to a pixel only if alpha = min(0.99, o exp(power)) >= 1/255, i.e.

@@ -850,59 +850,13 @@ __global__ __launch_bounds__(256) void duplicate_kernel(int P, int gx, int nb, i
 }
 
 // ---------------------------------------------------------------- longest-processing-time-first tile dispatch
-// A tile's blend time is proportional to its list; the lists are very uneven (Metric-1: 0..374 blended records,
-// mean 127), and workgroups are dispatched in grid order: with tiles in image order the long ones that start late
-// run on an otherwise idle chip.  Dispatching tiles in descending work order fills the tail with short ones.
-// One workgroup: counting sort of the tiles by min(work / 16, 1023), descending.  FROM_RANGES: a tile's work is the
-// length of its list, taken from `ranges` directly (forward order) instead of from a `work` array.
+// tile_order_body: raster_common.hpp
 template <bool FROM_RANGES>
 __global__ __launch_bounds__(1024) void tile_order_kernel(const uint32_t* __restrict__ work_in,
                                                           const uint2* __restrict__ ranges, int num_tiles,
                                                           uint32_t* __restrict__ order, uint32_t* __restrict__ n_long,
                                                           uint32_t long_thr, uint32_t long_max) {
-  __shared__ uint32_t hist[1024];
-  __shared__ uint32_t base[1024];
-  const int tid = threadIdx.x;
-  auto work = [&](int t) -> uint32_t {
-    if constexpr (FROM_RANGES) { const uint2 r = ranges[t]; return r.y - r.x; }
-    else return work_in[t];
-  };
-  hist[tid] = 0u;
-  __syncthreads();
-  for (int t = tid; t < num_tiles; t += 1024) atomicAdd(&hist[min(work(t) >> 4, 1023u)], 1u);
-  __syncthreads();
-  // exclusive scan over the bins in DESCENDING bin order (bin 1023 first); 1024 threads, one bin each
-  uint32_t v = hist[1023 - tid];
-  base[tid] = v;
-  __syncthreads();
-  for (int off = 1; off < 1024; off <<= 1) {
-    const uint32_t add = tid >= off ? base[tid - off] : 0u;
-    __syncthreads();
-    base[tid] += add;
-    __syncthreads();
-  }
-  const uint32_t excl = base[tid] - v;
-  __syncthreads();
-  hist[1023 - tid] = excl;   // hist[bin] = first output position of the bin
-  __syncthreads();
-  for (int t = tid; t < num_tiles; t += 1024) order[atomicAdd(&hist[min(work(t) >> 4, 1023u)], 1u)] = (uint32_t)t;
-  // tiles with work >= long_thr (a multiple of 16: whole bins) are the first entries of the order: their number.
-  // The order WITHIN a bin is the arrival order of the LDS atomics above, so a cap that cut through a bin would make
-  // the set of tiles the backward splits depend on timing.  The cap therefore takes whole bins only: the longest
-  // prefix of bins (from the top, down to the threshold's) whose tiles number at most long_max — if the top bin alone
-  // holds more, nothing is split.  A threshold above the top bin (work >> 4 is clamped to 1023) splits nothing either.
-  if (n_long) {
-    const uint32_t bin = long_thr >> 4;
-    if (bin > 1023u) {
-      if (tid == 0) *n_long = 0u;
-    } else {
-      // base[k] = inclusive count of bins 1023 .. 1023 - k, non-decreasing in k: exactly one thread writes
-      const uint32_t kmax = 1023u - bin;
-      const uint32_t k = (uint32_t)tid;
-      if (k <= kmax && base[k] <= long_max && (k == kmax || base[k + 1] > long_max)) *n_long = base[k];
-      if (tid == 0 && base[0] > long_max) *n_long = 0u;
-    }
-  }
+  tile_order_body<FROM_RANGES>(work_in, ranges, num_tiles, order, n_long, long_thr, long_max);
 }
 
 int launch_tile_order(const uint32_t* work, int num_tiles, uint32_t* order, hipStream_t st, uint32_t* n_long,
@@ -1066,7 +1020,9 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
       // arrival slots of the survivors live in rank_of until ds_rank_kernel overwrites it with the final ranks
       hipLaunchKernelGGL(ds_hist_kernel, grid, block, 0, st, P, gs.depth_key, gs.ds_head, gs.ds_cnt, gs.rank_of);
       PINGS_LAUNCH_CHECK();
-      PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(gs.temp, tb, gs.ds_cnt, gs.ds_off, DS_NB + (int)grid.x + 1, st));
+      if (int e = raster_scan_u32(gs.ds_cnt, DS_NB + (int64_t)grid.x + 1, false, gs.ds_off, gs.temp, gs.temp_bytes,
+                                  knobs.library_scan, st))
+        return e;
       hipLaunchKernelGGL(ds_scatter_kernel, grid, block, 0, st, P, gs.depth_key, gs.ds_head, gs.ds_off, gs.rank_of,
                          gs.depth_key_sorted, gs.ds_idx, gs.gidx_sorted);
       PINGS_LAUNCH_CHECK();
@@ -1112,9 +1068,8 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
     PINGS_LAUNCH_CHECK();
     {
       pings::prof::Scope ps("tile_count_scan", st);
-      tb = gs.temp_bytes;
-      PINGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(gs.temp, tb, gs.tiles_sorted, gs.offsets_sorted,
-                                                       P, st));
+      if (int e = raster_scan_u32(gs.tiles_sorted, P, true, gs.offsets_sorted, gs.temp, gs.temp_bytes, knobs.library_scan, st))
+        return e;
     }
     {
       const auto t_start = std::chrono::steady_clock::now();

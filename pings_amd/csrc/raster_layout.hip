@@ -26,6 +26,8 @@ static size_t sort_temp_bytes(int64_t n) {
   if (c > a) a = c;
   // the tile sort: the library's scratch (its values come from a counting iterator: its own size) or the digit table
   a = std::max(a, std::max(tile_sort_library_bytes(n), tile_sort_table_bytes(n)));
+  // the scans: the library's scratch or the totals table
+  a = std::max(a, raster_scan_bytes(std::max<int64_t>(n, DS_NB + n / 256 + 2)));
   return align_up(a > b ? a : b) + 256;
 }
 
@@ -135,10 +137,7 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
   b.pair_owner = c.take<uint32_t>(b.np_max);
   b.partials = c.take<float>(b.np_max * GRAD_ROW);
   b.tau_partials = c.take<float>((size_t)ceil_div((int)np, 256) * 6);
-  size_t a = 0, d = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(ni + 1));
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, d, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(np + 1));
-  b.temp_bytes = align_up(a > d ? a : d) + 256;
+  b.temp_bytes = std::max(raster_scan_bytes((int64_t)ni + 1), raster_scan_bytes((int64_t)np + 1));
   b.temp = c.take<char>(b.temp_bytes);
   b.rows = c.take<float>(n * GRAD_ROW);
   b.total = c.off;
@@ -161,6 +160,8 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
 //   PINGS_DEPTH_SORT        bucket | l(ibrary)        tests         first letter l: rocPRIM radix sort instead of the bucket sort
 //   PINGS_TILE_SORT         radix | l(ibrary)         tests, A/B    first letter l: rocPRIM radix sort instead of the two-pass sort of
 //                                                                   tile_sort.hip (more than 65,536 tiles: always the library)
+//   PINGS_RASTER_SCAN       own | l(ibrary)           tests, A/B    first letter l: hipcub::DeviceScan instead of the two-launch scans of
+//                                                                   raster_scan.hip (more than 16,777,216 elements: always the library)
 //   PINGS_OCC_AMIN          0.15 | x                  A/B           alpha below which a tile stays out of the occlusion budget, in [1/255, 0.99]
 //   PINGS_RASTER_RECT       tight | 3(sigma) | e(llipse)  bench, tests  tile-rectangle rule of preprocess_kernel, by first letter
 //   PINGS_MARK_VISIBLE      frustum | d(epth)         tests         first letter d: mark_visible tests depth only, the variant in which
@@ -189,6 +190,7 @@ RasterKnobs read_knobs() {
   if (const char* e = getenv("PINGS_RASTER_OCCLUSION")) k.occlusion = atoi(e) != 0;
   if (const char* e = getenv("PINGS_DEPTH_SORT")) k.library_sort = e[0] == 'l';
   if (const char* e = getenv("PINGS_TILE_SORT")) k.library_tile_sort = e[0] == 'l';
+  if (const char* e = getenv("PINGS_RASTER_SCAN")) k.library_scan = e[0] == 'l';
   // Tiles a Gaussian covers with less than this alpha everywhere are left out of the occlusion budget: fewer entries
   // is still a lower bound of the opacity in front (conservative: the kept lists can only grow, results unchanged),
   // and the faint rim of every footprint was most of the budget pass's atomics.  Metric-1 sweep (r03): 1/255 -> 0.15

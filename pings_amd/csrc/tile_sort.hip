@@ -51,15 +51,6 @@ __global__ __launch_bounds__(TS_THREADS) void tile_sort_hist_kernel(const KeyT* 
   if (tid < nbins) table[(size_t)tid * nblk + blockIdx.x] = cnt[tid];
 }
 
-__device__ inline uint32_t wave_inclusive_sum(uint32_t v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const uint32_t u = __shfl_up(v, d, 64);
-    if (lane >= d) v += u;
-  }
-  return v;
-}
-
 // bases[i] = counts[0] + .. + counts[i - 1].  A workgroup owns TS_SCAN_CHUNK words and adds up everything in front of
 // them itself (whole chunks: 16-byte loads, workgroup g reads g of them per thread): no carry is handed from workgroup
 // to workgroup, so none waits and there is no state to clear.  The reads in front grow with the square of the table;
