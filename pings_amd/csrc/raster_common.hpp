@@ -91,6 +91,8 @@ struct GeomState {
   uint16_t* occ_bsat;                       // [num_tiles] last rank bucket a tile still needs (0xFFFF = all)
   unsigned long long* occ_mask;             // [occ_nb][occ_words] bit (tile % 64) of word tile / 64: bucket <= occ_bsat[tile]
   uint32_t* nvalid;                         // [1] Gaussians that survived culling (= ranks with a real depth key)
+  uint32_t* occ_bmax;                       // [1] largest occ_bsat over the tiles, occ_nb - 1 if one never saturates;
+                                            //     behind `stats`, cleared with them
   uint32_t* ds_head;                        // depth sort: header (key range shards, range, overflow flag), then
   uint32_t *ds_cnt, *ds_fill, *ds_off;      //   [DS_NB + blocks] bucket / per-block culled counts, [DS_NB] fill cursors,
   char* zero_begin; size_t zero_bytes;      // occ_bucket .. stats .. ds_head: the frame's one memset

@@ -695,10 +695,12 @@ __global__ __launch_bounds__(256) void occl_budget_kernel(int P, int gx, int nb,
 // Epilogue: the tile bitmasks of the row walks.  The workgroup's 64 tiles are one word of every bucket's mask
 // (word blockIdx.x of `words` = gridDim.x): wave g ballots `bucket <= bsat` for each bucket of its group and lane u
 // stores the word of the group's bucket u.  Bits of tiles from num_tiles on are 0.  With the budget all zero (the
-// occlusion bound switched off) every tile comes out as OCC_ALL and every mask as all ones.
+// occlusion bound switched off) every tile comes out as OCC_ALL and every mask as all ones.  `bmax` (zero before the
+// launch) receives the largest last needed bucket over the tiles, nb - 1 as soon as one tile never saturates.
 __global__ __launch_bounds__(512) void occl_scan_kernel(int num_tiles, int nb, const uint32_t* __restrict__ bucket,
                                                         uint16_t* __restrict__ bsat,
-                                                        unsigned long long* __restrict__ mask) {
+                                                        unsigned long long* __restrict__ mask,
+                                                        uint32_t* __restrict__ bmax) {
   __shared__ uint32_t sSum[8][64];
   __shared__ uint32_t sSat[64];
   const int t = threadIdx.x & 63, g = threadIdx.x >> 6;
@@ -736,6 +738,12 @@ __global__ __launch_bounds__(512) void occl_scan_kernel(int num_tiles, int nb, c
   }
   __syncthreads();
   const uint32_t sat = tile < num_tiles ? sSat[t] : 0u;
+  if (g == 0) {   // the last bucket any tile needs (count_kept_kernel): an integer maximum, order independent
+    uint32_t m = min(sat, (uint32_t)nb - 1u);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, o, 64));
+    if (t == 0) atomicMax(bmax, m);
+  }
   unsigned long long word = 0ull;
   for (int u = 0; u < per; ++u) {
     const unsigned long long w = __ballot(tile < num_tiles && (uint32_t)(g * per + u) <= sat);
@@ -744,12 +752,16 @@ __global__ __launch_bounds__(512) void occl_scan_kernel(int num_tiles, int nb, c
   if (t < per) mask[(size_t)(g * per + t) * gridDim.x + blockIdx.x] = word;
 }
 
-// kept tiles per depth rank (the Gaussian's rank bucket must not exceed the tile's last needed bucket)
+// kept tiles per depth rank (the Gaussian's rank bucket must not exceed the tile's last needed bucket).  A rank whose
+// bucket lies behind the last one ANY tile needs (occl_scan_kernel's bmax) keeps nothing and walks nothing: where every
+// tile saturates (the headline, closed rooms) that is most of the visible Gaussians; where one tile sees sky bmax is
+// nb - 1 and nothing changes.  Its rectangle is still loaded: the footprint statistics count every pair.
 __global__ __launch_bounds__(256) void count_kept_kernel(int P, int gx, int nb, int words,
                                                          const uint32_t* __restrict__ gidx_sorted,
                                                          const uint4* __restrict__ rect,
                                                          const unsigned long long* __restrict__ mask,
                                                          const uint32_t* __restrict__ nvalid,
+                                                         const uint32_t* __restrict__ bmax,
                                                          uint32_t* __restrict__ tiles_sorted,
                                                          unsigned long long* __restrict__ pairs_full) {
   const int r = strided_rank(P);
@@ -757,7 +769,7 @@ __global__ __launch_bounds__(256) void count_kept_kernel(int P, int gx, int nb, 
   const uint32_t nv = *nvalid;
   const RectLane me = rect_lane(r, gidx_sorted, rect, nv);
   const uint32_t bk = rank_bucket(r, nb, nv);
-  const uint32_t items = rect_items(me);
+  const uint32_t items = bk <= *bmax ? rect_items(me) : 0u;
   uint32_t kept = 0, acc = 0;
   if (items != 0u && items <= (uint32_t)SMALL_ITEMS)
     walk_items_serial(me, items, gx, mask + (size_t)bk * words,
@@ -1047,15 +1059,16 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
       // with the bound off the budget is still all zero: every tile keeps every rank bucket (OCC_ALL, masks all ones);
       // nvalid stays: rect_lane skips the culled ranks with it
       pings::prof::Scope ps("occl_scan", st);
+      // a retry clears again what the first attempt left: the statistics and, behind them, occ_bmax
+      if (attempt > 0) PINGS_HIP_CHECK(hipMemsetAsync(gs.stats, 0, (3 * STAT_SHARDS + 1) * sizeof(unsigned long long), st));
       hipLaunchKernelGGL(occl_scan_kernel, dim3(gs.occ_words), dim3(512), 0, st, num_tiles, gs.occ_nb, gs.occ_bucket,
-                         gs.occ_bsat, gs.occ_mask);
+                         gs.occ_bsat, gs.occ_mask, gs.occ_bmax);
       PINGS_LAUNCH_CHECK();
     }
     {
       pings::prof::Scope ps("tile_count_scan", st);
-      if (attempt > 0) PINGS_HIP_CHECK(hipMemsetAsync(gs.stats, 0, 3 * STAT_SHARDS * sizeof(unsigned long long), st));
       hipLaunchKernelGGL(count_kept_kernel, grid, block, 0, st, P, kp.gx, gs.occ_nb, gs.occ_words, gs.gidx_sorted,
-                         gs.rect, gs.occ_mask, gs.nvalid, gs.tiles_sorted, gs.stats);
+                         gs.rect, gs.occ_mask, gs.nvalid, gs.occ_bmax, gs.tiles_sorted, gs.stats);
       PINGS_LAUNCH_CHECK();
     }
     // The summary needs nothing of the instance scan (the kept total is one of count_kept_kernel's 64-bit statistics),
