@@ -799,7 +799,7 @@ PINGS_API int pings_image_losses_backward(const pings_image_loss_params* p, cons
  *   PINGS_HEAD_COLOR     out_value[B, C] = sum_j w_j sigmoid(raw_j)              (Decoder.regress_color, decoder.py:133-134)
  *   PINGS_HEAD_SEMANTIC  out_label[B] = argmax_c sum_j w_j log_softmax(raw_j)[c], first maximum as torch.argmax
  *                        (Decoder.sem_label_prob, decoder.py:119-122); out_value (nullable) receives the [B, C] sums
- * k <= 16.  One streaming pass instead of three to five torch passes per head. */
+ * PINGS_HEAD_SEMANTIC needs k <= 16 (PINGS_ERR_ARG otherwise); PINGS_HEAD_COLOR takes any k >= 1.  One streaming pass instead of three to five torch passes per head. */
 #define PINGS_HEAD_COLOR 0
 #define PINGS_HEAD_SEMANTIC 1
 PINGS_API int pings_head_reduce(const float* raw, const float* weight, int64_t B, int32_t k, int32_t C, int32_t mode,

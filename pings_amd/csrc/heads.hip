@@ -64,7 +64,7 @@ __global__ __launch_bounds__(256) void head_sem_kernel(long long B, int k, int C
 
 PINGS_API int pings_head_reduce(const float* raw, const float* weight, int64_t B, int32_t k, int32_t C, int32_t mode,
                                 float* out_value, int64_t* out_label, void* stream) {
-  PINGS_ARG_CHECK(B >= 0 && k >= 1 && k <= kMaxK && C >= 1, "bad shape");
+  PINGS_ARG_CHECK(B >= 0 && k >= 1 && C >= 1, "bad shape");
   if (B == 0) return PINGS_OK;
   PINGS_ARG_CHECK(raw != nullptr, "null input");
   hipStream_t st = pings::as_stream(stream);
@@ -74,6 +74,8 @@ PINGS_API int pings_head_reduce(const float* raw, const float* weight, int64_t B
     const long long n = (long long)B * C;
     head_color_kernel<<<(unsigned)((n + 255) / 256), 256, 0, st>>>(B, k, C, raw, weight, out_value);
   } else if (mode == PINGS_HEAD_SEMANTIC) {
+    // one log-sum-exp and one weight per neighbour stay in registers; the colour kernel loops over k and has no limit
+    PINGS_ARG_CHECK(k <= kMaxK, "semantic head: k > 16");
     PINGS_ARG_CHECK(out_label != nullptr, "semantic head needs out_label");
     head_sem_kernel<<<(unsigned)((B + 255) / 256), 256, 0, st>>>(B, k, C, raw, weight, out_value,
                                                                  reinterpret_cast<long long*>(out_label));

@@ -26,8 +26,8 @@ from . import neural_points as _np
 
 def head_reduce(raw: torch.Tensor, w_knn, mode: int):
     """`pings_head_reduce` (csrc/heads.hip): raw = decoder outputs [B, k, C] (per-neighbour) or [B, C] (`weighted_first`),
-    w_knn = IDW weights [B, k, 1] or None.  mode _abi.HEAD_COLOR -> colours [B, C]; _abi.HEAD_SEMANTIC -> int64
-    labels [B]."""
+    w_knn = IDW weights [B, k, 1] or None.  mode _abi.HEAD_COLOR -> colours [B, C] (any k); _abi.HEAD_SEMANTIC -> int64
+    labels [B] (the kernel for k <= 16, the reference's torch composition on the device beyond)."""
     L = _lib.lib()
     raw = raw.detach().to(torch.float32).contiguous()
     if raw.dim() == 2:
@@ -36,6 +36,15 @@ def head_reduce(raw: torch.Tensor, w_knn, mode: int):
         B, k, Cn = raw.shape
         w = None if w_knn is None else w_knn.detach().to(torch.float32).reshape(B, k).contiguous()
     dev = raw.device
+    if mode == _abi.HEAD_SEMANTIC and k > 16:
+        # the semantic kernel holds one log-sum-exp and one weight per neighbour in registers (k <= 16); a larger
+        # query_nn_k takes the reference's composition (Decoder.sem_label_prob, decoder.py:119-122, then the IDW sum)
+        if not raw.is_cuda:
+            raise _lib.PingsHipError("pings_amd ops run on the HIP device only (got a CPU tensor); "
+                                     "there is no CPU fallback")
+        prob = torch.log_softmax(raw, dim=-1)
+        prob = prob.sum(dim=1) if w is None else (prob * w.unsqueeze(-1)).sum(dim=1)
+        return torch.argmax(prob, dim=1)
     val = torch.empty(B, Cn, device=dev) if mode == _abi.HEAD_COLOR else None
     lab = torch.empty(B, dtype=torch.int64, device=dev) if mode == _abi.HEAD_SEMANTIC else None
     _lib.check(L.pings_head_reduce(_lib.ptr(raw), _lib.ptr(w), B, k, Cn, mode, _lib.ptr(val), _lib.ptr(lab),
