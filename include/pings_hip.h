@@ -459,6 +459,29 @@ PINGS_API int pings_sdf_forward(const pings_knn_map* m, const pings_sdf_decoder*
 PINGS_API int pings_sdf_plan(int nn_k, int feat_dim, int hidden, int weighted_first, int order, int misaligned,
                              int32_t* out);
 
+/* Fused colour query with its Jacobian (csrc/knn_color.hip): the colour head of Tracker.query_source_points
+ * (utils/tracker.py:328-336) for the photometric term and the colour-consistency weight of the tracker.
+ * One hidden level, ReLU, biases, sigmoid on the output (Decoder.regress_color, model/decoder.py:133). */
+typedef struct pings_color_decoder {
+  const float* W1;        /* [hidden, Fc+3] layers.0.weight                  */
+  const float* b1;        /* [hidden]                                        */
+  const float* W2;        /* [channels, hidden] lout.weight                  */
+  const float* b2;        /* [channels]                                      */
+  int32_t hidden;         /* <= 64                                           */
+  int32_t feat_dim;       /* Fc (<= 61)                                      */
+  int32_t channels;       /* 1..3                                            */
+  int32_t weighted_first; /* config.weighted_first                           */
+} pings_color_decoder;
+/* color[B,channels] and, when `jac` is not NULL, jac[B,channels,3] = d colour / d query (through the neighbour vectors
+ * and through the inverse-distance weights).  idx[B,nn_k]: rows of the tables passed (`features` [rows,Fc], `points`
+ * [rows,3], `orientations` [rows,4] wxyz, read when after_pgo), -1 = no neighbour: what pings_sdf_forward(idx_out) and
+ * pings_knn_search emit, so the search is not repeated.  A query without a neighbour gets colour 0 (sigmoid(mlp(0)) in
+ * weighted_first mode) and a zero Jacobian.  No side effects. */
+PINGS_API int pings_color_forward(const pings_color_decoder* dec, const float* features, int64_t rows,
+                                  const float* points, const float* orientations, int32_t after_pgo,
+                                  const float* queries, int64_t B, const int64_t* idx, int32_t nn_k, float* color,
+                                  float* jac, void* stream);
+
 /* First-order backward of the fused query w.r.t. the feature table and the decoder
  * (the training path of Mapper.sdf_mapping, utils/mapper.py:822-970: loss(sdf).backward()).
  *   dL_dfeatures[rows,F]  dense, every row written (zero where no query touched the row)
@@ -873,6 +896,28 @@ PINGS_API int pings_reg_partials(int64_t n);
 PINGS_API int pings_reg_transform(const pings_reg_loop_args* a, void* stream);
 PINGS_API int pings_reg_assemble(const pings_reg_loop_args* a, void* stream);
 PINGS_API int pings_reg_step(const pings_reg_loop_args* a, void* stream);
+/* `assemble` with the tracker's colour terms (utils/tracker.py:485-535, :692-737), for the configurations with
+ * color_on and photometric_loss_on or consist_wieght_on.  Writes the same `part` layout as pings_reg_assemble, so
+ * pings_reg_step runs behind it unchanged: the reference sums the geometric and the photometric system before damping.
+ * Intensity I = the one channel, or 0.144 c0 + 0.299 c1 + 0.587 c2 of three (utils/tools.py:723), of source colour,
+ * prediction and Jacobian rows alike.
+ *   PINGS_REG_COLOR_PHOTO    N += w photo_weight J_c^T J_c, g -= w photo_weight r_c J_c with r_c = I_pred - I_src and
+ *                            J_c = [p x grad I, grad I]; the weight is the geometric one
+ *   PINGS_REG_COLOR_CONSIST  w *= exp(-|I_src - I_pred|); color_jac is not read
+ * Validity is the SDF's alone; the colours of an invalid point are not read.  photo_part[block] = sum |I_pred - I_src|
+ * over the block's valid points.  Set PINGS_REG_F_WEIGHTED in a->flags: the reference's w is a tensor on this path. */
+#define PINGS_REG_COLOR_PHOTO 1
+#define PINGS_REG_COLOR_CONSIST 2
+typedef struct pings_reg_color_args {
+  const float* src_color;        /* [n,channels] measured colours                                                  */
+  const float* color_pred;       /* [n,channels] pings_color_forward                                               */
+  const float* color_jac;        /* [n,channels,3] d colour / d point, or NULL (CONSIST)                           */
+  int32_t channels;              /* 1 or 3                                                                         */
+  int32_t mode;                  /* PINGS_REG_COLOR_*                                                              */
+  float photo_weight;            /* config.photometric_loss_weight                                                 */
+  double* photo_part;            /* [pings_reg_partials(n)] per-block sum |r_c|                                    */
+} pings_reg_color_args;
+PINGS_API int pings_reg_assemble_color(const pings_reg_loop_args* a, const pings_reg_color_args* c, void* stream);
 /* The one host read of an iteration: the 8 record words behind everything queued on `stream`, by the polled
  * read-back the other checked entry points use (not a launch function: it returns when the words have arrived). */
 PINGS_API int pings_reg_read_record(const int32_t* record_dev, int32_t* record_host, void* stream);

@@ -14,6 +14,7 @@ RASTER_SURFEL, RASTER_3DGS, RASTER_2DGS = 0, 1, 2                 # PINGS_RASTER
 HEAD_COLOR, HEAD_SEMANTIC = 0, 1                                  # PINGS_HEAD_*: pings_head_reduce mode
 REG_SINGULAR, REG_ILL_CONDITIONED, REG_NONFINITE = 1, 2, 4        # PINGS_REG_*: pings_reg_solve_checked status bits
 REG_F_NORMALS, REG_F_DIV_GRAD, REG_F_WEIGHTED = 1, 2, 4           # PINGS_REG_F_*: pings_reg_loop_args.flags
+REG_COLOR_PHOTO, REG_COLOR_CONSIST = 1, 2                         # PINGS_REG_COLOR_*: pings_reg_color_args.mode
 MC_ALLOW_DEGENERATE, MC_ASCENT = 1, 2                             # PINGS_MC_*: pings_mc_count / pings_mc_emit flags
 ADAMW_MAX_JOBS, ADAMW_CHUNK = 48, 4096                            # PINGS_ADAMW_*: tensors per launch, elements per item
 EVAL_VIEW_RECORD, EVAL_PAIR_RECORD = 9, 12                        # PINGS_EVAL_*_RECORD: doubles per record
@@ -60,6 +61,12 @@ class SdfDecoder(C.Structure):
                 ("weighted_first", C.c_int32)]
 
 
+class ColorDecoder(C.Structure):
+    _fields_ = [("W1", C.c_void_p), ("b1", C.c_void_p), ("W2", C.c_void_p), ("b2", C.c_void_p),
+                ("hidden", C.c_int32), ("feat_dim", C.c_int32), ("channels", C.c_int32),
+                ("weighted_first", C.c_int32)]
+
+
 class MlpJob(C.Structure):
     _fields_ = [("x", C.c_void_p), ("IN", C.c_int32), ("OUT", C.c_int32), ("W1", C.c_void_p), ("b1", C.c_void_p),
                 ("W2", C.c_void_p), ("b2", C.c_void_p), ("y", C.c_void_p), ("dL_dy", C.c_void_p), ("dL_dx", C.c_void_p),
@@ -89,6 +96,11 @@ class RegLoopArgs(C.Structure):
                 ("gm_grad", C.c_float), ("lm_lambda", C.c_float)] + \
                [(k, C.c_void_p) for k in ("src", "cur", "sdf", "grad", "std", "mask", "label", "normals", "valid",
                                           "part", "T", "delta", "record", "trace")]
+
+
+class RegColorArgs(C.Structure):
+    _fields_ = [("src_color", C.c_void_p), ("color_pred", C.c_void_p), ("color_jac", C.c_void_p),
+                ("channels", C.c_int32), ("mode", C.c_int32), ("photo_weight", C.c_float), ("photo_part", C.c_void_p)]
 
 
 class GaussLossArgs(C.Structure):
@@ -188,6 +200,7 @@ SIGNATURES = {
     "pings_sdf_forward": (i32, [C.POINTER(KnnMap), C.POINTER(SdfDecoder), vp, vp, vp, vp, i32, vp, i64, vp, vp, vp, vp,
                                 vp, vp, vp, vp, vp]),
     "pings_sdf_plan": (i32, [i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32)]),
+    "pings_color_forward": (i32, [C.POINTER(ColorDecoder), vp, i64, vp, vp, i32, vp, i64, vp, i32, vp, vp, vp]),
     "pings_sdf_backward_scratch_bytes": (sz, [i64, i32, i32, i32, i64]),
     "pings_sdf_double_backward": (i32, [C.POINTER(SdfDecoder), vp, i64, vp, vp, vp, i32, vp, i64, i32, vp, vp, vp, vp,
                                         vp, vp, vp, vp, vp, vp, vp]),
@@ -265,6 +278,7 @@ SIGNATURES = {
     "pings_reg_transform": (i32, [C.POINTER(RegLoopArgs), vp]),
     "pings_reg_assemble": (i32, [C.POINTER(RegLoopArgs), vp]),
     "pings_reg_step": (i32, [C.POINTER(RegLoopArgs), vp]),
+    "pings_reg_assemble_color": (i32, [C.POINTER(RegLoopArgs), C.POINTER(RegColorArgs), vp]),
     "pings_reg_read_record": (i32, [vp, vp, vp]),
     # Gaussian-space loss block
     "pings_gauss_loss_select": (i32, [C.POINTER(GaussLossArgs), vp]),

@@ -240,6 +240,106 @@ __global__ __launch_bounds__(256) void reg_assemble_kernel(pings_reg_loop_args a
         ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
+// reg_assemble_kernel with the colour terms of registration_step (utils/tracker.py:485-535) and implicit_color_reg
+// (:692-737).  The reference sums the geometric and the photometric system before damping (N = N_geo + lambda N_col, g
+// likewise), so both go into the same 27 sums and reg_step_kernel runs behind this kernel as it stands.  PHOTO: residual
+// r_c = I_pred - I_src and J_c = [p x grad I, grad I] of the intensity (the one channel, or 0.144 c0 + 0.299 c1 +
+// 0.587 c2 of three: utils/tools.py:723, applied to colours and Jacobian rows alike).  CONSIST: the weight is multiplied
+// by exp(-|I_src - I_pred|), no Jacobian is read.  Validity is the SDF's alone; an invalid point's colours are not read.
+__device__ inline float reg_intensity(const float* __restrict__ c, int channels) {
+  return channels == 3 ? (0.144f * c[0] + 0.299f * c[1]) + 0.587f * c[2] : c[0];
+}
+
+__global__ __launch_bounds__(256) void reg_assemble_color_kernel(pings_reg_loop_args a, pings_reg_color_args ca) {
+  __shared__ double red[4][kLoopTerms];
+  double acc[kLoopTerms];
+#pragma unroll
+  for (int k = 0; k < kLoopTerms; ++k) acc[k] = 0.0;
+  const bool normals = (a.flags & PINGS_REG_F_NORMALS) && a.normals, div = a.flags & PINGS_REG_F_DIV_GRAD;
+  const bool photo = ca.mode == PINGS_REG_COLOR_PHOTO;
+  const int C = ca.channels;
+  const double lam = (double)ca.photo_weight;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < a.n; i += (long long)gridDim.x * blockDim.x) {
+    const float gx = a.grad[3 * i], gy = a.grad[3 * i + 1], gz = a.grad[3 * i + 2];
+    const float gn = sqrtf((gx * gx + gy * gy) + gz * gz);
+    const bool ok = a.mask[i] && gn < a.max_grad && gn > a.min_grad && a.std[i] < a.max_std;
+    if (a.valid) a.valid[i] = ok;
+    if (!ok) continue;
+    float sdf = a.sdf[i];
+    if (div) sdf = sdf / gn;
+    const float r = sdf - a.label[i];
+    float w = 1.f;
+    if (a.gm_dist > 0.f) { const float q = a.gm_dist / (a.gm_dist + r * r); w = q * q; }          // w_res
+    if (a.gm_grad > 0.f) {                                                                        // * w_grad
+      const float an = gn - 1.f, q = a.gm_grad / (a.gm_grad + an * an);
+      w = w * (q * q);
+    }
+    if (normals) {                                                                                // * w_normal
+      const float den = gn + 1e-7f;
+      const float ux = gx / den, uy = gy / den, uz = gz / den;
+      const float d = (a.normals[3 * i] * ux + a.normals[3 * i + 1] * uy) + a.normals[3 * i + 2] * uz;
+      w = w * (0.5f + fabsf(d));
+    }
+    const float i_src = reg_intensity(ca.src_color + (size_t)i * C, C);
+    const float i_pred = reg_intensity(ca.color_pred + (size_t)i * C, C);
+    const float rc = i_pred - i_src;
+    if (!photo) w = w * expf(-fabsf(i_src - i_pred));                                             // * w_color
+    const float px = a.cur[3 * i], py = a.cur[3 * i + 1], pz = a.cur[3 * i + 2];
+    float J[6], Jc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    J[0] = py * gz - pz * gy;
+    J[1] = pz * gx - px * gz;
+    J[2] = px * gy - py * gx;
+    J[3] = gx; J[4] = gy; J[5] = gz;
+    if (photo) {
+      const float* jc = ca.color_jac + (size_t)i * C * 3;
+      float cx, cy, cz;
+      if (C == 3) {
+        cx = (0.144f * jc[0] + 0.299f * jc[3]) + 0.587f * jc[6];
+        cy = (0.144f * jc[1] + 0.299f * jc[4]) + 0.587f * jc[7];
+        cz = (0.144f * jc[2] + 0.299f * jc[5]) + 0.587f * jc[8];
+      } else {
+        cx = jc[0]; cy = jc[1]; cz = jc[2];
+      }
+      Jc[0] = py * cz - pz * cy;
+      Jc[1] = pz * cx - px * cz;
+      Jc[2] = px * cy - py * cx;
+      Jc[3] = cx; Jc[4] = cy; Jc[5] = cz;
+    }
+    const double wd = (double)w, rd = (double)r, wl = wd * lam, rcd = (double)rc;
+    int k = 0;
+#pragma unroll
+    for (int p = 0; p < 6; ++p) {
+      const double wa = wd * (double)J[p], wc = wl * (double)Jc[p];
+#pragma unroll
+      for (int q = p; q < 6; ++q) acc[k++] += wa * (double)J[q] + wc * (double)Jc[q];
+      acc[21 + p] -= wa * rd + wc * rcd;
+    }
+    acc[27] += 1.0;
+    acc[28] += wd;
+    acc[29] += fabs(rd);
+    acc[30] += wd * rd * rd;
+    acc[31] += fabs(rcd);
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < kLoopTerms; ++k) {
+    double v = acc[k];
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
+    if (lane == 0) red[wave][k] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kLoopTerms) {
+    const double v = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+    // slot 31 of `part` stays the pad it is today (0); sum |r_c| has a buffer of its own
+    if (threadIdx.x < kLoopTerms - 1) a.part[(size_t)blockIdx.x * kLoopTerms + threadIdx.x] = v;
+    else {
+      a.part[(size_t)blockIdx.x * kLoopTerms + threadIdx.x] = 0.0;
+      ca.photo_part[blockIdx.x] = v;
+    }
+  }
+}
+
 // The update of one iteration (utils/tracker.py:407-413, :494-497, :608-689, :121-168) in one workgroup of 64
 __global__ __launch_bounds__(64) void reg_step_kernel(pings_reg_loop_args a, int nblocks) {
   __shared__ double tot[kLoopTerms];
@@ -368,6 +468,23 @@ PINGS_API int pings_reg_assemble(const pings_reg_loop_args* a, void* stream) {
   hipStream_t st = pings::as_stream(stream);
   pings::prof::Scope sc("reg_assemble", st);
   reg_assemble_kernel<<<loop_blocks(a->n), 256, 0, st>>>(*a);
+  PINGS_LAUNCH_CHECK();
+  return PINGS_OK;
+}
+
+PINGS_API int pings_reg_assemble_color(const pings_reg_loop_args* a, const pings_reg_color_args* c, void* stream) {
+  PINGS_ARG_CHECK(a && a->n >= 0 && a->part, "bad argument");
+  PINGS_ARG_CHECK(a->n == 0 || (a->cur && a->sdf && a->grad && a->std && a->mask && a->label), "null input");
+  PINGS_ARG_CHECK(!(a->flags & PINGS_REG_F_NORMALS) || a->normals, "PINGS_REG_F_NORMALS without normals");
+  PINGS_ARG_CHECK((a->flags & ~7) == 0, "unknown flag");
+  PINGS_ARG_CHECK(c && c->photo_part, "null colour arguments");
+  PINGS_ARG_CHECK(c->channels == 1 || c->channels == 3, "channels must be 1 or 3");
+  PINGS_ARG_CHECK(c->mode == PINGS_REG_COLOR_PHOTO || c->mode == PINGS_REG_COLOR_CONSIST, "unknown colour mode");
+  PINGS_ARG_CHECK(a->n == 0 || (c->src_color && c->color_pred), "null colours");
+  PINGS_ARG_CHECK(a->n == 0 || c->mode != PINGS_REG_COLOR_PHOTO || c->color_jac, "the photometric term needs color_jac");
+  hipStream_t st = pings::as_stream(stream);
+  pings::prof::Scope sc("reg_assemble_color", st);
+  reg_assemble_color_kernel<<<loop_blocks(a->n), 256, 0, st>>>(*a, *c);
   PINGS_LAUNCH_CHECK();
   return PINGS_OK;
 }

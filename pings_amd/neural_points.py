@@ -727,17 +727,22 @@ def _sdf_composed(npm, decoder, x, need_grad=False, need_certainty=False, query_
 
 def sdf_fused(npm, decoder, x: torch.Tensor, need_grad: bool = False, need_certainty: bool = False,
               query_locally: bool = True, use_only_measured_points: bool = True,
-              use_only_valid_points: bool = False, need_std: bool = False):
+              use_only_valid_points: bool = False, need_std: bool = False, want_idx: bool = False):
     """Fused inference query = `Mapper.sdf(x)` under no_grad (utils/mapper.py:2273-2289) and, with
     need_grad, the analytic gradient the tracker asks autograd for (utils/tracker.py:282-321).
 
     Returns (sdf[B], grad[B,3] | None, nn_counts[B], certainty[B] | None) and, with need_std, a fifth value
     sdf_std[B] (spread of the per-neighbour predictions, utils/tracker.py:303-313).  `decoder` is the
     reference's `Decoder` (model/decoder.py) with one hidden level, or any object with
-    `layers[0].weight/.bias`, `lout.weight/.bias`, `sdf_scale`."""
+    `layers[0].weight/.bias`, `lout.weight/.bias`, `sdf_scale`.  With want_idx the neighbour rows idx[B,k] (int64, -1 =
+    none; rows of the local or global tables, as queried) are appended: what `color_fused` takes."""
     if not fused_supported(npm, decoder):
-        return _sdf_composed(npm, decoder, x, need_grad, need_certainty, query_locally, use_only_measured_points,
-                             use_only_valid_points, need_std)
+        res = _sdf_composed(npm, decoder, x, need_grad, need_certainty, query_locally, use_only_measured_points,
+                            use_only_valid_points, need_std)
+        if want_idx:
+            res = res + (radius_neighborhood_topk(npm, x, bool(npm.temporal_local_map_on and query_locally),
+                                                  use_only_measured_points, use_only_valid_points, query_locally)[0],)
+        return res
     L = _lib.lib()
     q = x.detach().to(torch.float32).contiguous()
     B = q.shape[0]
@@ -764,14 +769,70 @@ def sdf_fused(npm, decoder, x: torch.Tensor, need_grad: bool = False, need_certa
     cnt = torch.empty(B, dtype=torch.int64, device=dev)
     cert = torch.empty(B, dtype=torch.float32, device=dev) if need_certainty else None
     std = torch.empty(B, dtype=torch.float32, device=dev) if need_std else None
+    idx = torch.empty(B, a.nn_k, dtype=torch.int64, device=dev) if want_idx else None
     st = L.pings_sdf_forward(C.byref(a.c), C.byref(dec), _lib.ptr(feats), _lib.ptr(pts), _lib.ptr(quat),
                              _lib.ptr(cert_tab), int(bool(npm.after_pgo)), _lib.ptr(q), B, _lib.ptr(sdf),
-                             _lib.ptr(grad), _lib.ptr(cnt), _lib.ptr(cert), None, None, _lib.ptr(std), None,
+                             _lib.ptr(grad), _lib.ptr(cnt), _lib.ptr(cert), _lib.ptr(idx), None, _lib.ptr(std), None,
                              _lib.stream_ptr(dev))
     _lib.check(st, "pings_sdf_forward")
-    if need_std:
-        return sdf, grad, cnt, cert, std
-    return sdf, grad, cnt, cert
+    res = (sdf, grad, cnt, cert, std) if need_std else (sdf, grad, cnt, cert)
+    return res + (idx,) if want_idx else res
+
+
+def colour_fused_supported(npm, decoder) -> bool:
+    """Whether `color_fused` covers this (map, colour decoder) pair: one hidden level of at most 64 units, ReLU, biases,
+    1-3 output channels, Fc <= 61, no layer norm.  Everything else keeps the composed path (`query_feature` + the
+    decoder's own layers + autograd)."""
+    cfg = getattr(npm, "config", None)
+    if cfg is not None and getattr(cfg, "layer_norm_on", False):
+        return False
+    layers = getattr(decoder, "layers", None)
+    if layers is None or len(layers) != 1 or getattr(decoder, "use_leaky_relu", False):
+        return False
+    l0, lo = layers[0], decoder.lout
+    if l0.bias is None or lo.bias is None or not 1 <= int(lo.weight.shape[0]) <= 3:
+        return False
+    return int(l0.weight.shape[0]) <= 64 and int(l0.weight.shape[1]) - 3 <= 61 and _nn_k(npm) <= 16
+
+
+def color_fused(npm, decoder, x: torch.Tensor, idx: torch.Tensor, need_jac: bool = True, query_locally: bool = True):
+    """Fused colour query (`pings_color_forward`): colour[B,C] = IDW of sigmoid(colour decoder) over the neighbours
+    `idx[B,k]` (from `sdf_fused(want_idx=True)` or `radius_neighborhood_topk`, same `query_locally`) and, with need_jac,
+    jac[B,C,3] = d colour / d x, what utils/tracker.py:328-336 gets from one autograd pass per channel.  Returns
+    (colour, jac | None)."""
+    if not x.is_cuda:
+        raise _lib.PingsHipError("color_fused runs on the HIP device only (got a CPU tensor); there is no CPU fallback")
+    if not colour_fused_supported(npm, decoder):
+        raise _lib.PingsHipError("color_fused: this colour decoder is not covered by the fused kernel "
+                                 "(see colour_fused_supported)")
+    L = _lib.lib()
+    q = x.detach().to(torch.float32).contiguous()
+    B = q.shape[0]
+    cfg = getattr(npm, "config", None)
+    weighted_first = bool(cfg.weighted_first) if cfg is not None else bool(npm.weighted_first)
+    W1 = decoder.layers[0].weight.detach().to(torch.float32).contiguous()
+    b1 = decoder.layers[0].bias.detach().to(torch.float32).contiguous()
+    W2 = decoder.lout.weight.detach().to(torch.float32).contiguous()
+    b2 = decoder.lout.bias.detach().to(torch.float32).contiguous()
+    feats = (npm.local_color_features if query_locally else npm.color_features).detach().to(torch.float32).contiguous()
+    pts = (npm.local_neural_points if query_locally else npm.neural_points).detach().contiguous()
+    quat = (npm.local_point_orientations if query_locally else npm.point_orientations).detach().contiguous()
+    Fc, ch = int(feats.shape[1]), int(W2.shape[0])
+    if W1.shape[1] != Fc + 3:
+        raise ValueError(f"colour decoder input dim {W1.shape[1]} != colour feature dim {Fc} + 3")
+    ix = idx.detach().to(torch.int64).contiguous()
+    if ix.dim() != 2 or ix.shape[0] != B:
+        raise ValueError(f"idx must be [B, k] for B = {B} queries, got {tuple(ix.shape)}")
+    rows = min(int(feats.shape[0]), int(pts.shape[0]), int(quat.shape[0]))
+    dec = _abi.ColorDecoder(W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), int(W1.shape[0]), Fc, ch,
+                            int(weighted_first))
+    dev = q.device
+    col = torch.empty(B, ch, dtype=torch.float32, device=dev)
+    jac = torch.empty(B, ch, 3, dtype=torch.float32, device=dev) if need_jac else None
+    _lib.check(L.pings_color_forward(C.byref(dec), _lib.ptr(feats), rows, _lib.ptr(pts), _lib.ptr(quat),
+                                     int(bool(npm.after_pgo)), _lib.ptr(q), B, _lib.ptr(ix), int(ix.shape[1]),
+                                     _lib.ptr(col), _lib.ptr(jac), _lib.stream_ptr(dev)), "pings_color_forward")
+    return col, jac
 
 
 _SCRATCH_BYTES = {}

@@ -5,8 +5,9 @@ gradient, spread of the per-neighbour predictions, marching-cubes / registration
 point come from ONE fused kernel launch per batch (`pings_sdf_forward`: hash-grid kNN + feature gather + decoder +
 IDW + d/dx), where the reference runs query_feature, the decoder, an autograd backward through all of it and a
 dozen element-wise kernels, 50-100 times per frame.  Colour and semantic queries without a gradient run HIP
-`query_feature`, the head's decoder on the fused kernels and `pings_head_reduce`; the colour gradient of the photometric
-term (`query_color_grad`) keeps the reference's torch tail behind the HIP `query_feature`.
+`query_feature`, the head's decoder on the fused kernels and `pings_head_reduce`; the colour with its Jacobian for the
+photometric term (`query_color_grad`) is `pings_color_forward` on the neighbour rows the SDF launch emitted (one more
+launch; colour decoders it does not cover keep the reference's torch tail behind the HIP `query_feature`).
 
 `implicit_reg` — drop-in for the module-level function (utils/tracker.py:608-689): the 6x6 normal equations come from
 `pings_reg_normal_equations` (one pass, fp64 accumulation, fixed-order reduction); LM damping, the fp64 6x6 solve and
@@ -21,8 +22,11 @@ reference's host reads (compacted `valid_points`, the residual as a float).
 
 `install(tracker_module)` rebinds `query_source_points` and `implicit_reg`; `install(tracker_module, loop=True)` also
 rebinds `Tracker.tracking` and `Tracker.registration_step`, keeping the originals for what the loop delegates (the
-photometric and colour-consistency configurations, and the Open3D weight cloud of a `vis_result` run).  Host tensors
-raise: there is no CPU path (oracle/tracker_cpu.py is the CPU restatement used by the tests).
+photometric and colour-consistency configurations, and the Open3D weight cloud of a `vis_result` run).
+`install(tracker_module, loop=True, colour=True)` runs those two colour configurations in the device loop as well:
+SDF forward with the neighbour rows out, `pings_color_forward` on them, `pings_reg_assemble_color`, the unchanged
+`pings_reg_step`, one record read.  Host tensors raise: there is no CPU path (oracle/tracker_cpu.py is the CPU
+restatement used by the tests).
 """
 from __future__ import annotations
 
@@ -42,6 +46,7 @@ last_solve_status = None    # int32[1] device tensor of the most recent `implici
 # count, residual (cm), rotation (deg), translation (m), status bits, sum w, sum w r^2, 0, then dT row-major (16)
 last_trace = None
 _ORIG = {}                  # the reference's Tracker.tracking / registration_step, kept by install(loop=True)
+_COLOUR = False             # install(loop=True, colour=True): the colour configurations run in the device loop
 TRACE_ROW = 24
 
 
@@ -128,13 +133,18 @@ def query_source_points(self, coord, bs, query_sdf=True, query_sdf_grad=True, qu
     color_grad = torch.zeros(n, channels, 3, device=dev) if query_color_grad else None
     sem_pred = torch.zeros(n, device=dev) if query_sem else None
     npm = self.neural_points
+    # the photometric term: the fused colour kernel on the neighbour rows of the SDF launch, when it covers the decoder
+    colour_native = bool(query_color and query_color_grad) and _np.colour_fused_supported(npm, self.color_mlp)
     for k in range(iters):
         head, tail = k * bs, min((k + 1) * bs, n)
         x = coord[head:tail]
+        idx = None
         if query_sdf or query_mask or query_certainty:
-            s, g, cnt, cert, std = _np.sdf_fused(npm, self.sdf_mlp, x, need_grad=bool(query_sdf_grad),
-                                                 need_certainty=bool(query_certainty), query_locally=query_locally,
-                                                 use_only_valid_points=True, need_std=True)
+            s, g, cnt, cert, std, *rest = _np.sdf_fused(npm, self.sdf_mlp, x, need_grad=bool(query_sdf_grad),
+                                                        need_certainty=bool(query_certainty),
+                                                        query_locally=query_locally, use_only_valid_points=True,
+                                                        need_std=True, want_idx=colour_native)
+            idx = rest[0] if rest else None
             if iters == 1:   # the usual case (bs >= n): hand the kernel's outputs over, no zero fills, no slice copies
                 if query_sdf:
                     sdf_pred, sdf_std = s, std
@@ -171,7 +181,14 @@ def query_source_points(self, coord, bs, query_sdf=True, query_sdf_grad=True, qu
                                                       _abi.HEAD_SEMANTIC).to(sem_pred.dtype)
                 if query_color and not query_color_grad:
                     color_pred[head:tail] = head_reduce(_dec.mlp(self.color_mlp, cf), wk, _abi.HEAD_COLOR)
-        if query_color and query_color_grad:   # photometric term with its gradient: HIP query_feature + the reference's torch tail
+        if colour_native:
+            if idx is None:
+                idx = _np.radius_neighborhood_topk(npm, x, bool(npm.temporal_local_map_on and query_locally), True, True,
+                                                   query_locally)[0]
+            col, jac = _np.color_fused(npm, self.color_mlp, x, idx, need_jac=True, query_locally=query_locally)
+            color_pred[head:tail] = col
+            color_grad[head:tail] = jac
+        elif query_color and query_color_grad:   # decoders the kernel does not cover: HIP query_feature + the reference's torch tail
             xc = x.detach().clone().requires_grad_(bool(query_color_grad))
             _, color_feature, w_knn, _, _ = npm.query_feature(xc, accumulate_stability=False, query_locally=query_locally,
                                                               query_color_feature=True, use_only_valid_points=True)
@@ -198,7 +215,7 @@ class _Loop:
     """Buffers and argument block of one `tracking` / `registration_step` call (caller-owned scratch of the kernels)."""
 
     def __init__(self, self_, points, labels, normals, min_grad, max_grad, GM_dist, GM_grad, lm_lambda, weighted,
-                 pose, trace_rows=0, valid_out=False):
+                 pose, trace_rows=0, valid_out=False, colours=None, colour_mode=0):
         if not points.is_cuda:
             raise _lib.PingsHipError("tracking runs on the HIP device only (got a CPU tensor); there is no CPU fallback")
         cfg = self_.config
@@ -232,6 +249,14 @@ class _Loop:
         self.stream = _lib.stream_ptr(dev)
         self.bs = int(cfg.infer_bs)
         self.nn_k = int(getattr(cfg, "track_mask_query_nn_k", getattr(cfg, "query_nn_k", 4)))
+        self.colour = None
+        if colour_mode:
+            ch = int(cfg.color_channel)
+            self.src_colour = colours.detach().to(dev, torch.float32)[:, :ch].contiguous()
+            self.photo_part = torch.zeros(int(L.pings_reg_partials(self.n)), dtype=torch.float64, device=dev)
+            self.colour = _abi.RegColorArgs(self.src_colour.data_ptr(), None, None, ch, int(colour_mode),
+                                            float(getattr(cfg, "photometric_loss_weight", 0.0)),
+                                            self.photo_part.data_ptr())
 
     def transform(self):
         _lib.check(self.L.pings_reg_transform(C.byref(self.args), self.stream), "pings_reg_transform")
@@ -240,15 +265,24 @@ class _Loop:
     def iterate(self, self_, it, sync_tag):
         """query, assemble, step and the one host read; returns (valid count, status, residual cm, rot deg, tran m)."""
         a = self.args
-        # the colour query is skipped: no weight uses it in the configurations that reach this path
-        sdf, grad, _, _, _, mask, _, std = query_source_points(self_, self.cur, self.bs, True, True, False, False,
-                                                                query_certainty=False, query_locally=True,
-                                                                mask_min_nn_count=self.nn_k)
-        keep = [t.contiguous() for t in (sdf, grad, std, mask)]
+        if self.colour is None:
+            # the colour query is skipped: no weight uses it in the configurations that reach this path
+            sdf, grad, _, _, _, mask, _, std = query_source_points(self_, self.cur, self.bs, True, True, False, False,
+                                                                    query_certainty=False, query_locally=True,
+                                                                    mask_min_nn_count=self.nn_k)
+            keep = [t.contiguous() for t in (sdf, grad, std, mask)]
+        else:
+            keep = [None if t is None else t.contiguous() for t in self._query_colour(self_)]
+            c = self.colour
+            c.color_pred, c.color_jac = keep[4].data_ptr(), _lib.ptr(keep[5])
         a.sdf, a.grad, a.std = (t.data_ptr() for t in keep[:3])
         a.mask = keep[3].view(torch.uint8).data_ptr()
         a.iter = it
-        _lib.check(self.L.pings_reg_assemble(C.byref(a), self.stream), "pings_reg_assemble")
+        if self.colour is None:
+            _lib.check(self.L.pings_reg_assemble(C.byref(a), self.stream), "pings_reg_assemble")
+        else:
+            _lib.check(self.L.pings_reg_assemble_color(C.byref(a), C.byref(self.colour), self.stream),
+                       "pings_reg_assemble_color")
         _lib.check(self.L.pings_reg_step(C.byref(a), self.stream), "pings_reg_step")
         _lib.check(self.L.pings_reg_read_record(self.record.data_ptr(), C.addressof(self.host), self.stream),
                    "pings_reg_read_record")
@@ -258,6 +292,28 @@ class _Loop:
         raw = bytes(h)
         res, rot, tran = struct.unpack("<3d", raw[8:32])
         return int(h[0]), int(h[1]), res, rot, tran
+
+    def _query_colour(self, self_):
+        """(sdf, grad, std, mask, colour, jac | None) of the current points: per batch the SDF forward with its neighbour
+        rows out, then the colour forward on those rows (with the Jacobian for the photometric term only)."""
+        npm, jac_on = self_.neural_points, self.colour.mode == _abi.REG_COLOR_PHOTO
+        outs = []
+        for head in range(0, self.n, self.bs):
+            x = self.cur[head:head + self.bs]
+            s, g, cnt, _, std, idx = _np.sdf_fused(npm, self_.sdf_mlp, x, need_grad=True, need_certainty=False,
+                                                   query_locally=True, use_only_valid_points=True, need_std=True,
+                                                   want_idx=True)
+            col, jac = _np.color_fused(npm, self_.color_mlp, x, idx, need_jac=jac_on, query_locally=True)
+            outs.append((s, g, std, cnt >= self.nn_k, col, jac))
+        if len(outs) == 1:
+            return [t for t in outs[0] if t is not None] + ([None] if not jac_on else [])
+        cols = list(zip(*outs))
+        return [torch.cat(c) for c in cols[:5]] + [torch.cat(cols[5]) if jac_on else None]
+
+    def photo_residual(self, count):
+        """mean |I_pred - I_src| over the valid points of the last assemble (one host read)."""
+        _lib.note_sync("registration_step_photo")
+        return float(self.photo_part.sum().item()) / count
 
 
 def _check_status(status, warned):
@@ -290,9 +346,26 @@ def _original(name):
 
 
 def _colour_branch(cfg, colors):
-    """The reference's colour-using branches (photometric term, consistency weight): delegated, not native."""
+    """The reference's colour-using branches (photometric term, consistency weight): delegated to the saved originals
+    unless install(..., loop=True, colour=True) put them into the device loop (`_colour_mode`)."""
     colors_on = colors is not None and cfg.color_on
     return colors_on and (cfg.photometric_loss_on or cfg.consist_wieght_on)
+
+
+def _colour_mode(self, cfg, points, colors):
+    """The colour configuration in the device loop (install(..., colour=True)): PINGS_REG_COLOR_* of the reference's
+    branch, or 0 when the call goes to the saved original (option off, or a colour decoder / channel count the
+    kernels do not cover).  Host tensors raise."""
+    if not _COLOUR:
+        return 0
+    if not points.is_cuda or not colors.is_cuda:
+        raise _lib.PingsHipError("tracking with colours runs on the HIP device only (got a CPU tensor); there is no "
+                                 "CPU fallback")
+    if int(cfg.color_channel) not in (1, 3) or colors.shape[1] < int(cfg.color_channel) or \
+            not _np.colour_fused_supported(self.neural_points, getattr(self, "color_mlp", None)):
+        return 0
+    # an `elif` in the reference: the consistency weight is ignored when the photometric term is on
+    return _abi.REG_COLOR_PHOTO if cfg.photometric_loss_on else _abi.REG_COLOR_CONSIST
 
 
 def tracking(self, source_points, init_pose=None, source_colors=None, source_normals=None, source_semantics=None,
@@ -301,9 +374,12 @@ def tracking(self, source_points, init_pose=None, source_colors=None, source_nor
     host read per iteration (`note_sync("tracking_iteration")`); the records of the call are left in `last_trace`."""
     global last_trace
     cfg = self.config
+    colour_mode = 0
     if _colour_branch(cfg, source_colors):
-        return _original("tracking")(self, source_points, init_pose, source_colors, source_normals, source_semantics,
-                                     source_sdf, cur_ts, loop_reg, vis_result)
+        colour_mode = _colour_mode(self, cfg, source_points, source_colors)
+        if not colour_mode:
+            return _original("tracking")(self, source_points, init_pose, source_colors, source_normals,
+                                         source_semantics, source_sdf, cur_ts, loop_reg, vis_result)
     if not source_points.is_cuda:
         raise _lib.PingsHipError("tracking runs on the HIP device only (got a CPU tensor); there is no CPU fallback")
     dev = source_points.device
@@ -323,9 +399,11 @@ def tracking(self, source_points, init_pose=None, source_colors=None, source_nor
     _say(self, f"# Source point for registeration : {source_point_count}")
     if source_sdf is None:
         source_sdf = torch.zeros(source_point_count, device=dev)
-    weighted = cur_GM_dist_m is not None or cur_GM_grad is not None or source_normals is not None
+    # (with a colour term the reference's w is a tensor whatever else is on)
+    weighted = cur_GM_dist_m is not None or cur_GM_grad is not None or source_normals is not None or bool(colour_mode)
     lp = _Loop(self, source_points, source_sdf, source_normals, min_grad_norm, max_grad_norm, cur_GM_dist_m,
-               cur_GM_grad, lm_lambda, weighted, pose, trace_rows=max(int(iter_n), 1))
+               cur_GM_grad, lm_lambda, weighted, pose, trace_rows=max(int(iter_n), 1), colours=source_colors,
+               colour_mode=colour_mode)
     warned = False
     i = -1
     for i in range(iter_n):
@@ -386,7 +464,10 @@ def registration_step(self, points: torch.Tensor, normals: torch.Tensor, sdf_lab
     reference's (T, cov_mat, eigenvalues, weight_point_cloud, valid_points, sdf_residual_cm, photo_residual).  Keeps
     the reference's host reads (compacted valid_points, the residual as a float); `tracking` does not call it."""
     cfg = self.config
-    if vis_weight_pc or _colour_branch(cfg, colors):
+    colour_mode = 0
+    if not vis_weight_pc and _colour_branch(cfg, colors):
+        colour_mode = _colour_mode(self, cfg, points, colors)
+    if vis_weight_pc or (_colour_branch(cfg, colors) and not colour_mode):
         return _original("registration_step")(self, points, normals, sdf_labels, colors, min_grad_norm, max_grad_norm,
                                               GM_dist, GM_grad, lm_lambda, vis_weight_pc)
     if not points.is_cuda:
@@ -394,21 +475,26 @@ def registration_step(self, points: torch.Tensor, normals: torch.Tensor, sdf_lab
                                  "fallback")
     dev = points.device
     pose = torch.eye(4, dtype=torch.float64, device=dev)
-    weighted = GM_dist is not None or GM_grad is not None or normals is not None
+    weighted = GM_dist is not None or GM_grad is not None or normals is not None or bool(colour_mode)
     lp = _Loop(self, points, sdf_labels, normals, min_grad_norm, max_grad_norm, GM_dist, GM_grad, lm_lambda, weighted,
-               pose, valid_out=True)
+               pose, valid_out=True, colours=colors, colour_mode=colour_mode)
     lp.cur.copy_(lp.src)     # the points arrive transformed already
     count, status, res_cm, _, _ = lp.iterate(self, 0, "registration_step")
     valid_points = points[lp.valid]
     if count < 10:
         return lp.delta, None, None, None, valid_points, 0.0, 0.0
     _check_status(status, False)
-    return lp.delta, None, None, None, valid_points, res_cm, None
+    photo = lp.photo_residual(count) if colour_mode == _abi.REG_COLOR_PHOTO else None
+    return lp.delta, None, None, None, valid_points, res_cm, photo
 
 
-def install(tracker_module, loop: bool = False) -> None:
+def install(tracker_module, loop: bool = False, colour: bool = False) -> None:
     """`import utils.tracker as T; install(T)`: Tracker.query_source_points and implicit_reg -> HIP.  With loop=True
-    also Tracker.tracking and Tracker.registration_step (the originals are kept for what the loop delegates)."""
+    also Tracker.tracking and Tracker.registration_step (the originals are kept for what the loop delegates).  With
+    loop=True and colour=True the photometric and colour-consistency configurations run in the device loop too; an
+    install without it turns that off again."""
+    global _COLOUR
+    _COLOUR = bool(loop and colour)
     tracker_module.Tracker.query_source_points = query_source_points
     tracker_module.implicit_reg = implicit_reg
     if loop:
