@@ -1137,4 +1137,41 @@ PINGS_API int pings_eval_pair_reduce(const float* dist_p, int64_t np, const int6
                                      int64_t nr, const int64_t* nr_dev, double threshold, double truncation_com,
                                      const int32_t* status, double* record, void* stream);
 
+/* ------------------------------------------------------------- camera pose on the device
+ * utils/campose_utils.py:28-98 (`update_pose`, `SE3_exp`) and gaussian_splatting/utils/cameras.py:207-219
+ * (`CamImage.set_pose`), each as ONE launch of one 64-lane workgroup with no host wait.  The arithmetic runs in fp64
+ * from the fp32 inputs and every output is rounded to fp32 once.  Matrices are read through element strides
+ * (element [r, c] of X is X[r * X_s0 + c * X_s1]), so the transposed views a `CamImage` holds need no copy.
+ *
+ * Both entries fill one caller-allocated block `out` of 40 fp32 words:
+ *   [0,16)  world_view_transform = T_cw^T (row-major 4x4; R = out[:3,:3]^T and T = out[3,:3] are views of it)
+ *   [16,32) full_proj_transform = world_view_transform(fp32) . projection_matrix
+ *   [32,35) camera_center      35: unused      36: |tau| (fp32)      37: converged (uint32 0 / 1)      38,39: unused
+ *
+ * pings_camera_update_pose: tau = [cam_trans_delta, cam_rot_delta]; T_cw' = SE3_exp(tau) . [R T; 0 1], both
+ *   `angle < 1e-5` series branches of the reference included; camera_center = -R'^T t'; converged = |tau| <
+ *   converged_threshold; the two delta vectors are set to zero.  |tau| == 0 (pose optimisation off: the reference
+ *   returns True and touches nothing): the current world_view_transform, full_proj_transform and camera_center are
+ *   copied into the block bit for bit, converged = 1, the deltas are left alone.  `out` must not overlap an input.
+ * pings_camera_set_pose: T_wc [4,4] (fp64 if is_f64, else fp32) camera -> world; T_cw is its GENERAL inverse
+ *   (cofactors and determinant in fp64, no rigid shortcut); camera_center = T_wc[:3, 3]; words 35..37 are zero.
+ *   A singular T_wc gives non-finite outputs (no status: that would need a host wait). */
+typedef struct pings_camera_pose_args {
+  const float* R;                    /* [3,3] rotation of T_cw */
+  const float* T;                    /* [3] translation of T_cw */
+  const float* projection_matrix;    /* [4,4] */
+  const float* world_view_transform; /* [4,4] current values, read only when |tau| == 0 */
+  const float* full_proj_transform;  /* [4,4] */
+  const float* camera_center;        /* [3] */
+  float* cam_trans_delta;            /* [3] rho, contiguous */
+  float* cam_rot_delta;              /* [3] theta, contiguous */
+  float* out;                        /* [40] */
+  int64_t R_s0, R_s1, T_s, proj_s0, proj_s1, wvt_s0, wvt_s1, fpt_s0, fpt_s1, center_s;
+  double converged_threshold;
+} pings_camera_pose_args;
+PINGS_API int pings_camera_update_pose(const pings_camera_pose_args* args, void* stream);
+PINGS_API int pings_camera_set_pose(const void* T_wc, int is_f64, int64_t s0, int64_t s1,
+                                    const float* projection_matrix, int64_t proj_s0, int64_t proj_s1, float* out,
+                                    void* stream);
+
 #endif /* PINGS_HIP_H_ */

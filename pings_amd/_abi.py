@@ -134,6 +134,13 @@ class AdamwJob(C.Structure):
                                          "bc2_sqrt", "eps")]
 
 
+class CameraPoseArgs(C.Structure):
+    _fields_ = [(n, vp) for n in ("R", "T", "projection_matrix", "world_view_transform", "full_proj_transform",
+                                  "camera_center", "cam_trans_delta", "cam_rot_delta", "out")] + \
+               [(n, C.c_int64) for n in ("R_s0", "R_s1", "T_s", "proj_s0", "proj_s1", "wvt_s0", "wvt_s1", "fpt_s0",
+                                         "fpt_s1", "center_s")] + [("converged_threshold", C.c_double)]
+
+
 # ---------------------------------------------------------------- entry points: {name: (restype, argtypes)}
 SIGNATURES = {
     # general
@@ -310,4 +317,7 @@ SIGNATURES = {
     "pings_eval_nn_build": (i32, [vp, i64, vp, f64, vp, vp, vp]),
     "pings_eval_nn_query": (i32, [vp, i64, vp, vp, i64, f64, f64, vp, vp, vp]),
     "pings_eval_pair_reduce": (i32, [vp, i64, vp, vp, i64, vp, f64, f64, vp, vp, vp]),
+    # camera pose
+    "pings_camera_update_pose": (i32, [C.POINTER(CameraPoseArgs), vp]),
+    "pings_camera_set_pose": (i32, [vp, i32, i64, i64, vp, i64, i64, vp, vp]),
 }
