@@ -35,7 +35,7 @@
 
 /* ABI version of this header (bumped on any signature change).  A binding compares pings_abi_version() of the
  * library it loaded with the PINGS_ABI_VERSION of the header it was written against (pings_amd/_lib.py does). */
-#define PINGS_ABI_VERSION 10
+#define PINGS_ABI_VERSION 11
 PINGS_API int pings_abi_version(void);
 /* Message of the last failing call on this thread ("" if none). Host string. */
 PINGS_API const char* pings_last_error(void);
@@ -726,8 +726,10 @@ PINGS_API size_t pings_map_update_scratch_bytes(int64_t M, int64_t num_points);
  * (temporal_local_map_on False); sample_colors / point_colors nullable together.  update_mask[M] (uint8, nullable)
  * <- 1 where the sample became a new neural point; *num_new (HOST).  Appends rows num_points .. num_points+num_new-1
  * of every map array (identity orientation, ts = cur_ts, certainty 0, free = !is_reliable, valid = 1, colour +
- * colour validity) and refreshes the colour of existing points whose colour was invalid.  Synchronises once. */
-PINGS_API int pings_map_update(const float* sample_points, const float* sample_colors, int64_t M, float resolution,
+ * colour validity) and refreshes the colour of existing points whose colour was invalid.  Synchronises once.
+ * resolution is the caller's double: the grid and the hash use it rounded to fp32, the new-point threshold is
+ * fp32(3 * resolution^2) formed in double, the one rounding of the reference's `d2 > 3 * res ** 2`. */
+PINGS_API int pings_map_update(const float* sample_points, const float* sample_colors, int64_t M, double resolution,
                                int64_t buffer_size, int64_t* table, int64_t num_points, const float* travel_dist,
                                int cur_ts, float diff_travel_dist_local, int is_reliable, float* neural_points,
                                float* point_orientations, int32_t* point_ts_create, int32_t* point_ts_update,
@@ -738,12 +740,13 @@ PINGS_API size_t pings_map_reset_local_scratch_bytes(int64_t num_points);
 /* local_mask / sorrounding_mask [num_points+1] (uint8, last = 1), global2local[num_points+1] (int64: rank for local
  * points, 1 for the others — the reference's full_like(bool,-1) — and -1 for the padding entry),
  * local_idx[num_points+1] (int64: the local rows in order, followed by the padding row num_points),
- * *num_local (HOST).  sensor_position: DEVICE [3].  Synchronises once. */
+ * *num_local (HOST).  sensor_position: DEVICE [3].  Synchronises once.  The radii are the caller's doubles: the
+ * squared distances are compared with fp32(radius^2) formed in double (`d2 < radius ** 2` in the reference). */
 PINGS_API int pings_map_reset_local(int64_t num_points, const float* neural_points, const int32_t* point_ts_create,
                                     const int32_t* point_ts_update, const float* travel_dist, int cur_ts,
                                     int use_mid_ts, int use_travel_dist, float diff_travel_dist_local,
                                     int diff_ts_local, const float* sensor_position, int range_filter_2d,
-                                    float local_radius, float sorrounding_radius, void* scratch, uint8_t* local_mask,
+                                    double local_radius, double sorrounding_radius, void* scratch, uint8_t* local_mask,
                                     uint8_t* sorrounding_mask, int64_t* global2local, int64_t* local_idx,
                                     int64_t* num_local, void* stream);
 /* `NeuralPoints.gather_local_data` (model/neural_gaussians.py:1135-1173) indexes nine per-point tensors with the

@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import ctypes as C
 
-ABI_VERSION = 10                                                  # PINGS_ABI_VERSION
+ABI_VERSION = 11                                                  # PINGS_ABI_VERSION
 
 RASTER_SURFEL, RASTER_3DGS, RASTER_2DGS = 0, 1, 2                 # PINGS_RASTER_*: pings_raster_settings.mode
 HEAD_COLOR, HEAD_SEMANTIC = 0, 1                                  # PINGS_HEAD_*: pings_head_reduce mode
@@ -254,10 +254,10 @@ SIGNATURES = {
     "pings_map_adjust": (i32, [i64, vp, vp, vp, vp, i32, vp, i32, i64, vp, vp]),
     "pings_map_rehash": (i32, [vp, vp, i64, f32, i64, vp, vp, vp]),
     "pings_map_update_scratch_bytes": (sz, [i64, i64]),
-    "pings_map_update": (i32, [vp, vp, i64, f32, i64, vp, i64, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+    "pings_map_update": (i32, [vp, vp, i64, f64, i64, vp, i64, vp, i32, f32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp,
                                vp, vp, C.POINTER(i64), vp]),
     "pings_map_reset_local_scratch_bytes": (sz, [i64]),
-    "pings_map_reset_local": (i32, [i64, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, i32, f32, f32, vp, vp, vp, vp, vp,
+    "pings_map_reset_local": (i32, [i64, vp, vp, vp, vp, i32, i32, i32, f32, i32, vp, i32, f64, f64, vp, vp, vp, vp, vp,
                                     C.POINTER(i64), vp]),
     "pings_mask_rows_scratch_bytes": (sz, [i64]),
     "pings_mask_rows": (i32, [vp, i64, vp, vp, C.POINTER(i64), vp]),

@@ -20,6 +20,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
+#include <cmath>
 
 #include "common.hpp"
 
@@ -29,6 +30,13 @@ using i64 = long long;
 constexpr int kQuant = 1000;  // distance bins of voxel_down_sample_torch (utils/tools.py:937)
 
 __host__ __device__ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
+
+// `x ** 2` of a python float: libm's pow, which differs from x * x in the last bit for about one double in a
+// thousand.  The volatile exponent keeps the compiler from folding the call into a multiplication.
+inline double py_square(double x) {
+  volatile double two = 2.0;
+  return std::pow(x, two);
+}
 
 // ------------------------------------------------------------------ voxel down-sampling
 struct Bounds {
@@ -573,7 +581,7 @@ PINGS_API size_t pings_map_update_scratch_bytes(int64_t M, int64_t num_points) {
   return up256(8 * m) * 2 + up256(4 * m) * 2 + up256(4 * np) + up256(scan) + 256;
 }
 
-PINGS_API int pings_map_update(const float* sample_points, const float* sample_colors, int64_t M, float resolution,
+PINGS_API int pings_map_update(const float* sample_points, const float* sample_colors, int64_t M, double resolution,
                                int64_t buffer_size, int64_t* table, int64_t num_points, const float* travel_dist,
                                int cur_ts, float diff_travel_dist_local, int is_reliable, float* neural_points,
                                float* point_orientations, int32_t* point_ts_create, int32_t* point_ts_update,
@@ -594,8 +602,10 @@ PINGS_API int pings_map_update(const float* sample_points, const float* sample_c
   auto take = [&](size_t bytes) { void* r = p + off; off += up256(bytes); return r; };
   UpdArgs a{};
   a.M = M; a.Np = num_points; a.S = buffer_size;
-  a.res = resolution;
-  a.thr = (float)(3.0 * (double)resolution * (double)resolution);   // 3 * res**2 (python float) cast to fp32
+  a.res = (float)resolution;                                   // points / res and the hash: the fp32 scalar
+  // d2 > 3 * res ** 2: the reference forms the threshold from the python double and torch rounds it to fp32 ONCE
+  // (squaring the fp32-rounded resolution gives another fp32 value for about half of all decimal inputs)
+  a.thr = (float)(3.0 * py_square(resolution));
   a.diff_travel = diff_travel_dist_local;
   a.cur_ts = cur_ts; a.temporal = travel_dist != nullptr; a.is_reliable = is_reliable;
   a.sp = sample_points; a.sc = sample_colors; a.table = reinterpret_cast<i64*>(table); a.travel = travel_dist;
@@ -641,7 +651,7 @@ PINGS_API int pings_map_reset_local(int64_t num_points, const float* neural_poin
                                     const int32_t* point_ts_update, const float* travel_dist, int cur_ts,
                                     int use_mid_ts, int use_travel_dist, float diff_travel_dist_local,
                                     int diff_ts_local, const float* sensor_position, int range_filter_2d,
-                                    float local_radius, float sorrounding_radius, void* scratch, uint8_t* local_mask,
+                                    double local_radius, double sorrounding_radius, void* scratch, uint8_t* local_mask,
                                     uint8_t* sorrounding_mask, int64_t* global2local, int64_t* local_idx,
                                     int64_t* num_local, void* stream) {
   PINGS_ARG_CHECK(num_local != nullptr, "null num_local");
@@ -661,8 +671,8 @@ PINGS_API int pings_map_reset_local(int64_t num_points, const float* neural_poin
   a.temporal = (travel_dist != nullptr) || !use_travel_dist ? 1 : 0;
   a.use_mid_ts = use_mid_ts; a.use_travel = use_travel_dist; a.diff_ts_local = diff_ts_local;
   a.range_2d = range_filter_2d; a.diff_travel = diff_travel_dist_local;
-  a.local_r2 = (float)((double)local_radius * (double)local_radius);
-  a.sur_r2 = (float)((double)sorrounding_radius * (double)sorrounding_radius);
+  a.local_r2 = (float)py_square(local_radius);               // radius ** 2 in double, rounded to fp32 once
+  a.sur_r2 = (float)py_square(sorrounding_radius);
   a.tflag = (uint8_t*)take(n);
   a.lflag = (int32_t*)take(4 * n);
   a.lpos = (int32_t*)take(4 * n);

@@ -119,7 +119,7 @@ def test_header_declares_and_library_exports_the_2dgs_entries():
 
     hdr = abi_header.HEADER.read_text()
     assert re.search(r"#define\s+PINGS_RASTER_2DGS\s+2", hdr)
-    assert abi_header.expected_abi() == 10
+    assert abi_header.expected_abi() == 11
     names = ("pings_raster2d_geom_bytes", "pings_raster2d_binning_bytes", "pings_raster2d_image_bytes",
              "pings_raster2d_preprocess", "pings_raster2d_render", "pings_raster2d_backward_bytes",
              "pings_raster2d_backward", "pings_raster2d_debug_lists", "pings_raster2d_debug_image")

@@ -119,7 +119,7 @@ def test_new_symbols_are_declared_in_the_header_and_mirrored():
     assert "pings_color_decoder" in structs
     assert defines["PINGS_REG_COLOR_PHOTO"] == _abi.REG_COLOR_PHOTO == cref.PHOTO
     assert defines["PINGS_REG_COLOR_CONSIST"] == _abi.REG_COLOR_CONSIST == cref.CONSIST
-    assert defines["PINGS_ABI_VERSION"] == 10
+    assert defines["PINGS_ABI_VERSION"] == 11
     # the layout the existing kernels read is untouched
     assert [n for _, n in structs["pings_reg_loop_args"]] == [f[0] for f in _abi.RegLoopArgs._fields_]
 
