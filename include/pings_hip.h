@@ -1177,4 +1177,64 @@ PINGS_API int pings_camera_set_pose(const void* T_wc, int is_f64, int64_t s0, in
                                     const float* projection_matrix, int64_t proj_s0, int64_t proj_s1, float* out,
                                     void* stream);
 
+/* ------------------------------------------------------------- SDF training-sample pool
+ * The reference's torch code around the mapper's sample pool, on the caller's own tensors (no state is kept here).
+ * Every kernel is bitwise deterministic: no float atomics, no hand-offs between waves.
+ *
+ * pings_pool_sample: `DataSampler.sample` (utils/data_sampler.py:18-264) with the three noise tensors passed in, one
+ *   thread per output row.  row = p * S + s, S = surface_sample_n + free_front_n + free_behind_n + 1; s = 0 is the
+ *   measured point, then the surface samples, the front samples, the behind samples (the reference's ray-wise order).
+ *   Replicate j of a section reads its noise at j * P + p.  fp32 op for op with IEEE division and square root; the
+ *   python-side scalar products (2 * range, 1 + 0.5 * scale, end - 0.2 * end) are formed in double from the fields
+ *   below and rounded to fp32 once.  sdf_label = -displacement; weight < 0 marks free space; out_sem (int32) is the
+ *   label for s <= surface_sample_n and 0 elsewhere, out_color the colour there and -1 elsewhere.  normal / sem /
+ *   color and their outputs are nullable together.  A point at the origin gives the reference's inf / NaN pattern.
+ * pings_pool_draw: the indexing of `Mapper.get_batch` (utils/mapper.py:704-771) and its row gathers in one launch.
+ *   Output row b < bs_history takes i = local_idx ? local_idx[r_hist[b]] : r_hist[b], the others
+ *   i = new_idx[r_new[b - bs_history]]; dst_g[b] = src_g[i] for every job g (rows = bs_history + bs_new in each job;
+ *   any row width).  An r outside its index list or an i outside [0, pool_rows) is never dereferenced: bit 0 of the
+ *   device word `out_of_range` (nullable; the caller zeroes it) is set and the row is zero-filled.
+ * pings_pool_ts_range: min_max[0] = min(ts), min_max[1] = max(ts) (device int64; INT64_MAX / INT64_MIN for N == 0).
+ * pings_pool_transform: `Mapper.transform_data_pool` (utils/mapper.py:774-778, utils/tools.py:903-921) in place:
+ *   p <- R[ts] p + t[ts] on points[N,3] fp32, pose_diff [num_poses,4,4] row-major (fp64 when pose_is_f64, rounded to
+ *   fp32 first as `transformation.to(points)` does), ts int32 or int64 with python index semantics; a ts outside
+ *   [-T, T) sets bit 0 of `out_of_range` (nullable) and leaves the row alone.
+ * pings_pool_window_count / pings_pool_window: the sample window of `process_frame` (utils/mapper.py:429-438):
+ *   rows (int64, ascending) with sqrt(dx^2 + dy^2 [+ dz^2]) < radius in fp32, d = p - origin (origin: DEVICE [3]).
+ *   _count fills `scratch` (pings_pool_window_scratch_bytes(n)) and returns the number of rows in *count (HOST; one
+ *   polled read-back); pings_pool_window then writes them, never past `capacity`.  No per-row temporary. */
+typedef struct pings_pool_sample_args {
+  int64_t P;
+  int32_t surface_sample_n, free_front_n, free_behind_n, color_channels;
+  int32_t dist_weight_on, behind_dropoff_on, sem_is_i64, reserved;
+  double surface_sample_range, free_sample_begin_ratio, free_sample_end_dist, dist_weight_scale, max_range;
+  const float* points;        /* [P,3] */
+  const float* normal;        /* [P,3] or NULL */
+  const void* sem;            /* [P] int32 / int64 or NULL */
+  const float* color;         /* [P,color_channels] or NULL */
+  const float* noise_surface; /* [surface_sample_n * P] standard normal */
+  const float* noise_front;   /* [free_front_n * P] uniform [0,1) */
+  const float* noise_behind;  /* [free_behind_n * P] uniform [0,1) */
+  float* coord;               /* [P*S,3] */
+  float* sdf_label;           /* [P*S] */
+  float* weight;              /* [P*S] */
+  float* out_normal;          /* [P*S,3] or NULL */
+  int32_t* out_sem;           /* [P*S] or NULL */
+  float* out_color;           /* [P*S,color_channels] or NULL */
+} pings_pool_sample_args;
+PINGS_API int pings_pool_sample(const pings_pool_sample_args* args, void* stream);
+PINGS_API int pings_pool_draw(const pings_gather_job* jobs, int njobs, const int64_t* r_hist, int64_t bs_history,
+                              const int64_t* r_new, int64_t bs_new, const int64_t* local_idx, int64_t n_local,
+                              const int64_t* new_idx, int64_t n_new, int64_t pool_rows, int32_t* out_of_range,
+                              void* stream);
+PINGS_API int pings_pool_ts_range(const void* ts, int32_t ts_is_i64, int64_t N, int64_t* min_max, void* stream);
+PINGS_API int pings_pool_transform(int64_t N, float* points, const void* ts, int32_t ts_is_i64, const void* pose_diff,
+                                   int32_t pose_is_f64, int64_t num_poses, int32_t* out_of_range, void* stream);
+PINGS_API size_t pings_pool_window_scratch_bytes(int64_t n);
+PINGS_API int pings_pool_window_count(const float* points, int64_t n, const float* origin, float radius,
+                                      int32_t range_filter_2d, void* scratch, int64_t* count, void* stream);
+PINGS_API int pings_pool_window(const float* points, int64_t n, const float* origin, float radius,
+                                int32_t range_filter_2d, const void* scratch, int64_t* rows, int64_t capacity,
+                                void* stream);
+
 #endif /* PINGS_HIP_H_ */

@@ -141,6 +141,16 @@ class CameraPoseArgs(C.Structure):
                                          "fpt_s1", "center_s")] + [("converged_threshold", C.c_double)]
 
 
+class PoolSampleArgs(C.Structure):
+    _fields_ = [("P", C.c_int64)] + \
+               [(n, C.c_int32) for n in ("surface_sample_n", "free_front_n", "free_behind_n", "color_channels",
+                                         "dist_weight_on", "behind_dropoff_on", "sem_is_i64", "reserved")] + \
+               [(n, C.c_double) for n in ("surface_sample_range", "free_sample_begin_ratio", "free_sample_end_dist",
+                                          "dist_weight_scale", "max_range")] + \
+               [(n, vp) for n in ("points", "normal", "sem", "color", "noise_surface", "noise_front", "noise_behind",
+                                  "coord", "sdf_label", "weight", "out_normal", "out_sem", "out_color")]
+
+
 # ---------------------------------------------------------------- entry points: {name: (restype, argtypes)}
 SIGNATURES = {
     # general
@@ -320,4 +330,12 @@ SIGNATURES = {
     # camera pose
     "pings_camera_update_pose": (i32, [C.POINTER(CameraPoseArgs), vp]),
     "pings_camera_set_pose": (i32, [vp, i32, i64, i64, vp, i64, i64, vp, vp]),
+    # SDF training-sample pool
+    "pings_pool_sample": (i32, [C.POINTER(PoolSampleArgs), vp]),
+    "pings_pool_draw": (i32, [C.POINTER(GatherJob), i32, vp, i64, vp, i64, vp, i64, vp, i64, i64, vp, vp]),
+    "pings_pool_ts_range": (i32, [vp, i32, i64, vp, vp]),
+    "pings_pool_transform": (i32, [i64, vp, vp, i32, vp, i32, i64, vp, vp]),
+    "pings_pool_window_scratch_bytes": (sz, [i64]),
+    "pings_pool_window_count": (i32, [vp, i64, vp, f32, i32, vp, C.POINTER(i64), vp]),
+    "pings_pool_window": (i32, [vp, i64, vp, f32, i32, vp, vp, i64, vp]),
 }
