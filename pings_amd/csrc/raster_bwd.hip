@@ -8,7 +8,8 @@
 //                         transmittance and forms the 16 per-(pixel, Gaussian) gradient terms of the
 //                         blend record; the wave reduces them with a transposed DPP reduce-scatter
 //                         (16 values x 64 lanes -> one 64-B row in 16 lanes, ~55 VALU ops instead of
-//                         96 for 16 separate wave sums).  The four waves' rows are summed in LDS in
+//                         96 for 16 separate wave sums; footprint class 2 starts it with the lane swaps,
+//                         raster_common.hpp: wave_reduce16_swap).  The four waves' rows are summed in LDS in
 //                         fixed order and stored ONCE per live instance as a 64-B row; the rows of
 //                         one Gaussian are contiguous (slot order = depth rank order).
 //   row_chunk_sum_kernel  balanced first level of the per-Gaussian sum: one 16-lane group per
@@ -438,8 +439,10 @@ __device__ __forceinline__ void blend_bwd_tile(PINGS_BLEND_BWD_PARAMS) {
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) lmax = max(lmax, (uint32_t)__shfl_xor((int)lmax, off, 64));
   const int max_last = __builtin_amdgcn_readfirstlane((int)lmax);
-  // the 0.5 of the cov2D xx / yy gradient terms, applied to the reduced sums (lane < 16 holds slot red_slot)
-  const int red_slot = ((lane & 1) << 3) | ((lane & 2) << 1) | (lane >> 2);
+  // the 0.5 of the cov2D xx / yy gradient terms, applied to the reduced sums (wave_reduce16_swap: the first four lanes
+  // of each 16-lane row hold the record's row, lane l slot red_slot)
+  const int red_slot = red16_lane_slot(lane);
+  const bool red_store = (lane & 12) == 0;
   const float red_scale = (red_slot == G_CONX || red_slot == G_CONZ) ? 0.5f : 1.0f;
 
   const int nbatch = ceil_div(max_last, BATCH);
@@ -473,21 +476,15 @@ __device__ __forceinline__ void blend_bwd_tile(PINGS_BLEND_BWD_PARAMS) {
 
     // Two-deep software pipeline over the list: the INDEX of record jj-2 and the RECORD jj-1 are fetched from LDS
     // while record jj is processed, so neither LDS latency sits in an iteration's dependency chain.
-    int jcur = cnt > 0 ? (int)sList[cnt - 1] : 0;
-    int jnext = cnt > 1 ? (int)sList[cnt - 2] : 0;
-    float4 a = sA[jcur], bq = sB[jcur], c = sC[jcur], nn = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (MODE == MODE_SURFEL) nn = sD[jcur];
-    for (int jj = cnt - 1; jj >= 0; --jj) {
-      const int j = jcur;
-      const int jn = jnext;
-      const int jn2 = (int)sList[jj > 1 ? jj - 2 : 0];
-      const float4 a_n = sA[jn], b_n = sB[jn], c_n = sC[jn];
-      float4 n_n = nn;
-      if (MODE == MODE_SURFEL) n_n = sD[jn];
-      const float4 ca = a, cb = bq, cc = c, cn = nn;
-      a = a_n; bq = b_n; c = c_n; nn = n_n;
-      jcur = jn;
-      jnext = jn2;
+    // The loop is unrolled by two over two register sets: a trip reads its record from one set while the next record
+    // goes straight into the other, so nothing is copied from "next" to "current" (8 v_mov_b64 + 9 v_mov_b32 a trip).
+    int i0 = cnt > 0 ? (int)sList[cnt - 1] : 0;
+    int i1 = cnt > 1 ? (int)sList[cnt - 2] : 0;
+    float4 a0 = sA[i0], b0 = sB[i0], c0 = sC[i0], n0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    float4 a1, b1, c1, n1 = n0;
+    if (MODE == MODE_SURFEL) n0 = sD[i0];
+    auto trip = [&](const float4& ca, const float4& cb, const float4& cc, const float4& cn, const int j)
+                    __attribute__((always_inline)) {
       const uint32_t idx = (uint32_t)(start + j);
       // the forward pass's alpha and validity, operation for operation (blend_fwd_tile_kernel)
       const f2 dx = f2s(ca.x) - pixf_x;
@@ -509,7 +506,7 @@ __device__ __forceinline__ void blend_bwd_tile(PINGS_BLEND_BWD_PARAMS) {
         valid[r][1] = idx < last[r][1] && (power.y <= 0.0f) && (alpha[r].y >= ALPHA_MIN);
         any_v = any_v || valid[r][0] || valid[r][1];
       }
-      if (!__any(any_v)) continue;
+      if (!__any(any_v)) return;
 
       // gradient accumulation only: multiply-adds may fuse here (fewer instructions, one rounding less per term).
       // The first row assigns the 16 packed accumulators, the second adds to them; they are folded once per record.
@@ -581,11 +578,25 @@ __device__ __forceinline__ void blend_bwd_tile(PINGS_BLEND_BWD_PARAMS) {
         acc(G_CONZ, uy * qy);
         T[r] = Tn;
       }
-      float v[16];
-#pragma unroll
-      for (int q = 0; q < 16; ++q) v[q] = v2[q].x + v2[q].y;
-      const float tot = wave_reduce16(v, lane) * red_scale;
-      if (lane < 16) reinterpret_cast<float*>(&sG[j][0])[red_slot] = tot;
+      const float tot = wave_reduce16_swap<MODE != MODE_SURFEL>(v2, lane) * red_scale;
+      if (red_store) reinterpret_cast<float*>(&sG[j][0])[red_slot] = tot;
+      }
+    };
+    for (int jj = cnt - 1; jj >= 0; jj -= 2) {
+      {  // record i0 from set 0; set 1 takes record i1, i0 the index two trips ahead
+        const int j = i0;
+        a1 = sA[i1]; b1 = sB[i1]; c1 = sC[i1];
+        if (MODE == MODE_SURFEL) n1 = sD[i1];
+        i0 = (int)sList[jj > 1 ? jj - 2 : 0];
+        trip(a0, b0, c0, n0, j);
+      }
+      if (jj == 0) break;
+      {  // record i1 from set 1; set 0 takes record i0
+        const int j = i1;
+        a0 = sA[i0]; b0 = sB[i0]; c0 = sC[i0];
+        if (MODE == MODE_SURFEL) n0 = sD[i0];
+        i1 = (int)sList[jj > 2 ? jj - 3 : 0];
+        trip(a1, b1, c1, n1, j);
       }
     }
     __syncthreads();

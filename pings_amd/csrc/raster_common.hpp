@@ -308,6 +308,9 @@ __device__ inline float sel4(const float (&t)[4], bool m0, bool m1) {
 // steps (16 -> 8 -> 4 values per lane), one rotate step inside each 16-lane row (4 -> 1) and
 // two cross-row adds.  Afterwards lane l of EVERY row holds the wave total of slot
 //   8*(l&1) + 4*((l>>1)&1) + ((l>>2)&3).
+// Used by the forward kernels (the per-Gaussian weight and contribution sums) and by blend_bwd_pixels, the PPL 1 / 2
+// A/B variants of the backward.  The class-2 backward uses wave_reduce16_swap below; the forward keeps this one because
+// another order of the adds would change the bits of `contributions` and of the weight sums.
 __device__ inline float wave_reduce16(const float (&v)[16], int lane) {
   const bool b0 = lane & 1, b1 = lane & 2;
   float u[8];
@@ -343,6 +346,105 @@ __device__ inline float wave_reduce16(const float (&v)[16], int lane) {
     asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
     r = a + b;
   }
+  return r;
+}
+
+// The same 16 sums for the class-2 blend backward (blend_bwd_tile, raster_bwd.hip), which has the 16 terms as packed
+// pairs and is bound by vector issue: the WIDE stages go through the swaps, the narrow ones through DPP.
+//   fold           16 adds                       x + y of each pair
+//   16 -> 8        8 x (v_permlane32_swap, add)  swap(a, b) leaves a = {a.lo, b.lo}, b = {a.hi, b.hi}: a + b is a's sum
+//                                                over the halves in lanes 0-31 and b's in lanes 32-63
+//   8 -> 4         4 x (v_permlane16_swap, add)  the same between rows 0|1 and 2|3
+//   4 -> 2 -> 1    quad_perm exchanges as in wave_reduce16 (two v_cndmask and one DPP add per output)
+//   row_ror:4, :8  sum over the row's four quads
+// One output register costs two instructions on a swap stage and three on an exchange stage, and a swap's operands need
+// no copies (wave_reduce16 swaps a value with itself).  55 vector instructions against 72 for fold + wave_reduce16; the
+// forward kernels keep wave_reduce16, so every forward output keeps its bits.
+// Values travel by POSITION p: positions p and p + 8 meet in the first stage, p and p + 4 in the second, and lane l
+// ends with position 4*(l >> 4) + 2*(l & 1) + ((l >> 1) & 1); the 16 lanes with (l & 12) == 0 hold the row.  Slot
+// red16_slot(p) travels at position p.  The map puts the six slots that are zero in 3DGS mode at positions 3, 7, 11, 15
+// (zero meets zero in both stages) and 6, 14 (in the first): ZERO6 leaves out their folds, four swaps and four adds.
+// Inline asm: this hipcc maps both results of __builtin_amdgcn_permlane32_swap to one register (v_add_f32 v1, v1, v1).
+// The swaps of a stage stand behind ONE s_nop 1 (two wait states between a VALU write and a swap's read).
+__host__ __device__ constexpr int red16_slot(int pos) {
+  constexpr int m[16] = {G_MX, G_MY, G_CONX, G_NX, G_CONY, G_CONZ, G_ZLO, G_NY, G_OPAC, G_R, G_G, G_NZ, G_B, G_PZ, G_ZHI, G_Q};
+  return m[pos];
+}
+__device__ inline int red16_lane_slot(int lane) {
+  const int pos = 4 * (lane >> 4) + 2 * (lane & 1) + ((lane >> 1) & 1);
+  // slot of position p in nibble p (a table indexed by a lane value would live in memory)
+  constexpr unsigned long long packed = [] {
+    unsigned long long w = 0;
+    for (int q = 0; q < 16; ++q) w |= (unsigned long long)red16_slot(q) << (4 * q);
+    return w;
+  }();
+  return (int)((packed >> (4 * pos)) & 15ull);
+}
+
+#define PINGS_SWAP3(op, a0, b0, a1, b1, a2, b2)                                     \
+  asm volatile("s_nop 1\n\t" op " %0, %3\n\t" op " %1, %4\n\t" op " %2, %5"         \
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(b0), "+v"(b1), "+v"(b2))
+#define PINGS_SWAP4(op, a0, b0, a1, b1, a2, b2, a3, b3)                             \
+  asm volatile("s_nop 1\n\t" op " %0, %4\n\t" op " %1, %5\n\t" op " %2, %6\n\t" op " %3, %7" \
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3))
+#define PINGS_SWAP5(op, a0, b0, a1, b1, a2, b2, a3, b3, a4, b4)                     \
+  asm volatile("s_nop 1\n\t" op " %0, %5\n\t" op " %1, %6\n\t" op " %2, %7\n\t" op " %3, %8\n\t" op " %4, %9" \
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4))
+#define PINGS_SWAP8(op, a0, b0, a1, b1, a2, b2, a3, b3, a4, b4, a5, b5, a6, b6, a7, b7)                        \
+  asm volatile("s_nop 1\n\t" op " %0, %8\n\t" op " %1, %9\n\t" op " %2, %10\n\t" op " %3, %11\n\t"             \
+               op " %4, %12\n\t" op " %5, %13\n\t" op " %6, %14\n\t" op " %7, %15"                             \
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6), "+v"(a7),               \
+                 "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4), "+v"(b5), "+v"(b6), "+v"(b7))
+
+// (r0, r1) = (a0 + b0, a1 + b1) as one packed add
+__device__ inline void pair_add(float& r0, float& r1, float a0, float a1, float b0, float b1) {
+  const f2 r = f2{a0, a1} + f2{b0, b1};
+  r0 = r.x;
+  r1 = r.y;
+}
+
+template <bool ZERO6>
+__device__ inline float wave_reduce16_swap(const f2 (&v2)[16], int lane) {
+  float s[16];
+#pragma unroll
+  for (int q = 0; q < 16; ++q) {
+    const bool zero = ZERO6 && ((q & 3) == 3 || (q & 7) == 6);
+    s[q] = zero ? 0.f : v2[red16_slot(q)].x + v2[red16_slot(q)].y;
+  }
+  float u[8], t[4];
+  if (ZERO6) {
+    PINGS_SWAP5("v_permlane32_swap_b32", s[0], s[8], s[1], s[9], s[2], s[10], s[4], s[12], s[5], s[13]);
+    // neighbouring positions are added as packed pairs (v_pk_add_f32)
+    pair_add(u[0], u[1], s[0], s[1], s[8], s[9]);
+    pair_add(u[4], u[5], s[4], s[5], s[12], s[13]);
+    u[2] = s[2] + s[10];
+    float z = 0.f;                                        // position 6 is zero: position 2 swaps with a zero register
+    PINGS_SWAP3("v_permlane16_swap_b32", u[0], u[4], u[1], u[5], u[2], z);
+    pair_add(t[0], t[1], u[0], u[1], u[4], u[5]);
+    t[2] = u[2] + z;
+    t[3] = 0.f;
+  } else {
+    PINGS_SWAP8("v_permlane32_swap_b32", s[0], s[8], s[1], s[9], s[2], s[10], s[3], s[11], s[4], s[12], s[5], s[13],
+                s[6], s[14], s[7], s[15]);
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) pair_add(u[k], u[k + 1], s[k], s[k + 1], s[k + 8], s[k + 9]);
+    PINGS_SWAP4("v_permlane16_swap_b32", u[0], u[4], u[1], u[5], u[2], u[6], u[3], u[7]);
+#pragma unroll
+    for (int k = 0; k < 4; k += 2) pair_add(t[k], t[k + 1], u[k], u[k + 1], u[k + 4], u[k + 5]);
+  }
+  const bool b0 = lane & 1, b1 = lane & 2;
+  float x[2];
+#pragma unroll
+  for (int k = 0; k < 2; ++k) {
+    const float send = b0 ? t[k] : t[k + 2];
+    const float keep = b0 ? t[k + 2] : t[k];
+    x[k] = keep + dpp_mov<0xb1>(send);  // quad_perm [1,0,3,2]
+  }
+  float r = (b1 ? x[1] : x[0]) + dpp_mov<0x4e>(b1 ? x[0] : x[1]);  // quad_perm [2,3,0,1]
+  r += dpp_mov<0x124>(r);  // row_ror:4
+  r += dpp_mov<0x128>(r);  // row_ror:8
+  // keeps the last add a DPP add: behind the caller's store predicate it would become a move, a DPP move and an add
+  asm volatile("" : "+v"(r));
   return r;
 }
 
