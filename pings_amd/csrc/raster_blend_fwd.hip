@@ -844,7 +844,6 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
   constexpr int PPL = 4;
   __shared__ float4 sA[64], sB[64], sC[64], sD[64];
   __shared__ uint32_t sSlot[64];
-  __shared__ int sE[64];
   __shared__ float sW[64];
   __shared__ uint32_t sCnt[64];
 
@@ -887,6 +886,7 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
   // is exactly `!done && alpha >= ALPHA_MIN`.  The wave's count of pixels not yet done is kept in a scalar register
   // (a pixel stops at most once), which replaces the per-record all-done vote.
   constexpr float DONE_AMIN = 2.0f;
+  const float done_amin = DONE_AMIN;
   float amin[PPL];
   int live_px = 0;   // wave-uniform
 #pragma unroll
@@ -949,10 +949,12 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
       const int at = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u));
       sA[at] = ra;
       sB[at] = rb;
-      sC[at] = rc;
-      if (MODE == MODE_SURFEL) sD[at] = rd;
+      // the record's list position + 1 (what n_contrib takes) travels in the record's unused fourth word: the normal's
+      // (surfels) or the colour's (3DGS, which has no q), so the blend reads it with the record, not from an array of its own
+      const float e1f = __uint_as_float((uint32_t)(base + lane + 1));
+      sC[at] = MODE == MODE_SURFEL ? rc : make_float4(rc.x, rc.y, rc.z, e1f);
+      if (MODE == MODE_SURFEL) sD[at] = make_float4(rd.x, rd.y, rd.z, e1f);
       sSlot[at] = slot;
-      sE[at] = base + lane;
     }
     sW[lane] = 0.f;
     if (MODE == MODE_3DGS) sCnt[lane] = 0u;
@@ -966,21 +968,30 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
     // the whole zero-initialised array through every record's control flow (~12 v_mov per record).
     for (int j0 = 0; j0 < n && live_px > 0; j0 += 16) {
       float ws[16], wc[16];
+      // the group's first record index in a VECTOR register: a record's LDS reads are then this one base plus the record's
+      // position in the instruction's immediate offset, instead of a scalar address moved to a VGPR for every record
+      int jv = j0;
+      asm("" : "+v"(jv));
 #pragma unroll
       for (int jj = 0; jj < 16; ++jj) {
         const int j = j0 + jj;
         float wsum = 0.f;
         uint32_t touched = 0;
         if (j < n && live_px > 0) {   // wave-uniform
-          const float4 a = sA[j], b = sB[j], c = sC[j];
+          float4 a = sA[jv + jj], b = sB[jv + jj];
+          const float4 c = sC[jv + jj];
           float4 nn = make_float4(0.f, 0.f, 0.f, 0.f);
-          if (MODE == MODE_SURFEL) nn = sD[j];
+          if (MODE == MODE_SURFEL) nn = sD[jv + jj];
+          // whole 16-byte reads of a and b: pz and rz come with the words the alpha test needs instead of by reads of
+          // their own in the branch, and opacity sits in an aligned register pair (no move to build the packed operand)
+          asm("" : "+v"(a.w), "+v"(b.w));
           const f2 dx = f2s(a.x) - pixf_x2;
           const f2 p0 = f2s(-0.5f) * ((f2s(b.x) * dx) * dx);
           const f2 pxy = f2s(b.y) * dx;
           f2 alpha[2], test_T[2];
-          bool contrib[PPL];
-          bool any_c = false;
+          // the per-pixel decisions as lane masks (raster_common.hpp): each compare is issued once and lands in an
+          // SGPR pair, stop / contrib are scalar logic on them, and every select below reads its mask directly
+          lmask contrib[PPL];
           int n_stop = 0;
 #pragma unroll
           for (int r = 0; r < 2; ++r) {
@@ -992,31 +1003,31 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
 #pragma unroll
             for (int h = 0; h < 2; ++h) {
               const int k = 2 * r + h;
-              const bool valid = (power[h] <= 0.0f) && (alpha[r][h] >= amin[k]);   // amin folds in !done
-              const bool lt = test_T[r][h] < T_EPS;
-              const bool stop = valid && lt;
-              contrib[k] = valid && !lt;
-              amin[k] = stop ? DONE_AMIN : amin[k];
-              n_stop += __popcll(__ballot(stop));
-              any_c = any_c || contrib[k];
+              const lmask valid = mask_le(power[h], 0.0f) & mask_ge(alpha[r][h], amin[k]);   // amin folds in !done
+              const cmask lt = mask_lt(test_T[r][h], T_EPS);
+              const lmask stop = valid & lt;
+              contrib[k] = valid & ~lt;
+              amin[k] = mask_sel(stop, done_amin, amin[k]);
+              n_stop += mask_count(stop);
             }
           }
           live_px -= n_stop;
-          if (__any(any_c)) {
-            const uint32_t e1 = (uint32_t)(sE[j] + 1);
+          if ((contrib[0] | contrib[1] | contrib[2] | contrib[3]) != 0ull) {
+            const uint32_t e1 = __float_as_uint(MODE == MODE_SURFEL ? nn.w : c.w);
             // depth clamp as one v_med3: fminf(fmaxf(d, lo), hi) == med3(d, min(lo, hi), hi) for every non-NaN d
             // (lo > hi clamps to hi either way), and d is never NaN here
             const float zhi = a.w + b.w, zlo = fminf(a.w - b.w, zhi);
 #pragma unroll
             for (int r = 0; r < 2; ++r) {
-              const bool c0 = contrib[2 * r], c1 = contrib[2 * r + 1];
-              const f2 w = sel2(c0, c1, alpha[r] * T[r], f2{0.f, 0.f});
+              const lmask c0 = contrib[2 * r], c1 = contrib[2 * r + 1];
+              const f2 w = mask_sel2_0(c0, c1, alpha[r] * T[r]);
               C0[r] = fma2(f2s(c.x), w, C0[r]);
               C1[r] = fma2(f2s(c.y), w, C1[r]);
               C2[r] = fma2(f2s(c.z), w, C2[r]);
               if (MODE == MODE_SURFEL) {
                 const f2 den = (f2s(nn.x) * rx2 + f2s(nn.y * ry[r])) + f2s(nn.z);
                 const f2 dq = f2s(c.w) * f2{__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
+                // compared and selected on directly: the compiler's select, which it keeps two wait states behind the compare
                 const f2 d0 = sel2(den.x < -DEN_EPS, den.y < -DEN_EPS, dq, f2s(a.w));
                 const f2 d = {__builtin_amdgcn_fmed3f(d0.x, zlo, zhi), __builtin_amdgcn_fmed3f(d0.y, zlo, zhi)};
                 N0[r] = fma2(f2s(nn.x), w, N0[r]);
@@ -1025,12 +1036,12 @@ __global__ __launch_bounds__(64) void blend_fwd_tile_kernel(
                 D[r] = fma2(d, w, D[r]);
               } else {
                 D[r] = fma2(f2s(a.w), w, D[r]);
-                touched += (c0 && test_T[r].x > 0.5f) ? 1u : 0u;
-                touched += (c1 && test_T[r].y > 0.5f) ? 1u : 0u;
+                touched += mask_one(c0 & mask_gt(test_T[r].x, 0.5f));
+                touched += mask_one(c1 & mask_gt(test_T[r].y, 0.5f));
               }
-              T[r] = sel2(c0, c1, test_T[r], T[r]);
-              last[2 * r] = c0 ? e1 : last[2 * r];
-              last[2 * r + 1] = c1 ? e1 : last[2 * r + 1];
+              T[r] = mask_sel2(c0, c1, test_T[r], T[r]);
+              last[2 * r] = mask_sel(c0, e1, last[2 * r]);
+              last[2 * r + 1] = mask_sel(c1, e1, last[2 * r + 1]);
               wsum = r == 0 ? w.x + w.y : (wsum + w.x) + w.y;   // pixel order k = 0..3, as the scalar sum
             }
           }

@@ -289,6 +289,62 @@ __device__ inline f2 f2s(float x) { return f2{x, x}; }
 __device__ inline f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ inline f2 sel2(bool c0, bool c1, f2 a, f2 b) { return f2{c0 ? a.x : b.x, c1 ? a.y : b.y}; }
 
+// ---------------------------------------------------------------- lane masks of the class-2 blend kernels
+// A per-lane decision of a wave-per-tile kernel is kept as a 64-bit scalar (one bit per lane, an SGPR pair), never as a
+// `bool`: hipcc carries a bool that lives across a wave-uniform branch as a 0/1 VGPR and turns it back into a mask with
+// a second compare, and it compares again for the negation of a condition.  The compare helpers deliver the mask
+// straight from a VOP3 v_cmp (llvm.amdgcn.fcmp: the ballot of the compare over the active lanes; ordered
+// predicates, so a NaN operand gives 0 exactly as the C++ operators do).  The select helpers issue one
+// v_cndmask_b32_e64 reading the mask; they are inline asm only because C++ has no select that takes a lane mask.
+// HAZARD (gfx940 and later, gfx950 included): a VALU instruction that writes an SGPR pair must be followed by two wait
+// states before a VALU instruction reads that pair, a select mask included.  hipcc pads its own v_cmp -> v_cndmask
+// pairs with `s_nop 1` on this target; it does not look into an asm string.  The types keep the pair apart instead of a
+// pad: a compare returns a `cmask`, which no select helper accepts; and / and-not / or / complement of cmasks (and of
+// lmasks) are scalar-ALU instructions and return an `lmask`, the only thing a select helper takes, and a scalar-ALU
+// result read by a vector instruction needs no wait state.  A condition that is compared and selected on directly, with
+// no scalar logic in between, uses the compiler's own select (`sel2`, `?:`), which hipcc pads or fills.  The operands
+// of the selects are never the direct result of a transcendental (exp, rcp) either.  The asm is not volatile: the
+// compiler may schedule, merge or drop a select like any pure operation.  Callers run with every lane active.
+typedef unsigned long long lmask;   // a mask written by the scalar ALU
+struct cmask {                      // a mask written by a vector compare: combine it before any select reads it
+  unsigned long long bits;
+};
+enum { LM_OGT = 2, LM_OGE = 3, LM_OLT = 4, LM_OLE = 5 };   // llvm::CmpInst predicate codes
+__device__ inline cmask mask_lt(float a, float b) { return cmask{__builtin_amdgcn_fcmpf(a, b, LM_OLT)}; }
+__device__ inline cmask mask_le(float a, float b) { return cmask{__builtin_amdgcn_fcmpf(a, b, LM_OLE)}; }
+__device__ inline cmask mask_gt(float a, float b) { return cmask{__builtin_amdgcn_fcmpf(a, b, LM_OGT)}; }
+__device__ inline cmask mask_ge(float a, float b) { return cmask{__builtin_amdgcn_fcmpf(a, b, LM_OGE)}; }
+__device__ inline lmask operator&(cmask a, cmask b) { return a.bits & b.bits; }
+__device__ inline lmask operator&(lmask a, cmask b) { return a & b.bits; }
+__device__ inline lmask operator&(cmask a, lmask b) { return a.bits & b; }
+__device__ inline lmask operator|(cmask a, cmask b) { return a.bits | b.bits; }
+__device__ inline lmask operator~(cmask a) { return ~a.bits; }
+__device__ inline int mask_count(lmask m) { return __builtin_popcountll(m); }
+// m ? a : b per lane
+__device__ inline float mask_sel(lmask m, float a, float b) {
+  float r;
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
+  return r;
+}
+__device__ inline uint32_t mask_sel(lmask m, uint32_t a, uint32_t b) {
+  uint32_t r;
+  asm("v_cndmask_b32_e64 %0, %1, %2, %3" : "=v"(r) : "v"(b), "v"(a), "s"(m));
+  return r;
+}
+// m ? a : 0 and m ? 1 : 0 (the zero and the one are inline constants of the instruction)
+__device__ inline float mask_sel0(lmask m, float a) {
+  float r;
+  asm("v_cndmask_b32_e64 %0, 0, %1, %2" : "=v"(r) : "v"(a), "s"(m));
+  return r;
+}
+__device__ inline uint32_t mask_one(lmask m) {
+  uint32_t r;
+  asm("v_cndmask_b32_e64 %0, 0, 1, %1" : "=v"(r) : "s"(m));
+  return r;
+}
+__device__ inline f2 mask_sel2(lmask m0, lmask m1, f2 a, f2 b) { return f2{mask_sel(m0, a.x, b.x), mask_sel(m1, a.y, b.y)}; }
+__device__ inline f2 mask_sel2_0(lmask m0, lmask m1, f2 a) { return f2{mask_sel0(m0, a.x), mask_sel0(m1, a.y)}; }
+
 // wave64 sum through DPP; the total ends up in lane 63.
 template <int CTRL>
 __device__ inline float dpp_mov(float v) {
