@@ -1237,4 +1237,42 @@ PINGS_API int pings_pool_window(const float* points, int64_t n, const float* ori
                                 int32_t range_filter_2d, const void* scratch, int64_t* rows, int64_t capacity,
                                 void* stream);
 
+/* ------------------------------------------------------------- frame-time point tests
+ * Three per-frame query steps of the reference's `Mapper`, on the caller's own tensors (no state is kept here).  Every
+ * threshold is the double the reference forms between python scalars; it is rounded to fp32 once, as torch does with a
+ * python scalar against an fp32 tensor.  Bitwise deterministic: no LDS, no float atomics, no hand-offs between waves.
+ *
+ * pings_frame_new_count / pings_frame_new_rows: the new-sample test of `process_frame` (utils/mapper.py:447-513).  Row r
+ *   of coord[n,3] / sdf_label[n] looks up its OWN cell in the map's table (`m`: table or compact, buffer_size,
+ *   neural_points, resolution; no neighbourhood, no time window: `query_certainty`, model/neural_gaussians.py:1117-1133,
+ *   under `set_search_neighborhood(1, 0.0)`), drops the point when its squared distance is above `max_valid_dist2` (the
+ *   one-cell 3 * ((1 + 1) * resolution)^2, an argument: the map is not touched) and takes
+ *   certainty = point_certainties[idx], 0 without a point.  The row is kept iff certainty < new_certainty_thre and
+ *   |sdf_label| < label_thre (= 3 * surface_sample_range_m).  _count fills `scratch`
+ *   (pings_frame_new_scratch_bytes(n): a bit per row and 12 B per 512 rows) and returns the number of kept rows in
+ *   *count (HOST; one polled read-back); _rows then writes r + pool_offset for the kept rows in ascending order (int64),
+ *   never past `capacity`.  A table entry >= num_points is treated as an empty cell.
+ * pings_frame_static_mask: `Mapper.dynamic_filter` / `dynamic_filter_neural_points` (utils/mapper.py:554-564) from the
+ *   fused query's outputs: mask[i] = certainty[i] < certainty_thre || sdf[i] < sdf_thre, and with grad[n,3] != NULL
+ *   also && (sqrt(gx^2 + gy^2 + gz^2) > min_grad_norm || certainty[i] < certainty_thre).  *dynamic_count (DEVICE int64;
+ *   cleared by the call) receives the number of zeros, one integer atomic per wave.
+ * pings_frame_valid_scatter: `Mapper.check_invalid_neural_points` (utils/mapper.py:1647-1655) for the stable rows
+ *   rows[n] (distinct local rows) with their sdf[n] and nn_count[n]: v = |sdf[i]| < sdf_thre && nn_count[i] >= min_nn_count
+ *   is stored to local_valid[rows[i]] and valid[local_idx[rows[i]]].  A row outside [0, n_local) or a global row outside
+ *   [0, n_global) is skipped. */
+PINGS_API size_t pings_frame_new_scratch_bytes(int64_t n);
+PINGS_API int pings_frame_new_count(const pings_knn_map* m, const float* point_certainties, int64_t num_points,
+                                    const float* coord, const float* sdf_label, int64_t n, double max_valid_dist2,
+                                    double new_certainty_thre, double label_thre, void* scratch, int64_t* count,
+                                    void* stream);
+PINGS_API int pings_frame_new_rows(const void* scratch, int64_t n, int64_t pool_offset, int64_t* rows,
+                                   int64_t capacity, void* stream);
+PINGS_API int pings_frame_static_mask(const float* sdf, const float* certainty, const float* grad, int64_t n,
+                                      double certainty_thre, double sdf_thre, double min_grad_norm, uint8_t* mask,
+                                      int64_t* dynamic_count, void* stream);
+PINGS_API int pings_frame_valid_scatter(const int64_t* rows, int64_t n, const float* sdf, const int64_t* nn_count,
+                                        double sdf_thre, int64_t min_nn_count, const int64_t* local_idx,
+                                        int64_t n_local, int64_t n_global, uint8_t* local_valid, uint8_t* valid,
+                                        void* stream);
+
 #endif /* PINGS_HIP_H_ */

@@ -338,4 +338,10 @@ SIGNATURES = {
     "pings_pool_window_scratch_bytes": (sz, [i64]),
     "pings_pool_window_count": (i32, [vp, i64, vp, f32, i32, vp, C.POINTER(i64), vp]),
     "pings_pool_window": (i32, [vp, i64, vp, f32, i32, vp, vp, i64, vp]),
+    # frame-time point tests
+    "pings_frame_new_scratch_bytes": (sz, [i64]),
+    "pings_frame_new_count": (i32, [C.POINTER(KnnMap), vp, i64, vp, vp, i64, f64, f64, f64, vp, C.POINTER(i64), vp]),
+    "pings_frame_new_rows": (i32, [vp, i64, i64, vp, i64, vp]),
+    "pings_frame_static_mask": (i32, [vp, vp, vp, i64, f64, f64, f64, vp, vp, vp]),
+    "pings_frame_valid_scatter": (i32, [vp, i64, vp, vp, f64, i64, vp, i64, i64, vp, vp, vp]),
 }

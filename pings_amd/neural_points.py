@@ -727,7 +727,7 @@ def _sdf_composed(npm, decoder, x, need_grad=False, need_certainty=False, query_
 
 def sdf_fused(npm, decoder, x: torch.Tensor, need_grad: bool = False, need_certainty: bool = False,
               query_locally: bool = True, use_only_measured_points: bool = True,
-              use_only_valid_points: bool = False, need_std: bool = False, want_idx: bool = False):
+              use_only_valid_points: bool = False, need_std: bool = False, want_idx: bool = False, out=None):
     """Fused inference query = `Mapper.sdf(x)` under no_grad (utils/mapper.py:2273-2289) and, with
     need_grad, the analytic gradient the tracker asks autograd for (utils/tracker.py:282-321).
 
@@ -735,10 +735,21 @@ def sdf_fused(npm, decoder, x: torch.Tensor, need_grad: bool = False, need_certa
     sdf_std[B] (spread of the per-neighbour predictions, utils/tracker.py:303-313).  `decoder` is the
     reference's `Decoder` (model/decoder.py) with one hidden level, or any object with
     `layers[0].weight/.bias`, `lout.weight/.bias`, `sdf_scale`.  With want_idx the neighbour rows idx[B,k] (int64, -1 =
-    none; rows of the local or global tables, as queried) are appended: what `color_fused` takes."""
+    none; rows of the local or global tables, as queried) are appended: what `color_fused` takes.  `out` = (sdf[B],
+    nn_counts[B]) lets a chunked caller have the kernel write into slices of its own arrays (contiguous float32 /
+    int64 on the query's device); they are then the tensors returned."""
+    if out is not None:
+        B_ = int(x.shape[0])
+        if not (len(out) == 2 and all(t.is_cuda and t.is_contiguous() and t.shape == (B_,) and t.device == x.device
+                                      for t in out) and out[0].dtype is torch.float32 and out[1].dtype is torch.int64):
+            raise _lib.PingsHipError("sdf_fused: `out` must be (float32 [B], int64 [B]), contiguous, on the query's device")
     if not fused_supported(npm, decoder):
         res = _sdf_composed(npm, decoder, x, need_grad, need_certainty, query_locally, use_only_measured_points,
                             use_only_valid_points, need_std)
+        if out is not None:
+            out[0].copy_(res[0])
+            out[1].copy_(res[2])
+            res = (out[0], res[1], out[1]) + res[3:]
         if want_idx:
             res = res + (radius_neighborhood_topk(npm, x, bool(npm.temporal_local_map_on and query_locally),
                                                   use_only_measured_points, use_only_valid_points, query_locally)[0],)
@@ -764,9 +775,9 @@ def sdf_fused(npm, decoder, x: torch.Tensor, need_grad: bool = False, need_certa
     dec = _abi.SdfDecoder(W1.data_ptr(), b1.data_ptr(), W2.data_ptr(), b2.data_ptr(), int(W1.shape[0]), int(F),
                           float(decoder.sdf_scale), int(weighted_first))
     dev = q.device
-    sdf = torch.empty(B, dtype=torch.float32, device=dev)
+    sdf = torch.empty(B, dtype=torch.float32, device=dev) if out is None else out[0]
     grad = torch.empty(B, 3, dtype=torch.float32, device=dev) if need_grad else None
-    cnt = torch.empty(B, dtype=torch.int64, device=dev)
+    cnt = torch.empty(B, dtype=torch.int64, device=dev) if out is None else out[1]
     cert = torch.empty(B, dtype=torch.float32, device=dev) if need_certainty else None
     std = torch.empty(B, dtype=torch.float32, device=dev) if need_std else None
     idx = torch.empty(B, a.nn_k, dtype=torch.int64, device=dev) if want_idx else None
