@@ -203,6 +203,12 @@ PINGS_API int pings_raster_debug_lists(const void* binning_blob, int64_t num_ins
                                        uint32_t* ranges_xy, void* stream);
 PINGS_API int pings_raster_debug_image(const void* image_blob, int image_height, int image_width,
                                        float* final_T, uint32_t* n_contrib, void* stream);
+/* The occlusion budget out of a geometry blob: `*occ_nb` (host) = rank buckets per tile for this image size;
+ * occ_bucket [occ_nb x tiles] fixed-point budget words, bucket-major; occ_bsat [tiles] last rank bucket a tile
+ * needs (0xFFFF = all).  With both device pointers null only `*occ_nb` is written (to size the copies). */
+PINGS_API int pings_raster_debug_occlusion(const void* geom_blob, int P, int image_height, int image_width,
+                                           uint32_t* occ_bucket, uint16_t* occ_bsat, int32_t* occ_nb,
+                                           void* stream);
 
 
 /* ------------------------------------------- 2D Gaussian splatting rasteriser

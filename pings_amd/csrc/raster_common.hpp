@@ -215,6 +215,7 @@ struct RasterKnobs {
   bool library_tile_sort = false;  // PINGS_TILE_SORT
   bool library_scan = false;     // PINGS_RASTER_SCAN
   float occ_amin = 0.15f;        // PINGS_OCC_AMIN
+  bool occ_walk_lanes = false;   // PINGS_OCC_WALK
   int rect_rule = RECT_TIGHT;    // PINGS_RASTER_RECT
   bool mark_depth_only = false;  // PINGS_MARK_VISIBLE
 };
@@ -538,6 +539,17 @@ __device__ inline uint32_t wave_inclusive_sum(uint32_t v, int lane) {
     const uint32_t u = __shfl_up(v, d, 64);
     if (lane >= d) v += u;
   }
+  return v;
+}
+
+// the same sum by DPP row shifts and row broadcasts: six vector instructions, no LDS crossbar round trips
+__device__ inline uint32_t wave_inclusive_sum_dpp(uint32_t v) {
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, false);  // row_shr:1
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xf, 0xf, false);  // row_shr:2
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xf, 0xf, false);  // row_shr:4
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xf, 0xf, false);  // row_shr:8
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x142, 0xa, 0xf, false);  // row_bcast:15 -> rows 1, 3
+  v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x143, 0xc, 0xf, false);  // row_bcast:31 -> rows 2, 3
   return v;
 }
 

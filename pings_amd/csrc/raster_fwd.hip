@@ -645,6 +645,19 @@ __device__ inline uint32_t rank_bucket(int r, int nb, uint32_t nvalid) {
   return min(b, (uint32_t)nb - 1u);
 }
 
+// The budget pass.  A lane owns one depth rank: its inner rectangle, the six record values tile_min_alpha reads and its
+// rank bucket.  DENSE (the product): the (rank, tile) pairs of the workgroup's 256 ranks are numbered through — one
+// exclusive sum of the inner-tile counts, inside the wave and then over the four wave totals in LDS, one barrier — and
+// thread t takes pairs t, t + 256, ...: every lane of every step has a pair until the workgroup's last step, whatever
+// the rectangle sizes.  The owner of pair p is the last rank whose offset is <= p: its wave from three compares with
+// the wave bases, then three 16-byte probes in LDS (the offsets of every 16th, every 4th and every rank of that wave,
+// four at a time: half the dependent round trips of a binary search); what a pair needs of its owner is nine words of
+// LDS (corner and width packed, the reciprocal width — one correctly rounded divide per rank instead of one per pair
+// — the bucket and the six record values).  A workgroup without a pair (most of those behind nvalid) ends after the
+// barrier.  !DENSE (PINGS_OCC_WALK=l): the dealing of walk_rects — a lane walks a rectangle of up to SMALL_RECT tiles
+// itself, the wave walks the larger ones one after the other.  The same pairs, the same arithmetic per pair and
+// integer atomics: the budget table is the same words either way.
+template <bool DENSE>
 __global__ __launch_bounds__(256) void occl_budget_kernel(int P, int gx, int nb,
                                                           const uint32_t* __restrict__ gidx_sorted,
                                                           const uint4* __restrict__ rect,
@@ -677,16 +690,64 @@ __global__ __launch_bounds__(256) void occl_budget_kernel(int P, int gx, int nb,
     if (a > 0.f)
       atomicAdd(&bucket[(size_t)b * num_tiles + (ty * gx + tx)], (uint32_t)(-__logf(1.f - a) * OCC_FIX));
   };
-  float smx = 0, smy = 0, so = 0, scx = 0, scy = 0, scz = 0;
-  uint32_t sb = 0;
-  walk_rects(
-      me, gx, [&](int tx, int ty) { add(tx, ty, ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, bk); },
-      [&](int src) {
-        smx = lane_value(ra.x, src); smy = lane_value(ra.y, src); so = lane_value(ra.z, src);
-        scx = lane_value(rb.x, src); scy = lane_value(rb.y, src); scz = lane_value(rb.z, src);
-        sb = lane_value(bk, src);
-      },
-      [&](int, int tx, int ty, bool act) { if (act) add(tx, ty, smx, smy, so, scx, scy, scz, sb); });
+  if constexpr (!DENSE) {
+    float smx = 0, smy = 0, so = 0, scx = 0, scy = 0, scz = 0;
+    uint32_t sb = 0;
+    walk_rects(
+        me, gx, [&](int tx, int ty) { add(tx, ty, ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, bk); },
+        [&](int src) {
+          smx = lane_value(ra.x, src); smy = lane_value(ra.y, src); so = lane_value(ra.z, src);
+          scx = lane_value(rb.x, src); scy = lane_value(rb.y, src); scz = lane_value(rb.z, src);
+          sb = lane_value(bk, src);
+        },
+        [&](int, int tx, int ty, bool act) { if (act) add(tx, ty, smx, smy, so, scx, scy, scz, sb); });
+  } else {
+    // first pair of a rank, counted from its wave's first pair: of every 16th rank, of every 4th and of every rank
+    __shared__ alignas(16) uint32_t sOff16[16], sOff4[64], sOff[256];
+    __shared__ uint32_t sTot[4];     // pairs per wave
+    __shared__ uint4 sGeo[256];      // xmin | ymin << 16, wdt | bucket << 16, 1 / wdt, conic z
+    __shared__ float4 sRec[256];     // mean x, mean y, opacity, conic x
+    __shared__ float sCy[256];       // conic y
+    const int t = (int)threadIdx.x, lane = t & 63, wave = t >> 6;
+    const uint32_t incl = wave_inclusive_sum_dpp(me.n);
+    sOff[t] = incl - me.n;
+    if ((t & 3) == 0) sOff4[t >> 2] = incl - me.n;
+    if ((t & 15) == 0) sOff16[t >> 4] = incl - me.n;
+    if (lane == 63) sTot[wave] = incl;
+    if (me.n != 0u) {
+      sGeo[t] = make_uint4((uint32_t)me.xmin | ((uint32_t)me.ymin << 16), (uint32_t)me.wdt | (bk << 16),
+                           __float_as_uint(1.0f / (float)me.wdt), __float_as_uint(rb.z));
+      sRec[t] = make_float4(ra.x, ra.y, ra.z, rb.x);
+      sCy[t] = rb.y;
+    }
+    __syncthreads();
+    const uint32_t b1 = sTot[0], b2 = b1 + sTot[1], b3 = b2 + sTot[2], total = b3 + sTot[3];
+    for (uint32_t p = (uint32_t)t; p < total; p += 256u) {
+      // equal bases (a wave without a pair) and equal offsets (a rank without one) resolve to the last of them
+      const int w = (int)(p >= b1) + (int)(p >= b2) + (int)(p >= b3);
+      const uint32_t q = p - (w == 0 ? 0u : w == 1 ? b1 : w == 2 ? b2 : b3);
+      // three 16-byte probes, four offsets each: the first of a group is <= q, so the count of those <= q, less one,
+      // is the last of them
+      auto last4 = [q](uint4 o) { return (int)(o.y <= q) + (int)(o.z <= q) + (int)(o.w <= q); };
+      int own = 4 * w + last4(reinterpret_cast<const uint4*>(sOff16)[w]);
+      own = 4 * own + last4(reinterpret_cast<const uint4*>(sOff4)[own]);
+      const uint4 o1 = reinterpret_cast<const uint4*>(sOff)[own];
+      const int j = last4(o1);
+      own = 4 * own + j;
+      const uint32_t k = q - (j == 0 ? o1.x : j == 1 ? o1.y : j == 2 ? o1.z : o1.w);
+      const uint4 ge = sGeo[own];
+      const float4 re = sRec[own];
+      const float cy = sCy[own];
+      const int wdt = (int)(ge.y & 0xFFFFu);
+      // k / wdt without an integer division (k < 2^24: the float quotient is off by at most one)
+      int yy = (int)((float)k * __uint_as_float(ge.z));
+      int xx = (int)k - yy * wdt;
+      if (xx < 0) { --yy; xx += wdt; }
+      if (xx >= wdt) { ++yy; xx -= wdt; }
+      add((int)(ge.x & 0xFFFFu) + xx, (int)(ge.x >> 16) + yy, re.x, re.y, re.z, re.w, cy, __uint_as_float(ge.w),
+          ge.y >> 16);
+    }
+  }
 }
 
 // Running budget over the rank buckets -> last bucket a tile needs.  A 512-thread workgroup takes 64 tiles x 8
@@ -1050,8 +1111,8 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
       }
       {
         pings::prof::Scope ps("occl_budget", st);
-        hipLaunchKernelGGL(occl_budget_kernel, grid, block, 0, st, P, kp.gx, gs.occ_nb, gs.gidx_sorted, gs.rect,
-                           gs.rec, gs.nvalid, num_tiles, gs.occ_bucket);
+        hipLaunchKernelGGL(knobs.occ_walk_lanes ? occl_budget_kernel<false> : occl_budget_kernel<true>, grid, block, 0,
+                           st, P, kp.gx, gs.occ_nb, gs.gidx_sorted, gs.rect, gs.rec, gs.nvalid, num_tiles, gs.occ_bucket);
         PINGS_LAUNCH_CHECK();
       }
     }

@@ -165,6 +165,8 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
 //   PINGS_RASTER_SCAN       own | l(ibrary)           tests, A/B    first letter l: hipcub::DeviceScan instead of the two-launch scans of
 //                                                                   raster_scan.hip (more than 16,777,216 elements: always the library)
 //   PINGS_OCC_AMIN          0.15 | x                  A/B           alpha below which a tile stays out of the occlusion budget, in [1/255, 0.99]
+//   PINGS_OCC_WALK          dense | l(anes)           tests, A/B    first letter l: occl_budget_kernel deals one rank to a lane (walk_rects)
+//                                                                   instead of the workgroup's pairs densely to its threads; same table
 //   PINGS_RASTER_RECT       tight | 3(sigma) | e(llipse)  bench, tests  tile-rectangle rule of preprocess_kernel, by first letter
 //   PINGS_MARK_VISIBLE      frustum | d(epth)         tests         first letter d: mark_visible tests depth only, the variant in which
 //                                                                   upstream's frustum test stays commented out (assumption 2)
@@ -199,6 +201,7 @@ RasterKnobs read_knobs() {
   // takes occl_budget 0.116 -> 0.053 ms and the step 1.136 -> 1.072 ms for 7.8 % more instances (0.2: 17 % more for
   // 0.005 ms); C2 / C3 unchanged.  1/255 = every covered tile, the round-2 behaviour.
   if (const char* e = getenv("PINGS_OCC_AMIN")) k.occ_amin = fminf(fmaxf((float)atof(e), 1.0f / 255.0f), 0.99f);
+  if (const char* e = getenv("PINGS_OCC_WALK")) k.occ_walk_lanes = e[0] == 'l';
   if (const char* e = getenv("PINGS_RASTER_RECT")) k.rect_rule = e[0] == '3' ? RECT_3SIGMA : e[0] == 'e' ? RECT_ELLIPSE : RECT_TIGHT;
   if (const char* e = getenv("PINGS_MARK_VISIBLE")) k.mark_depth_only = e[0] == 'd';
   return k;
@@ -278,6 +281,21 @@ PINGS_API int pings_raster_debug_lists(const void* binning_blob, int64_t I, int 
   }
   PINGS_HIP_CHECK(hipMemcpyAsync(ranges_xy, bs.ranges, sizeof(uint2) * (size_t)nt,
                                  hipMemcpyDeviceToDevice, st));
+  return PINGS_OK;
+}
+
+PINGS_API int pings_raster_debug_occlusion(const void* geom_blob, int P, int image_height, int image_width,
+                                           uint32_t* occ_bucket, uint16_t* occ_bsat, int32_t* occ_nb, void* stream) {
+  PINGS_ARG_CHECK(occ_nb, "null pointer");
+  const int nt = pings::ceil_div(image_width, TILE) * pings::ceil_div(image_height, TILE);
+  *occ_nb = occlusion_buckets(nt);
+  if (!occ_bucket && !occ_bsat) return PINGS_OK;   // the table's height alone: what the caller sizes its copies by
+  PINGS_ARG_CHECK(geom_blob && occ_bucket && occ_bsat, "null pointer");
+  GeomState gs = carve_geom(const_cast<void*>(geom_blob), P, nt);
+  hipStream_t st = pings::as_stream(stream);
+  PINGS_HIP_CHECK(hipMemcpyAsync(occ_bucket, gs.occ_bucket, sizeof(uint32_t) * (size_t)nt * (size_t)gs.occ_nb,
+                                 hipMemcpyDeviceToDevice, st));
+  PINGS_HIP_CHECK(hipMemcpyAsync(occ_bsat, gs.occ_bsat, sizeof(uint16_t) * (size_t)nt, hipMemcpyDeviceToDevice, st));
   return PINGS_OK;
 }
 

@@ -221,6 +221,24 @@ def debug_lists(fs: _ForwardState):
     return pl[:fs.I].long(), rg.view(nt, 2).long(), fT, nc
 
 
+def debug_occlusion(fs: _ForwardState):
+    """(occ_bucket[nb, num_tiles] int64, occ_bsat[num_tiles] int64 (0xFFFF = every bucket), nb) — the occlusion budget
+    of the frame, out of the geometry blob."""
+    L = _lib.lib()
+    dev = fs.geom.device
+    H, W = fs.prep.H, fs.prep.W
+    nt = ((W + 15) // 16) * ((H + 15) // 16)
+    nb = C.c_int32(0)
+    stream = _lib.stream_ptr(dev)
+    _lib.check(L.pings_raster_debug_occlusion(None, fs.P, H, W, None, None, C.byref(nb), stream),
+               "pings_raster_debug_occlusion")
+    bucket = torch.empty(nb.value * nt, dtype=torch.int32, device=dev)
+    bsat = torch.empty(nt, dtype=torch.int16, device=dev)
+    _lib.check(L.pings_raster_debug_occlusion(_lib.ptr(fs.geom), fs.P, H, W, _lib.ptr(bucket), _lib.ptr(bsat),
+                                              C.byref(nb), stream), "pings_raster_debug_occlusion")
+    return (bucket.view(nb.value, nt).long() & 0xFFFFFFFF), (bsat.long() & 0xFFFF), nb.value
+
+
 class _RasterizeGaussians(torch.autograd.Function):
     """autograd.Function over pings_raster_{preprocess,render,backward}.
 
