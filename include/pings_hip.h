@@ -1281,4 +1281,66 @@ PINGS_API int pings_frame_valid_scatter(const int64_t* rows, int64_t n, const fl
                                         int64_t n_local, int64_t n_global, uint8_t* local_valid, uint8_t* valid,
                                         void* stream);
 
+/* ------------------------------------------------------------- loop-closure context
+ * The scan-context descriptors and the global loop search of utils/loop_detector.py (`ptcloud2sc_torch`, `sc2rk`,
+ * `set_virtual_node`, `detect_loop`, `distance_sc_torch`, `distance_sc_feature_torch`) on caller-owned buffers.  A
+ * descriptor is sc[R,S] (largest z per ring / sector bin, 0.0 for a bin no point reached) and, with D-wide point
+ * features, sc_feat[R,S,D] (mean feature row per bin); a ring key is the mean over the sectors, [R] or [R,D].
+ * Limits: R <= PINGS_LOOP_MAX_R, S <= PINGS_LOOP_MAX_S, D <= PINGS_LOOP_MAX_D, poses / queries <= PINGS_LOOP_MAX_Q,
+ * candidates <= PINGS_LOOP_MAX_C; outside them (and for a null pointer) an entry returns PINGS_ERR_ARG.  No float
+ * atomics: maxima by integer atomics on an order-preserving key, feature sums by the deterministic row scatter in
+ * ascending point index, every other sum in a fixed order.  Two runs on the same input agree bit for bit.
+ *
+ * pings_loop_context_build: descriptors of M poses from one pass over points[n_points,3] (features[n_points,D] with
+ *   D > 0).  transforms[M,12] are row-major 3x4 fp32 (rounded once from fp64 by the caller; identity for a cloud in
+ *   its sensor frame).  Per (pose, point), in fp32: p' = T p, r = |p'|, kept iff r < max_length (false for NaN / inf
+ *   rows), theta = atan2(y', x') * 180 / pi + 180, ring = floor(r / (max_length / R)), sector = floor(theta / (360 / S)),
+ *   both clamped to the shape.  Outputs sc[M,R,S], ringkey[M,R] and, with D > 0, sc_feat[M,R,S,D], ringkey_feat[M,R,D].
+ *   use_stored[M] (DEVICE, nullable): a pose with a non-zero flag takes stored_sc[R,S], stored_ringkey[R]
+ *   (stored_sc_feat, stored_ringkey_feat) instead of what was built: the reference's centre pose (:135-139).
+ *   scratch: pings_loop_context_scratch_bytes(n_points, M, R, S, D) bytes (0 for arguments outside the limits).
+ * pings_loop_ring_key: `sc2rk` of one descriptor, sc[R,S] (D = 0) or sc[R,S,D].
+ * pings_loop_virtual_poses: the M = 2 * side_count + 1 lateral virtual poses of `set_virtual_node` (:84-133) from
+ *   frame_pose[4,4] and last_frame_pose[4,4] (nullable: lateral direction (0,1,0)), both DEVICE fp64 row-major with
+ *   last row (0,0,0,1): lat_tran[M,3] (fp32, as the reference forms it), tran_from_frame[M,4,4] (fp64),
+ *   transforms[M,12] = inv(frame_pose @ inv(T_k)) in fp64 rounded once, use_stored[k] = (|lat_tran[k]| == 0 in fp32).
+ *   Two identical consecutive poses give NaN everywhere, as in the reference.
+ * pings_loop_search: `detect_loop` (:250-295) in two launches.  bank_context[capacity, R*S*(use_feature ? D : 1)] and
+ *   bank_ringkey[capacity, R*(use_feature ? D : 1)] hold the nodes by slot; cand[C] are slots in the caller's order (a
+ *   slot outside [0, capacity) is skipped); the Q queries are query_context / query_ringkey in the same layouts.  Phase
+ *   one: ring-key distance of every (query, candidate) pair, L1 (plain) or 1 - cosine (features); the winner is the
+ *   smallest distance, then the earliest query, then the first candidate in cand order.  Phase two (a second launch that
+ *   reads the winner from `record`; skipped on the device when the distance exceeds ringkey_thre): for the shifts
+ *   i = 1..S the candidate is rolled by i sectors and the mean over the S (S*D) columns of the cosine similarity over
+ *   the R rings is taken (a zero column contributes 0; eps 1e-8); the largest mean wins, ties to the smallest shift.
+ *   record[8] (DEVICE int32): 0 position in cand (-1: none), 1 query, 2 ring-key distance (fp32 bits), 3 cosine distance
+ *   (fp32 bits), 4 shift in 1..S (S = no rotation), 5 gate (1 = phase two ran), 6-7 spare.  Fields 3 and 4 are written
+ *   only when the gate is open.  query_tran[Q,3] / win_tran[3] (nullable): the winner's row is copied to win_tran.
+ * pings_loop_context_distance: phase two alone on two descriptors (sc1 is the one rolled): record[3], record[4].
+ * pings_loop_read_record: one polled read of 8 words into record_host (HOST): record[0..7], or with win_tran_dev
+ *   record[0..4] followed by win_tran[0..2]. */
+#define PINGS_LOOP_MAX_R 32
+#define PINGS_LOOP_MAX_S 128
+#define PINGS_LOOP_MAX_D 16
+#define PINGS_LOOP_MAX_Q 16
+#define PINGS_LOOP_MAX_C 65536
+PINGS_API size_t pings_loop_context_scratch_bytes(int64_t n_points, int32_t M, int32_t R, int32_t S, int32_t D);
+PINGS_API int pings_loop_context_build(const float* points, int64_t n_points, const float* features, int32_t D,
+                                       const float* transforms, int32_t M, int32_t R, int32_t S, double max_length,
+                                       const int32_t* use_stored, const float* stored_sc, const float* stored_ringkey,
+                                       const float* stored_sc_feat, const float* stored_ringkey_feat, void* scratch,
+                                       float* sc, float* ringkey, float* sc_feat, float* ringkey_feat, void* stream);
+PINGS_API int pings_loop_ring_key(const float* sc, int32_t R, int32_t S, int32_t D, float* ringkey, void* stream);
+PINGS_API int pings_loop_virtual_poses(const double* frame_pose, const double* last_frame_pose, int32_t side_count,
+                                       double step_m, float* transforms, double* tran_from_frame, float* lat_tran,
+                                       int32_t* use_stored, void* stream);
+PINGS_API int pings_loop_search(const float* bank_context, const float* bank_ringkey, int64_t capacity,
+                                const int32_t* cand, int32_t C, const float* query_context, const float* query_ringkey,
+                                int32_t Q, int32_t R, int32_t S, int32_t D, int32_t use_feature, double ringkey_thre,
+                                const float* query_tran, int32_t* record, float* win_tran, void* stream);
+PINGS_API int pings_loop_context_distance(const float* sc1, const float* sc2, int32_t R, int32_t S, int32_t D,
+                                          int32_t* record, void* stream);
+PINGS_API int pings_loop_read_record(const int32_t* record_dev, const float* win_tran_dev, int32_t* record_host,
+                                     void* stream);
+
 #endif /* PINGS_HIP_H_ */

@@ -19,6 +19,8 @@ MC_ALLOW_DEGENERATE, MC_ASCENT = 1, 2                             # PINGS_MC_*: 
 ADAMW_MAX_JOBS, ADAMW_CHUNK = 48, 4096                            # PINGS_ADAMW_*: tensors per launch, elements per item
 EVAL_VIEW_RECORD, EVAL_PAIR_RECORD = 9, 12                        # PINGS_EVAL_*_RECORD: doubles per record
 EVAL_EXTENT = 1                                                   # PINGS_EVAL_EXTENT: status bit of the eval grids
+LOOP_MAX_R, LOOP_MAX_S, LOOP_MAX_D = 32, 128, 16                  # PINGS_LOOP_MAX_*: limits of the pings_loop_* entries
+LOOP_MAX_Q, LOOP_MAX_C = 16, 65536                                # poses / queries per call, candidates per search
 
 vp = C.c_void_p     # device pointers and the hipStream_t travel as integers (tensor.data_ptr())
 i32, i64, f32, f64, sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
@@ -345,4 +347,13 @@ SIGNATURES = {
     "pings_frame_new_rows": (i32, [vp, i64, i64, vp, i64, vp]),
     "pings_frame_static_mask": (i32, [vp, vp, vp, i64, f64, f64, f64, vp, vp, vp]),
     "pings_frame_valid_scatter": (i32, [vp, i64, vp, vp, f64, i64, vp, i64, i64, vp, vp, vp]),
+    # loop-closure context
+    "pings_loop_context_scratch_bytes": (sz, [i64, i32, i32, i32, i32]),
+    "pings_loop_context_build": (i32, [vp, i64, vp, i32, vp, i32, i32, i32, f64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp,
+                                       vp]),
+    "pings_loop_ring_key": (i32, [vp, i32, i32, i32, vp, vp]),
+    "pings_loop_virtual_poses": (i32, [vp, vp, i32, f64, vp, vp, vp, vp, vp]),
+    "pings_loop_search": (i32, [vp, vp, i64, vp, i32, vp, vp, i32, i32, i32, i32, i32, f64, vp, vp, vp, vp]),
+    "pings_loop_context_distance": (i32, [vp, vp, i32, i32, i32, vp, vp]),
+    "pings_loop_read_record": (i32, [vp, vp, vp, vp]),
 }
