@@ -2,7 +2,6 @@
 //
 //   blend_fwd_wave_kernel   one independent wave per 8x8 quadrant (the default); long tile lists in parallel segments
 //   blend_fwd_tile_kernel   one wave per 16x16 tile, four pixels per lane
-//   blend_fwd_kernel        one workgroup per tile, one or two pixels per lane (A/B variant, reference side of tests)
 //   per-Gaussian sums       `contributions` / `n_touched` are reduced per (tile, Gaussian) instance on chip (DPP wave
 //                           sum + LDS), stored once per instance, then summed per Gaussian: no global atomics
 //
@@ -12,247 +11,19 @@
 namespace pings {
 namespace raster {
 
-// PPL = pixels per lane (1 or 2).  A 16x16 tile is four 8x8 quadrants.  PPL = 1: wave w owns quadrant w
-// (qx = w & 1, qy = w >> 1), lane l the pixel (l & 7, l >> 3) of it.  PPL = 2: wave w owns the 8-pixel-wide
-// column half w (quadrants w and w + 2), lane l the two pixels (l & 7, l >> 3) and (l & 7, (l >> 3) + 8), which
-// share x: the x-part of the quadratic form, the record unpacking, the loop control and the wave reductions
-// are paid once per lane instead of once per pixel.
-//
-// Sub-tile culling: while a round of up to 256 records is staged in LDS, the staging thread of a record also
-// evaluates which quadrants its footprint ellipse (alpha >= 1/255) can reach (quadrant_mask).  Every wave then
-// compacts the records that may touch ITS pixels into a private index list (ballot + popcount, order kept) and
-// walks only that list: on surfel scenes 40-50 % of the (wave, record) visits of a plain tile walk blend
-// nothing, and a skipped record would have contributed exactly zero, so outputs are unchanged bit for bit.
-template <int MODE, int PPL>
-__global__ __launch_bounds__(BLOCK / PPL) void blend_fwd_kernel(
-    KParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
-    const float4* __restrict__ rec, const uint32_t* __restrict__ gval, float* __restrict__ out_color,
-    float* __restrict__ out_normal, float* __restrict__ out_depth, float* __restrict__ out_alpha,
-    float* __restrict__ final_T, uint32_t* __restrict__ n_contrib, float* __restrict__ inst_w,
-    uint32_t* __restrict__ inst_cnt, uint8_t* __restrict__ inst_qmask, int want_qmask) {
-  constexpr int NT = BLOCK / PPL;   // threads per workgroup
-  constexpr int NWV = NT / 64;      // waves per workgroup
-  constexpr int YS = 8;             // row distance of a lane's pixels
-  __shared__ float4 sA[BLOCK];  // mx, my, opacity, pz
-  __shared__ float4 sB[BLOCK];  // conic, rz
-  __shared__ float4 sC[BLOCK];  // rgb, q
-  __shared__ float4 sD[BLOCK];  // normal
-  __shared__ uint32_t sSlot[BLOCK];
-  __shared__ float sAcc[NWV][BLOCK];     // per-wave partial sums of blend weights
-  __shared__ uint32_t sCnt[NWV][BLOCK];  // per-wave counts (3DGS n_touched)
-  __shared__ uint8_t sQb[NWV][BLOCK];    // per-wave bits: quadrants in which the record blended something
-  __shared__ uint8_t sMask[BLOCK];       // quadrant mask of every staged record
-  __shared__ uint8_t sList[NWV][BLOCK];  // per-wave compacted record indices (ascending)
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int tile = blockIdx.x;
-  const int tx = tile % p.gx, ty = tile / p.gx;
-  const int pix_x = tx * TILE + (PPL == 1 ? 8 * (wave & 1) : 8 * wave) + (lane & 7);
-  const int pix_y0 = ty * TILE + (PPL == 1 ? 8 * (wave >> 1) : 0) + (lane >> 3);
-  const uint32_t need = PPL == 1 ? (1u << wave) : ((1u << wave) | (4u << wave));
-  const float pixf_x = (float)pix_x, pixf_y0 = (float)pix_y0;
-  const float tileX0 = (float)(tx * TILE), tileY0 = (float)(ty * TILE);
-  const size_t HW = (size_t)p.W * p.H;
-
-  float rx = 0.f, ry[PPL];
-#pragma unroll
-  for (int k = 0; k < PPL; ++k) ry[k] = 0.f;
-  if (MODE == MODE_SURFEL) {
-    const float cxp = (p.prcp ? p.prcp[0] : 0.5f) * (float)p.W - 0.5f;
-    const float cyp = (p.prcp ? p.prcp[1] : 0.5f) * (float)p.H - 0.5f;
-    rx = (pixf_x - cxp) / p.fx;
-#pragma unroll
-    for (int k = 0; k < PPL; ++k) ry[k] = ((pixf_y0 + (float)(YS * k)) - cyp) / p.fy;
-  }
-
-  const uint2 range = ranges[tile];
-  const int todo = (int)(range.y - range.x);
-
-  float T[PPL], C0[PPL], C1[PPL], C2[PPL], N0[PPL], N1[PPL], N2[PPL], D[PPL];
-  uint32_t last[PPL];
-  bool inside[PPL], done[PPL];
-  bool all_done = true;
-#pragma unroll
-  for (int k = 0; k < PPL; ++k) {
-    T[k] = 1.0f;
-    C0[k] = C1[k] = C2[k] = N0[k] = N1[k] = N2[k] = D[k] = 0.f;
-    last[k] = 0;
-    inside[k] = pix_x < p.W && (pix_y0 + YS * k) < p.H;
-    done[k] = !inside[k];
-    all_done = all_done && done[k];
-  }
-
-  for (int base = 0; base < todo; base += BLOCK) {
-    if (__syncthreads_and(all_done)) break;
-    const int n = min(BLOCK, todo - base);
-#pragma unroll
-    for (int rr = 0; rr < PPL; ++rr) {
-      const int e = tid + rr * NT;
-      if (e < n) {
-        const uint32_t slot = point_list[range.x + base + e];
-        const uint32_t g = gval[slot];
-        const float4 ra = rec[4 * (size_t)g + 0];
-        const float4 rb = rec[4 * (size_t)g + 1];
-        sA[e] = ra;
-        sB[e] = rb;
-        sC[e] = rec[4 * (size_t)g + 2];
-        if (MODE == MODE_SURFEL) sD[e] = rec[4 * (size_t)g + 3];
-        sSlot[e] = slot;
-        sMask[e] = (uint8_t)quadrant_mask(ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, tileX0, tileY0);
-#pragma unroll
-        for (int wv = 0; wv < NWV; ++wv) {
-          sAcc[wv][e] = 0.f;
-          if (PPL == 2) sQb[wv][e] = 0;
-          if (MODE == MODE_3DGS) sCnt[wv][e] = 0u;
-        }
-      }
-    }
-    __syncthreads();
-
-    // this wave's list: records whose footprint may reach its pixels, in list order
-    int cnt = 0;
-    for (int c0 = 0; c0 < n; c0 += 64) {
-      const int e = c0 + lane;
-      const bool hit = e < n && (sMask[e] & need) != 0;
-      const unsigned long long bal = __ballot(hit);
-      if (hit) sList[wave][cnt + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = (uint8_t)e;
-      cnt += __popcll(bal);
-    }
-    __builtin_amdgcn_wave_barrier();
-
-    // The record of list entry jj+1 is read from LDS while jj is blended; lanes that skip a Gaussian carry
-    // w = 0 and the only branches are wave-uniform.
-    int j = cnt > 0 ? (int)sList[wave][0] : 0;
-    float4 a = sA[j], b = sB[j], c = sC[j], nn = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (MODE == MODE_SURFEL) nn = sD[j];
-    for (int jj = 0; jj < cnt; ++jj) {
-      const int jn = (int)sList[wave][jj + 1 < cnt ? jj + 1 : jj];
-      const float4 a_n = sA[jn], b_n = sB[jn], c_n = sC[jn];
-      float4 n_n = nn;
-      if (MODE == MODE_SURFEL) n_n = sD[jn];
-      if (__all(all_done)) break;  // every pixel of this wave is saturated
-      // power = -0.5 (cx dx^2 + cz dy^2) - cy dx dy ; the dx-only part is shared by the lane's pixels
-      const float dx = a.x - pixf_x;
-      const float p0 = -0.5f * (b.x * dx * dx);
-      const float pxy = b.y * dx;
-      float alpha[PPL], test_T[PPL];
-      bool contrib[PPL];
-      bool any_c = false;
-#pragma unroll
-      for (int k = 0; k < PPL; ++k) {
-        const float dy = a.y - (pixf_y0 + (float)(YS * k));  // one rounding, as in the oracle
-        const float power = (p0 - 0.5f * (b.z * dy * dy)) - pxy * dy;
-        alpha[k] = fminf(ALPHA_MAX, a.z * __expf(power));
-        const bool valid = !done[k] && (power <= 0.0f) && (alpha[k] >= ALPHA_MIN);
-        test_T[k] = T[k] * (1.0f - alpha[k]);
-        const bool stop = valid && (test_T[k] < T_EPS);
-        contrib[k] = valid && !stop;
-        done[k] = done[k] || stop;
-        any_c = any_c || contrib[k];
-      }
-      if (__any(any_c)) {
-        float wsum = 0.f;
-        uint32_t touched = 0;
-#pragma unroll
-        for (int k = 0; k < PPL; ++k) {
-          const float w = contrib[k] ? alpha[k] * T[k] : 0.f;
-          wsum += w;
-          C0[k] = fmaf(c.x, w, C0[k]);
-          C1[k] = fmaf(c.y, w, C1[k]);
-          C2[k] = fmaf(c.z, w, C2[k]);
-          if (MODE == MODE_SURFEL) {
-            const float den = (nn.x * rx + nn.y * ry[k]) + nn.z;
-            float d = den < -DEN_EPS ? c.w * __builtin_amdgcn_rcpf(den) : a.w;
-            d = fminf(fmaxf(d, a.w - b.w), a.w + b.w);
-            N0[k] = fmaf(nn.x, w, N0[k]);
-            N1[k] = fmaf(nn.y, w, N1[k]);
-            N2[k] = fmaf(nn.z, w, N2[k]);
-            D[k] = fmaf(d, w, D[k]);
-          } else {
-            D[k] = fmaf(a.w, w, D[k]);
-            touched += (contrib[k] && test_T[k] > 0.5f) ? 1u : 0u;
-          }
-          T[k] = contrib[k] ? test_T[k] : T[k];
-          last[k] = contrib[k] ? (uint32_t)(base + j + 1) : last[k];
-        }
-        const float s = wave_reduce_sum_dpp(wsum);
-        if (lane == 63) sAcc[wave][j] = s;
-        if (PPL == 2 && want_qmask) {
-          // quadrants in which the record blended something, exactly (the Gaussian-per-lane backward kernel visits
-          // exactly these): a lane's pixel k lies in quadrant wave + 2 k.  With PPL 1 a wave IS a quadrant and the
-          // mask follows from sAcc; without `want_qmask` the pixel-per-lane backward kernel runs and needs none.
-          uint32_t qb = 0;
-#pragma unroll
-          for (int k = 0; k < PPL; ++k)
-            if (__ballot(contrib[k])) qb |= 1u << (wave + 2 * k);
-          if (lane == 63) sQb[wave][j] = (uint8_t)qb;
-        }
-        if (MODE == MODE_3DGS) {
-          const uint32_t cn = wave_reduce_sum_u32_dpp(touched);
-          if (lane == 63) sCnt[wave][j] = cn;
-        }
-      }
-      all_done = true;
-#pragma unroll
-      for (int k = 0; k < PPL; ++k) all_done = all_done && done[k];
-      a = a_n; b = b_n; c = c_n; nn = n_n;
-      j = jn;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int rr = 0; rr < PPL; ++rr) {
-      const int e = tid + rr * NT;
-      if (e < n) {
-        float v = sAcc[0][e];
-        uint32_t cn = (MODE == MODE_3DGS) ? sCnt[0][e] : 0u;
-        uint32_t qm = PPL == 1 ? (sAcc[0][e] != 0.f ? 1u : 0u) : (uint32_t)sQb[0][e];  // quadrants that blended
-#pragma unroll
-        for (int wv = 1; wv < NWV; ++wv) {
-          v += sAcc[wv][e];
-          qm |= PPL == 1 ? (sAcc[wv][e] != 0.f ? 1u << wv : 0u) : (uint32_t)sQb[wv][e];
-          if (MODE == MODE_3DGS) cn += sCnt[wv][e];
-        }
-        if (v != 0.f) {  // untouched slots stay at their memset zero
-          inst_w[sSlot[e]] = v;
-          inst_qmask[sSlot[e]] = (uint8_t)qm;
-          if (MODE == MODE_3DGS) inst_cnt[sSlot[e]] = cn;
-        }
-      }
-    }
-  }
-
-#pragma unroll
-  for (int k = 0; k < PPL; ++k) {
-    if (!inside[k]) continue;
-    const size_t pix_id = (size_t)(pix_y0 + YS * k) * p.W + pix_x;
-    const float A = 1.0f - T[k];
-    final_T[pix_id] = T[k];
-    n_contrib[pix_id] = last[k];
-    out_color[pix_id] = C0[k] + T[k] * p.bg[0];
-    out_color[HW + pix_id] = C1[k] + T[k] * p.bg[1];
-    out_color[2 * HW + pix_id] = C2[k] + T[k] * p.bg[2];
-    out_alpha[pix_id] = A;
-    if (MODE == MODE_SURFEL) {
-      out_normal[pix_id] = N0[k];
-      out_normal[HW + pix_id] = N1[k];
-      out_normal[2 * HW + pix_id] = N2[k];
-      out_depth[pix_id] = D[k] / fmaxf(A, DEPTH_ALPHA_EPS);
-    } else {
-      out_depth[pix_id] = D[k];
-    }
-  }
-}
-
 // ---------------------------------------------------------------- forward, one independent wave per 8x8 quadrant
-// Footprint class 1 (footprints of a few tiles).  In the workgroup-per-tile kernel above the four waves of a tile
-// share the staging rounds, and as their culled lists differ in length (a wave visits ~37 % of the staged records
-// on a street-like scene) they idle at the round barriers and cannot stop before the slowest one.  Here every wave
+// Footprint class 1 (footprints of a few tiles).  A 16x16 tile is four 8x8 quadrants; wave q of a workgroup owns
+// quadrant q (qx = q & 1, qy = q >> 1) of the workgroup's tile, lane l the pixel (l & 7, l >> 3) of it.  Sub-tile
+// culling: a record whose footprint ellipse (alpha >= 1/255) cannot reach the wave's quadrant would contribute
+// exactly zero to its pixels, so skipping it leaves the outputs unchanged bit for bit; a wave visits only ~37 % of
+// a tile's records on a street-like scene.  As the four culled lists of a tile differ that much in length, the waves
+// share nothing that would make them wait for each other (a kernel whose four waves staged the list together in
+// rounds idled at the round barriers and could not stop before the slowest one).  Every wave
 // walks the tile list by itself: 64 entries at a time it fetches slot -> Gaussian -> record (the next window is in
 // flight while the current one is blended), tests the footprint against ITS quadrant, compacts the survivors into
-// its own LDS slots and blends them; it stops as soon as its 64 pixels are done.  No barriers.  Per-instance sums
-// are written per quadrant (inst_wq / inst_cntq) and folded by combine_quadrants_kernel, so everything downstream
-// sees the same inst_w / inst_cnt / inst_qmask as from the workgroup kernel.  Pixel arithmetic is the same, op for op.
+// its own LDS slots and blends them front to back; it stops as soon as its 64 pixels are done.  No barriers.
+// Per-instance sums are written per quadrant (inst_wq / inst_cntq) and folded by combine_quadrants_kernel into
+// inst_w / inst_cnt / inst_qmask, which is all that the kernels downstream read.
 // Workgroups of four waves, wave = quadrant of ONE tile: the four walk the same list, so what one fetched (list entries,
 // ids, records) the others find in the CU's L1; as one-wave workgroups the four quadrants of a tile were dealt to four
 // XCDs (round-robin dispatch) and each fetched the list through its own L2.
@@ -1231,17 +1002,8 @@ int launch_blend_fwd(int mode, const KParams& kp, const BlendPlan& plan, int P, 
     pings::prof::Scope ps_blend("blend_fwd", st);
     const int e = with_mode(mode, [&](auto m) -> int {
       constexpr int M = m();
-      // (the per-instance sums the workgroup-per-tile and wave-per-tile kernels accumulate into were cleared with `ranges`)
-      auto workgroup_per_tile = [&](auto ppl) {
-        constexpr int L = ppl();
-        hipLaunchKernelGGL((blend_fwd_kernel<M, L>), dim3(num_tiles), dim3(BLOCK / L), 0, st, kp, bs.ranges,
-                           bs.point_list, gs.rec, bs.gval, o.color, o.normal, o.depth, o.alpha,
-                           im.final_T, im.n_contrib, bs.inst_w, bs.inst_cnt, bs.inst_qmask, (int)plan.want_qmask);
-      };
       switch (plan.fwd) {
-        case BlendPlan::FWD_WG1: workgroup_per_tile(std::integral_constant<int, 1>{}); break;
-        case BlendPlan::FWD_WG2: workgroup_per_tile(std::integral_constant<int, 2>{}); break;
-        case BlendPlan::FWD_TILE:
+        case BlendPlan::FWD_TILE:   // (the per-instance sums it stores into were cleared with `ranges`)
           hipLaunchKernelGGL((blend_fwd_tile_kernel<M>), dim3(num_tiles), dim3(64), 0, st, kp, bs.ranges,
                              bs.point_list, gs.rec, bs.gval, o.color, o.normal, o.depth, o.alpha,
                              im.final_T, im.n_contrib, bs.inst_w, bs.inst_cnt, bs.tile_order, bs.tile_maxc);

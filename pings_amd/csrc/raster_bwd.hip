@@ -2,16 +2,16 @@
 //
 //   live scan             cidx = exclusive scan of (inst_w > 0) over the instance slots: only
 //                         instances that blended something in the forward pass get a gradient row.
-//   blend_bwd_kernel      one 256-thread workgroup per 16x16 tile walks the tile's sorted list
-//                         back to front in batches of 64 records staged in LDS; dead instances are
-//                         skipped by the whole workgroup.  Each pixel re-derives alpha /
-//                         transmittance and forms the 16 per-(pixel, Gaussian) gradient terms of the
-//                         blend record; the wave reduces them with a transposed DPP reduce-scatter
-//                         (16 values x 64 lanes -> one 64-B row in 16 lanes, ~55 VALU ops instead of
-//                         96 for 16 separate wave sums; footprint class 2 starts it with the lane swaps,
-//                         raster_common.hpp: wave_reduce16_swap).  The four waves' rows are summed in LDS in
-//                         fixed order and stored ONCE per live instance as a 64-B row; the rows of
-//                         one Gaussian are contiguous (slot order = depth rank order).
+//   blend_bwd_tile_kernel footprint class 2, pixels on the lanes: one wave per 16x16 tile, four pixels per lane,
+//                         walks the tile's sorted list back to front in batches of 64 records staged in LDS;
+//                         dead instances and records whose footprint misses the tile are skipped.  Each pixel
+//                         re-derives alpha / transmittance and forms the 16 per-(pixel, Gaussian) gradient terms
+//                         of the blend record; the wave reduces them with a transposed reduce-scatter that starts
+//                         with the lane swaps (raster_common.hpp: wave_reduce16_swap; 16 values x 64 lanes -> one
+//                         64-B row).  The row is stored ONCE per live instance; the rows of one Gaussian are
+//                         contiguous (slot order = depth rank order).
+//   blend_bwd_scan_kernel footprint class 1, records on the lanes: one wave per 8x8 quadrant, two wave scans per
+//                         pixel instead of a reduction per record; one row per (live instance, quadrant).
 //   row_chunk_sum_kernel  balanced first level of the per-Gaussian sum: one 16-lane group per
 //                         (Gaussian, chunk of <= 64 rows) pair, lane = column, streaming 64-B rows.
 //   gaussian_bwd_kernel   per Gaussian (in index order, rows located through its depth rank): adds its chunk partials, then chains
@@ -39,324 +39,23 @@ constexpr int BATCH = 64;
 constexpr uint32_t LONG_TILES_MAX = 2048;
 constexpr uint32_t DEAD_ROW = 0xFFFFFFFFu;
 
-#define PINGS_BLEND_BWD_PARAMS                                                                         \
-    BParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,              \
-    const float4* __restrict__ rec, const uint32_t* __restrict__ gval,                                 \
-    const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib,                         \
-    const float* __restrict__ out_depth, const float* __restrict__ dL_dcolor,                          \
-    const float* __restrict__ dL_dnormal, const float* __restrict__ dL_ddepth,                         \
-    const float* __restrict__ dL_dalpha, const float* __restrict__ inst_w,                             \
-    const uint32_t* __restrict__ cidx, float* __restrict__ rows, const uint32_t* __restrict__ tile_order
-#define PINGS_BLEND_BWD_ARGS                                                                           \
-    p, ranges, point_list, rec, gval, final_T, n_contrib, out_depth, dL_dcolor, dL_dnormal, dL_ddepth, \
-    dL_dalpha, inst_w, cidx, rows, tile_order
-
-// PPL = pixels per lane (same lane -> pixel map as blend_fwd_kernel): the 16 gradient terms of a
-// lane's PPL pixels are summed in registers before the wave reduction, which is the expensive part.
-// PPL 1 / 2 (A/B variants, PINGS_BLEND_BWD_PPL): four / two waves per tile.  PPL 4 (footprint class 2): blend_bwd_tile.
-template <int MODE, int PPL>
-__device__ __forceinline__ void blend_bwd_pixels(PINGS_BLEND_BWD_PARAMS) {
-  constexpr int NT = BLOCK / PPL;
-  constexpr int NWV = NT / 64;
-  __shared__ float4 sA[BATCH], sB[BATCH], sC[BATCH], sD[BATCH];
-  __shared__ uint32_t sRow[BATCH];  // compact gradient-row index, DEAD_ROW for dead instances
-  __shared__ float4 sG[NWV][BATCH][4];
-  __shared__ uint32_t sMax;
-  __shared__ uint8_t sList[NWV][BATCH];  // per-wave list of live records that may reach its pixels (ascending)
-  __shared__ int sNum[NWV];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = tid >> 6;
-  const int tile = (int)tile_order[blockIdx.x];   // longest-processing-time-first dispatch (raster_fwd.hip)
-  const int tx = tile % p.gx, ty = tile / p.gx;
-  // lane -> pixel map and per-wave culled record lists as in blend_fwd_kernel (8x8 quadrants)
-  // PPL 1: wave = 8x8 quadrant; PPL 2: wave = 8x16 column strip (k -> y half); PPL 4: ONE wave owns the 16x16 tile
-  // (k & 1 -> x half, k >> 1 -> y half): no second wave to wait for, and the per-record overhead (LDS record fetch,
-  // 16-value wave reduction) is paid once per 256 pixels
-  constexpr int NXH = PPL == 4 ? 2 : 1;   // x halves per lane
-  const int pix_x = tx * TILE + (PPL == 1 ? 8 * (wave & 1) : (PPL == 2 ? 8 * wave : 0)) + (lane & 7);
-  const int pix_y0 = ty * TILE + (PPL == 1 ? 8 * (wave >> 1) : 0) + (lane >> 3);
-  const float pixf_x = (float)pix_x, pixf_y0 = (float)pix_y0;
-  auto xoff = [](int k) { return PPL == 4 ? 8 * (k & 1) : 0; };
-  auto yoff = [](int k) { return PPL == 4 ? 8 * (k >> 1) : 8 * k; };
-  const float tileX0 = (float)(tx * TILE), tileY0 = (float)(ty * TILE);
-  const size_t HW = (size_t)p.W * p.H;
-
-  float rxv[NXH], ry[PPL];
-#pragma unroll
-  for (int h = 0; h < NXH; ++h) rxv[h] = 0.f;
-#pragma unroll
-  for (int k = 0; k < PPL; ++k) ry[k] = 0.f;
-  if (MODE == MODE_SURFEL) {
-    const float cxp = (p.prcp ? p.prcp[0] : 0.5f) * (float)p.W - 0.5f;
-    const float cyp = (p.prcp ? p.prcp[1] : 0.5f) * (float)p.H - 0.5f;
-#pragma unroll
-    for (int h = 0; h < NXH; ++h) rxv[h] = ((pixf_x + (float)(8 * h)) - cxp) / p.fx;
-#pragma unroll
-    for (int k = 0; k < PPL; ++k) ry[k] = ((pixf_y0 + (float)yoff(k)) - cyp) / p.fy;
-  }
-
-  const uint2 range = ranges[tile];
-  uint32_t last[PPL];
-  float T[PPL], gC0[PPL], gC1[PPL], gC2[PPL], gN0[PPL], gN1[PPL], gN2[PPL], gD[PPL], coefT[PPL];
-  float Bs[PPL];  // blend of s = (upstream gradient) . (record features) over the records behind, normalised
-  uint32_t lmax = 0;
-#pragma unroll
-  for (int k = 0; k < PPL; ++k) {
-    last[k] = 0;
-    T[k] = 1.f;
-    gC0[k] = gC1[k] = gC2[k] = gN0[k] = gN1[k] = gN2[k] = gD[k] = coefT[k] = 0.f;
-    Bs[k] = 0.f;
-    const int pix_y = pix_y0 + yoff(k), pix_xk = pix_x + xoff(k);
-    if (pix_xk < p.W && pix_y < p.H) {
-      const size_t pix_id = (size_t)pix_y * p.W + pix_xk;
-      last[k] = n_contrib[pix_id];
-      const float T_final = final_T[pix_id];
-      T[k] = T_final;
-      if (dL_dcolor) {
-        gC0[k] = dL_dcolor[pix_id];
-        gC1[k] = dL_dcolor[HW + pix_id];
-        gC2[k] = dL_dcolor[2 * HW + pix_id];
-      }
-      float gA = dL_dalpha ? dL_dalpha[pix_id] : 0.f;
-      const float gDo = dL_ddepth ? dL_ddepth[pix_id] : 0.f;
-      if (MODE == MODE_SURFEL) {
-        if (dL_dnormal) {
-          gN0[k] = dL_dnormal[pix_id];
-          gN1[k] = dL_dnormal[HW + pix_id];
-          gN2[k] = dL_dnormal[2 * HW + pix_id];
-        }
-        const float A = 1.0f - T_final;
-        if (A > DEPTH_ALPHA_EPS) {
-          gD[k] = gDo / A;
-          gA -= gDo * out_depth[pix_id] / A;
-        }
-      } else {
-        gD[k] = gDo;
-      }
-      const float bgdot = (p.bg[0] * gC0[k] + p.bg[1] * gC1[k]) + p.bg[2] * gC2[k];
-      coefT[k] = (gA - bgdot) * T_final;
-    }
-    lmax = max(lmax, last[k]);
-  }
-
-  if (tid == 0) sMax = 0u;
-  __syncthreads();
-  {
-    uint32_t m = lmax;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) m = max(m, (uint32_t)__shfl_xor((int)m, off, 64));
-    if (lane == 0) atomicMax(&sMax, m);
-  }
-  __syncthreads();
-  const int max_last = (int)sMax;
-  // the 0.5 of the cov2D xx / yy gradient terms, applied to the reduced sums (lane < 16 holds slot red_slot)
-  const int red_slot = ((lane & 1) << 3) | ((lane & 2) << 1) | (lane >> 2);
-  const float red_scale = (red_slot == G_CONX || red_slot == G_CONZ) ? 0.5f : 1.0f;
-
-  const int nbatch = ceil_div(max_last, BATCH);
-  for (int b = nbatch - 1; b >= 0; --b) {
-    const int start = b * BATCH;
-    const int n = min(BATCH, max_last - start);
-    __syncthreads();  // previous batch's LDS fully consumed
-    if (wave == 0) {  // BATCH == 64: the first wave stages the batch and builds every wave's list
-      uint32_t qm = 0;
-      if (tid < n) {
-        const uint32_t slot = point_list[range.x + start + tid];
-        const uint32_t g = gval[slot];
-        const float4 ra = rec[4 * (size_t)g + 0];
-        const float4 rb = rec[4 * (size_t)g + 1];
-        sA[tid] = ra;
-        sB[tid] = rb;
-        sC[tid] = rec[4 * (size_t)g + 2];
-        if (MODE == MODE_SURFEL) sD[tid] = rec[4 * (size_t)g + 3];
-        const bool live = inst_w[slot] > 0.f;  // blended something in the forward pass
-        sRow[tid] = live ? cidx[slot] : DEAD_ROW;
-        if (live) qm = quadrant_mask(ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, tileX0, tileY0);
-      }
-#pragma unroll
-      for (int wv = 0; wv < NWV; ++wv) {
-        const uint32_t need = PPL == 1 ? (1u << wv) : (PPL == 2 ? ((1u << wv) | (4u << wv)) : 0xFu);
-        const bool hit = (qm & need) != 0;
-        const unsigned long long bal = __ballot(hit);
-        if (hit)
-          sList[wv][__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] =
-              (uint8_t)tid;
-        if (lane == 0) sNum[wv] = __popcll(bal);
-      }
-    }
-    {
-      float4* z = &sG[0][0][0];
-      const float4 zero = make_float4(0.f, 0.f, 0.f, 0.f);
-      for (int e = tid; e < NWV * BATCH * 4; e += NT) z[e] = zero;
-    }
-    __syncthreads();
-
-    // Record j-1 is read from LDS while j is processed; per-lane conditions are selects, the only
-    // branches are workgroup- or wave-uniform.
-    // Two-deep software pipeline over the wave's list: the INDEX of record jj-2 and the RECORD jj-1 are fetched
-    // from LDS while record jj is processed, so neither LDS latency (list byte -> record address -> 64-B record)
-    // sits in an iteration's dependency chain.
-    const int cnt = sNum[wave];
-    int jcur = cnt > 0 ? (int)sList[wave][cnt - 1] : 0;
-    int jnext = cnt > 1 ? (int)sList[wave][cnt - 2] : 0;
-    float4 a = sA[jcur], bq = sB[jcur], c = sC[jcur], nn = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (MODE == MODE_SURFEL) nn = sD[jcur];
-    // (unrolling this loop by two so that a record's reduction overlaps the next record's pixel math: no change, 0.349 ms)
-    for (int jj = cnt - 1; jj >= 0; --jj) {
-      const int j = jcur;
-      const int jn = jnext;
-      const int jn2 = (int)sList[wave][jj > 1 ? jj - 2 : 0];
-      const float4 a_n = sA[jn], b_n = sB[jn], c_n = sC[jn];
-      float4 n_n = nn;
-      if (MODE == MODE_SURFEL) n_n = sD[jn];
-      const float4 ca = a, cb = bq, cc = c, cn = nn;
-      a = a_n; bq = b_n; c = c_n; nn = n_n;
-      jcur = jn;
-      jnext = jn2;
-      const uint32_t idx = (uint32_t)(start + j);
-      float dxv[NXH], p0v[NXH], pxyv[NXH];
-#pragma unroll
-      for (int h = 0; h < NXH; ++h) {
-        dxv[h] = ca.x - (pixf_x + (float)(8 * h));
-        p0v[h] = -0.5f * (cb.x * dxv[h] * dxv[h]);
-        pxyv[h] = cb.y * dxv[h];
-      }
-      float Gs[PPL], raw[PPL], alpha[PPL], dyv[PPL];
-      bool valid[PPL];
-      bool any_v = false;
-#pragma unroll
-      for (int k = 0; k < PPL; ++k) {
-        const float dy = ca.y - (pixf_y0 + (float)yoff(k));
-        dyv[k] = dy;
-        const float p0 = p0v[PPL == 4 ? (k & 1) : 0], pxy = pxyv[PPL == 4 ? (k & 1) : 0];
-        const float power = (p0 - 0.5f * (cb.z * dy * dy)) - pxy * dy;
-        Gs[k] = __expf(power);
-        raw[k] = ca.z * Gs[k];
-        alpha[k] = fminf(ALPHA_MAX, raw[k]);
-        valid[k] = idx < last[k] && (power <= 0.0f) && (alpha[k] >= ALPHA_MIN);
-        any_v = any_v || valid[k];
-      }
-      if (!__any(any_v)) continue;
-
-      // The first pixel set assigns the 16 accumulators, the others add to them (no zeroing, no 0 + x per record).
-      // Changes against the forward-identical decisions below affect only the gradient sums, by rounding.
-      float v[16];
-      if (MODE != MODE_SURFEL) v[G_NX] = v[G_NY] = v[G_NZ] = v[G_Q] = v[G_ZLO] = v[G_ZHI] = 0.f;   // no surfel terms
-      const float zlo = ca.w - cb.w, zhi = ca.w + cb.w;
-      const float zlo_m = fminf(zlo, zhi);   // med3(d, min(lo, hi), hi) == fminf(fmaxf(d, lo), hi) for non-NaN d
-      // per-record products shared by the pixel sets of an x half / a row: q = conic . (dx, dy) as two adds
-      float cxdx[NXH], cydy[PPL], czdy[PPL];
-#pragma unroll
-      for (int h = 0; h < NXH; ++h) cxdx[h] = cb.x * dxv[h];
-#pragma unroll
-      for (int k = 0; k < PPL; ++k) {
-        cydy[k] = cb.y * dyv[k];
-        czdy[k] = cb.z * dyv[k];
-      }
-#pragma unroll
-      for (int k = 0; k < PPL; ++k) {
-        // gradient accumulation only (the alpha / validity decisions were taken above, un-contracted, exactly as in
-        // the forward pass): let multiply-adds fuse here — fewer instructions, one rounding less per term
-#pragma clang fp contract(fast)
-        // (a uniform `if (!__any(valid[k])) continue;` per pixel set here: 0.346 -> 0.399 ms — four more branches per
-        // record cost more than the skipped sets save)
-        const bool first = k == 0;
-        auto acc = [&](int q, float x) { v[q] = first ? x : v[q] + x; };
-        const int h = PPL == 4 ? (k & 1) : 0;
-        const float rx = rxv[h];
-        // Validity folded into alpha: an invalid pixel blends av = 0, so 1 - av = 1, rcp(1) = 1 exactly and Tn == T
-        // bit for bit; w = av * Tn and T = Tn need no select.  Valid pixels see the same operations as before.
-        const float av = valid[k] ? alpha[k] : 0.f;
-        const float one_m = 1.0f - av;
-        const float inv_one_m = __builtin_amdgcn_rcpf(one_m);  // 1-ulp reciprocal: alpha <= 0.99
-        const float Tn = T[k] * inv_one_m;
-        const float w = av * Tn;
-        // dL/dalpha needs sum_ch (feature_ch - B_ch) g_ch with B the normalised blend of the records behind.  Both
-        // the blend recurrence and the dot product are linear, so ONE scalar per pixel is tracked instead of the
-        // eight channels:  s = g . feature,  dLda = s - Bs,  Bs <- Bs + alpha (s - Bs).
-        float sdot = (cc.x * gC0[k] + cc.y * gC1[k]) + cc.z * gC2[k];
-        acc(G_R, gC0[k] * w);
-        acc(G_G, gC1[k] * w);
-        acc(G_B, gC2[k] * w);
-        if (MODE == MODE_SURFEL) {
-          sdot += (cn.x * gN0[k] + cn.y * gN1[k]) + cn.z * gN2[k];
-          // per-pixel depth of this surfel
-          const float den = (cn.x * rx + cn.y * ry[k]) + cn.z;
-          const bool hit = den < -DEN_EPS;
-          const float inv_den = __builtin_amdgcn_rcpf(den);
-          const float d0 = hit ? cc.w * inv_den : ca.w;
-          const float d = __builtin_amdgcn_fmed3f(d0, zlo_m, zhi);
-          sdot = fmaf(d, gD[k], sdot);
-          const float gd = gD[k] * w;
-          const bool lo = d0 < zlo, hi = d0 > zhi;
-          const bool mid = !lo && !hi;
-          acc(G_ZLO, lo ? gd : 0.f);
-          acc(G_ZHI, hi ? gd : 0.f);
-          const float gq = (mid && hit) ? gd * inv_den : 0.f;
-          acc(G_Q, gq);
-          acc(G_PZ, (mid && !hit) ? gd : 0.f);
-          const float gden = -gq * d0;  // = -gd * d0 / den on the unclamped ray hit, else 0
-          // two multiply-adds per normal component instead of multiply, multiply-add and add
-          v[G_NX] = fmaf(gden, rx, first ? gN0[k] * w : fmaf(gN0[k], w, v[G_NX]));
-          v[G_NY] = fmaf(gden, ry[k], first ? gN1[k] * w : fmaf(gN1[k], w, v[G_NY]));
-          v[G_NZ] = fmaf(gN2[k], w, first ? gden : v[G_NZ] + gden);
-        } else {
-          sdot = fmaf(ca.w, gD[k], sdot);
-          acc(G_PZ, gD[k] * w);
-        }
-        float dLda = sdot - Bs[k];
-        Bs[k] = fmaf(av, dLda, Bs[k]);
-        dLda = fmaf(dLda, Tn, coefT[k] * inv_one_m);
-        // alpha = min(0.99, opacity * G): no gradient through the clamp when it is active
-        dLda = (valid[k] && raw[k] <= ALPHA_MAX) ? dLda : 0.f;
-        acc(G_OPAC, Gs[k] * dLda);
-        const float dLp = raw[k] * dLda;  // dL/dpower = G * (opacity * dL/dalpha)
-        // q = conic . d.  d power / d mean = -q, and d power / d cov2D = 0.5 q q^T: accumulating the
-        // gradient w.r.t. the 2-D COVARIANCE here (instead of w.r.t. the conic, to be pushed through
-        // -conic G conic afterwards) keeps every per-pixel term O(1); the conic form sums d d^T terms
-        // of order 1e6 that must cancel to O(1) for large anisotropic footprints, which fp32 cannot do.
-        // The 0.5 of the xx / yy terms is applied once to the reduced sums (exact: a power of two).
-        const float qx = cxdx[h] + cydy[k], qy = pxyv[h] + czdy[k];
-        const float ux = dLp * qx, uy = dLp * qy;
-        acc(G_MX, -ux);
-        acc(G_MY, -uy);
-        acc(G_CONX, ux * qx);
-        acc(G_CONY, ux * qy);
-        acc(G_CONZ, uy * qy);
-        T[k] = Tn;
-      }
-      const float tot = wave_reduce16(v, lane) * red_scale;
-      // (one-wave kernel, PPL 4: storing the 64-byte row straight to global memory from here instead of through the
-      // LDS batch below was measured 5 % SLOWER: a scattered 16-lane store per record in the hot loop)
-      if (lane < 16)
-        reinterpret_cast<float*>(&sG[wave][j][0])[red_slot] = tot;
-    }
-    __syncthreads();
-    for (int e = tid; e < n * 4; e += NT) {
-      const int j = e >> 2, part = e & 3;
-      if (sRow[j] != DEAD_ROW) {
-        float4 s = sG[0][j][part];
-#pragma unroll
-        for (int wv = 1; wv < NWV; ++wv) {
-          const float4 r1 = sG[wv][j][part];
-          s.x += r1.x; s.y += r1.y; s.z += r1.z; s.w += r1.w;
-        }
-        reinterpret_cast<float4*>(rows)[(size_t)sRow[j] * 4 + part] = s;
-      }
-    }
-  }
-}
-
+// ---------------------------------------------------------------- blend backward, pixel-per-lane, wave per 16x16 tile
 // Footprint class 2: ONE wave owns the 16x16 tile, four pixels per lane (lane -> pixel map of blend_fwd_tile_kernel:
-// pixel (h, r) of lane l is (8h + (l & 7), 8r + (l >> 3)) in the tile).  The per-record overhead (LDS record fetch,
-// 16-value wave reduction) is paid once per 256 pixels, and a lane's two pixels of a row (h = 0, 1) are computed as
+// pixel (h, r) of lane l is (8h + (l & 7), 8r + (l >> 3)) in the tile).  The 16 gradient terms of a lane's four pixels
+// are summed in registers before the wave reduction, which is the expensive part: the per-record overhead (LDS record
+// fetch, 16-value wave reduction) is paid once per 256 pixels.  A lane's two pixels of a row (h = 0, 1) are computed as
 // one packed pair (f2: .x = left half, .y = right half): they share the row's dy / ry terms, their x terms are one
 // packed value, and nearly every per-pixel operation becomes one v_pk_* instruction for two pixels.  Only exp and the
 // reciprocals stay scalar.  The alpha / validity decisions are the forward pass's operations, component for component
 // (packed multiplies and adds round each component as the scalar ones do; no contraction there).
 template <int MODE>
-__device__ __forceinline__ void blend_bwd_tile(PINGS_BLEND_BWD_PARAMS) {
+__device__ __forceinline__ void blend_bwd_tile_body(
+    BParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+    const float4* __restrict__ rec, const uint32_t* __restrict__ gval, const float* __restrict__ final_T,
+    const uint32_t* __restrict__ n_contrib, const float* __restrict__ out_depth, const float* __restrict__ dL_dcolor,
+    const float* __restrict__ dL_dnormal, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha,
+    const float* __restrict__ inst_w, const uint32_t* __restrict__ cidx, float* __restrict__ rows,
+    const uint32_t* __restrict__ tile_order) {
   __shared__ float4 sA[BATCH], sB[BATCH], sC[BATCH], sD[BATCH];
   __shared__ uint32_t sRow[BATCH];  // compact gradient-row index, DEAD_ROW for dead instances
   __shared__ float4 sG[BATCH][4];
@@ -568,7 +267,11 @@ __device__ __forceinline__ void blend_bwd_tile(PINGS_BLEND_BWD_PARAMS) {
         dLda = sel2(valid[r][0] && raw[r].x <= ALPHA_MAX, valid[r][1] && raw[r].y <= ALPHA_MAX, dLda, f2{0.f, 0.f});
         acc(G_OPAC, Gs[r] * dLda);
         const f2 dLp = raw[r] * dLda;  // dL/dpower = G * (opacity * dL/dalpha)
-        // gradient w.r.t. the 2-D COVARIANCE (see blend_bwd_pixels): every per-pixel term O(1)
+        // q = conic . d.  d power / d mean = -q, and d power / d cov2D = 0.5 q q^T: accumulating the
+        // gradient w.r.t. the 2-D COVARIANCE here (instead of w.r.t. the conic, to be pushed through
+        // -conic G conic afterwards) keeps every per-pixel term O(1); the conic form sums d d^T terms
+        // of order 1e6 that must cancel to O(1) for large anisotropic footprints, which fp32 cannot do.
+        // The 0.5 of the xx / yy terms is applied once to the reduced sums (exact: a power of two).
         const f2 qx = cxdx + f2s(cb.y * dyv[r]), qy = pxy + f2s(cb.z * dyv[r]);
         const f2 ux = dLp * qx, uy = dLp * qy;
         acc(G_MX, -ux);
@@ -607,10 +310,20 @@ __device__ __forceinline__ void blend_bwd_tile(PINGS_BLEND_BWD_PARAMS) {
   }
 }
 
-template <int MODE, int PPL>
-__global__ __launch_bounds__(BLOCK / PPL, PPL == 4 ? 3 : 4) void blend_bwd_kernel(PINGS_BLEND_BWD_PARAMS) {
-  if constexpr (PPL == 4) blend_bwd_tile<MODE>(PINGS_BLEND_BWD_ARGS);
-  else blend_bwd_pixels<MODE, PPL>(PINGS_BLEND_BWD_ARGS);
+// The kernel is its body inlined (as blend_fwd_wave_kernel is blend_fwd_wave_body).  With the body written straight
+// into the __global__ function the compiler handles `p` differently (kernel argument, not a by-value copy), and the
+// record loop came out with other operand orders and a slightly different schedule: 0.306 -> 0.311 ms on the Metric-1
+// cloud in one A/B, at the edge of the run-to-run spread.  This form compiles to the same instructions as before.
+template <int MODE>
+__global__ __launch_bounds__(64, 3) void blend_bwd_tile_kernel(
+    BParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
+    const float4* __restrict__ rec, const uint32_t* __restrict__ gval, const float* __restrict__ final_T,
+    const uint32_t* __restrict__ n_contrib, const float* __restrict__ out_depth, const float* __restrict__ dL_dcolor,
+    const float* __restrict__ dL_dnormal, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha,
+    const float* __restrict__ inst_w, const uint32_t* __restrict__ cidx, float* __restrict__ rows,
+    const uint32_t* __restrict__ tile_order) {
+  blend_bwd_tile_body<MODE>(p, ranges, point_list, rec, gval, final_T, n_contrib, out_depth, dL_dcolor, dL_dnormal,
+                            dL_ddepth, dL_dalpha, inst_w, cidx, rows, tile_order);
 }
 
 // ---------------------------------------------------------------- blend backward, Gaussian-per-lane ("wave64 scan")
@@ -1378,15 +1091,9 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
                            bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor, dL_dnormal,
                            dL_ddepth, dL_dalpha, bs.inst_qmask, bw.cidx, bw.rows, order, n_long);
       } else {
-        auto pixel = [&](auto ppl) {
-          constexpr int L = ppl();
-          hipLaunchKernelGGL((blend_bwd_kernel<M, L>), dim3(num_tiles), dim3(BLOCK / L), 0, st, bp, bs.ranges,
-                             bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor,
-                             dL_dnormal, dL_ddepth, dL_dalpha, bs.inst_w, bw.cidx, bw.rows, order);
-        };
-        if (plan.bwd_ppl == 1) pixel(std::integral_constant<int, 1>{});
-        else if (plan.bwd_ppl == 4) pixel(std::integral_constant<int, 4>{});
-        else pixel(std::integral_constant<int, 2>{});
+        hipLaunchKernelGGL((blend_bwd_tile_kernel<M>), dim3(num_tiles), dim3(64), 0, st, bp, bs.ranges,
+                           bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor,
+                           dL_dnormal, dL_ddepth, dL_dalpha, bs.inst_w, bw.cidx, bw.rows, order);
       }
     });
     PINGS_LAUNCH_CHECK();

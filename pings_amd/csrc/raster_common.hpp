@@ -50,7 +50,7 @@ constexpr int RECT_TIGHT = 0, RECT_3SIGMA = 1, RECT_ELLIPSE = 2;
 
 // 16 floats of per-instance gradient accumulated by the blend backward pass
 // (one 64-B row per (tile, Gaussian) instance, summed per Gaussian afterwards).
-// G_CONX/Y/Z hold dL/d(cov2D xx, xy, yy) — NOT the gradient w.r.t. the conic (see blend_bwd_kernel).
+// G_CONX/Y/Z hold dL/d(cov2D xx, xy, yy) — NOT the gradient w.r.t. the conic (see blend_bwd_tile_kernel).
 constexpr int GRAD_ROW = 16;
 constexpr int CH = 64;  // rows per first-level chunk of the per-Gaussian sum
 enum GradSlot {
@@ -206,7 +206,6 @@ struct RasterKnobs {
   enum Bwd { BWD_AUTO, BWD_PIXEL, BWD_SCAN };
   int blend_ppl = 0;             // PINGS_BLEND_PPL
   Bwd blend_bwd = BWD_AUTO;      // PINGS_BLEND_BWD
-  int blend_bwd_ppl = 0;         // PINGS_BLEND_BWD_PPL: 0 (unset) | 1 | 2 | 4
   uint32_t blend_seg = 512u;     // PINGS_BLEND_SEG
   bool seg_reuse = true;         // PINGS_BLEND_SEG_REUSE
   uint32_t bwd_long = 3072u;     // PINGS_BWD_LONG: the threshold itself (never = 0xFFFFFFF0)
@@ -224,10 +223,9 @@ RasterKnobs read_knobs();
 // Which blend kernels a view runs.  pings_raster_render and pings_raster_backward both derive it from the same
 // arguments and branch on nothing else: the forward writes the exact quadrant masks iff the backward will scan them.
 struct BlendPlan {
-  enum Fwd { FWD_WG1, FWD_WG2, FWD_TILE, FWD_WAVE } fwd;  // workgroup per tile with 1 | 2 pixels per lane, wave per tile, wave per quadrant
+  enum Fwd { FWD_TILE, FWD_WAVE } fwd;  // wave per tile, wave per quadrant
   bool want_qmask;     // forward writes exact quadrant masks
-  bool bwd_scan;       // Gaussian-per-lane backward; else pixel-per-lane
-  int bwd_ppl;         // 1 | 2 | 4, pixel-per-lane backward only
+  bool bwd_scan;       // Gaussian-per-lane backward; else pixel-per-lane (wave per tile)
   uint32_t seg;        // entries per segment of the segmented forward of long tile lists
   bool seg_on, seg_reuse;
   uint32_t long_thr;   // four-wave split threshold of the scan backward
@@ -365,9 +363,9 @@ __device__ inline float sel4(const float (&t)[4], bool m0, bool m1) {
 // steps (16 -> 8 -> 4 values per lane), one rotate step inside each 16-lane row (4 -> 1) and
 // two cross-row adds.  Afterwards lane l of EVERY row holds the wave total of slot
 //   8*(l&1) + 4*((l>>1)&1) + ((l>>2)&3).
-// Used by the forward kernels (the per-Gaussian weight and contribution sums) and by blend_bwd_pixels, the PPL 1 / 2
-// A/B variants of the backward.  The class-2 backward uses wave_reduce16_swap below; the forward keeps this one because
-// another order of the adds would change the bits of `contributions` and of the weight sums.
+// Used by the forward kernels only (the per-Gaussian weight and contribution sums).  The class-2 backward uses
+// wave_reduce16_swap below; the forward keeps this one because another order of the adds would change the bits of
+// `contributions` and of the weight sums.
 __device__ inline float wave_reduce16(const float (&v)[16], int lane) {
   const bool b0 = lane & 1, b1 = lane & 2;
   float u[8];
@@ -406,7 +404,7 @@ __device__ inline float wave_reduce16(const float (&v)[16], int lane) {
   return r;
 }
 
-// The same 16 sums for the class-2 blend backward (blend_bwd_tile, raster_bwd.hip), which has the 16 terms as packed
+// The same 16 sums for the class-2 blend backward (blend_bwd_tile_kernel, raster_bwd.hip), which has the 16 terms as packed
 // pairs and is bound by vector issue: the WIDE stages go through the swaps, the narrow ones through DPP.
 //   fold           16 adds                       x + y of each pair
 //   16 -> 8        8 x (v_permlane32_swap, add)  swap(a, b) leaves a = {a.lo, b.lo}, b = {a.hi, b.hi}: a + b is a's sum

@@ -1171,9 +1171,11 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
   // wrapped, and its last entry is this number
   PINGS_ARG_CHECK(stats[2] < 0x7FFFFFFFull, "more than 2^31 - 1 (Gaussian, tile) instances in this frame");
   *num_instances = (int64_t)stats[2];
-  // Footprints of many tiles keep most lanes of a wave busy: two pixels per lane then amortise the per-record
-  // work; small footprints leave lanes idle and one pixel per lane (four 8x8 waves with their own culled lists)
-  // wins (measured: 52 tiles per Gaussian -> PPL 2 is 6 % faster, 5.6 tiles per Gaussian -> PPL 1 is 19 % faster).
+  // Class 2 = more than 16 (Gaussian, tile) pairs per visible Gaussian.  Footprints of many tiles reach nearly every
+  // pixel of a tile: blend_plan gives such a view one wave per tile with four pixels per lane, forward and backward
+  // (blend_fwd_tile_kernel, blend_bwd_tile_kernel), which amortises the per-record work.  Small footprints (class 1)
+  // would leave most of those lanes idle: one wave per 8x8 quadrant with its own culled list forward
+  // (blend_fwd_wave_kernel) and the Gaussian-per-lane scan backward (blend_bwd_scan_kernel).
   *footprint_class = (stats[1] > 0 && stats[0] > 16ull * stats[1]) ? 2 : 1;
   return PINGS_OK;
 }

@@ -149,10 +149,10 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
 // ---------------------------------------------------------------- environment knobs and the launch plan
 // The product sets none of these: the defaults ARE the product; tests and A/B tools force the other branches.
 //   knob                    values (default first)    set by        meaning
-//   PINGS_BLEND_PPL         0 | 1 | 2 | 4 | other     tests         forward blend kernel: 0 = by blend_plan; 1 | 2 = workgroup per tile with
-//                                                                   that many pixels per lane; 4 = wave per tile; other (-1) = wave per quadrant
-//   PINGS_BLEND_BWD         unset | pixel | other     tests         blend backward: unset = by footprint class; anything but "pixel" = scan
-//   PINGS_BLEND_BWD_PPL     unset | 1 | 4 | other     tests         pixels per lane of the pixel-per-lane backward; other than 1 and 4 = 2
+//   PINGS_BLEND_PPL         0 | 4 | other             tests         forward blend kernel: 0 = by blend_plan; 4 = wave per tile (four pixels
+//                                                                   per lane); other (-1) = wave per quadrant
+//   PINGS_BLEND_BWD         unset | pixel | other     tests         blend backward: unset = by footprint class; "pixel" = pixel-per-lane
+//                                                                   (wave per tile); anything else = scan
 //   PINGS_BLEND_SEG         512 | n | 0               tests         entries per segment of the segmented forward of long tile lists, 0 = off;
 //                                                                   also sizes the segment tables of the binning blob (carve_binning)
 //   PINGS_BLEND_SEG_REUSE   1 | 0                     tests         0: pass B re-tests every entry instead of walking pass T's compacted lists
@@ -174,10 +174,6 @@ RasterKnobs read_knobs() {
   RasterKnobs k;   // the defaults: raster_common.hpp
   if (const char* e = getenv("PINGS_BLEND_PPL")) k.blend_ppl = atoi(e);
   if (const char* e = getenv("PINGS_BLEND_BWD")) k.blend_bwd = strcmp(e, "pixel") != 0 ? RasterKnobs::BWD_SCAN : RasterKnobs::BWD_PIXEL;
-  if (const char* e = getenv("PINGS_BLEND_BWD_PPL")) {
-    const int v = atoi(e);
-    k.blend_bwd_ppl = (v == 1 || v == 4) ? v : 2;
-  }
   if (const char* e = getenv("PINGS_BLEND_SEG")) k.blend_seg = (uint32_t)atoi(e);
   if (const char* e = getenv("PINGS_BLEND_SEG_REUSE")) k.seg_reuse = atoi(e) != 0;
   // blend_bwd_scan_kernel: tiles whose largest per-pixel contributor count reaches the threshold get four waves per
@@ -214,20 +210,17 @@ BlendPlan blend_plan(const RasterKnobs& k, int footprint_class, int64_t I, int n
   // kernel would stay half empty and every instance would need four rows: 25 % faster on the Metric-1 cloud).
   // `footprint_class` comes from pings_raster_preprocess.
   p.bwd_scan = k.blend_bwd == RasterKnobs::BWD_AUTO ? footprint_class != 2 : k.blend_bwd == RasterKnobs::BWD_SCAN;
-  // the scan backward reads the exact per-quadrant masks, so the forward of the same view has to write them; they
-  // only cost something in the 2-pixels-per-lane forward
+  // the scan backward reads the exact per-quadrant masks, so the forward of the same view has to write them: only
+  // the wave-per-quadrant forward does
   p.want_qmask = p.bwd_scan;
-  // class 2: one wave per tile, four pixels per lane (0.40 -> 0.35 ms on Metric-1 vs two)
-  p.bwd_ppl = k.blend_bwd_ppl ? k.blend_bwd_ppl : footprint_class == 2 ? 4 : 1;
-  // The wave-per-quadrant kernel is the fastest forward on both footprint classes (Metric-1: 0.244 vs 0.265 ms for
-  // the workgroup-per-tile kernel with two pixels per lane; street-like scene: 0.86 vs 1.31 ms with one).  Footprint
+  // The pixel-per-lane backward is one wave per tile with four pixels per lane (0.40 -> 0.35 ms on Metric-1 against
+  // the removed two-waves-per-tile kernel with two).
+  // The wave-per-quadrant kernel is the forward of footprint class 1 (against the removed workgroup-per-tile kernels:
+  // Metric-1 0.244 vs 0.265 ms with two pixels per lane; street-like scene 0.86 vs 1.31 ms with one).  Footprint
   // class 2 with the pixel-per-lane backward to follow (no quadrant masks needed): wave per TILE, four pixels per
   // lane (Metric-1: 0.245 -> see DESIGN).
   const bool tile_wave = k.blend_ppl == 4 || (k.blend_ppl == 0 && footprint_class == 2 && !p.want_qmask);
-  p.fwd = k.blend_ppl == 1 ? BlendPlan::FWD_WG1
-        : k.blend_ppl == 2 ? BlendPlan::FWD_WG2
-        : tile_wave        ? BlendPlan::FWD_TILE
-                           : BlendPlan::FWD_WAVE;
+  p.fwd = tile_wave ? BlendPlan::FWD_TILE : BlendPlan::FWD_WAVE;
   // long lists in parallel segments (see blend_fwd_seg_kernel); pass B walks pass T's compacted lists (16-bit offsets)
   p.seg = k.blend_seg;
   p.seg_on = p.seg > 0 && I > (int64_t)num_tiles * (p.seg / 4) && I > 2 * (int64_t)p.seg;

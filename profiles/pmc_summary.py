@@ -33,8 +33,8 @@ FETCH_FACTOR = {
     # the blend kernels read 64-B tile-row pieces of the pixel planes (exact) and the per-Gaussian blend records, which
     # are four float4 = 64 B at a 64-B stride (csrc/raster_fwd.hip: rec[4 g + 0..3]): one aligned sector each (exact,
     # like the 8-B probes of the calibration; the 48-B pattern of pmc_calib.hip does not apply to them)
-    "blend_bwd_kernel": (1.0, "64-B tile-row pieces + 64-B aligned records: one half-line request each (exact)"),
-    "blend_bwd_scan_kernel": (1.0, "as blend_bwd_kernel"),
+    "blend_bwd_tile_kernel": (1.0, "64-B tile-row pieces + 64-B aligned records: one half-line request each (exact)"),
+    "blend_bwd_scan_kernel": (1.0, "as blend_bwd_tile_kernel"),
     "blend_fwd_tile_kernel": (1.0, "64-B aligned records; its pixel traffic is writes"),
     "blend_fwd_wave_kernel": (1.0, "64-B aligned records"),
     "blend_fwd_seg_kernel": (1.0, "64-B aligned records"),

@@ -1,4 +1,4 @@
-"""Class-2 blend backward (blend_bwd_kernel<MODE, 4>): the swap-first row reduction (wave_reduce16_swap), its lane ->
+"""Class-2 blend backward (blend_bwd_tile_kernel<MODE>): the swap-first row reduction (wave_reduce16_swap), its lane ->
 slot map and store predicate, and the record loop unrolled by two, on the smallest scenes at which they can go wrong.
 Every case forces the class-2 kernels the way test_blend_class2.py does and is run twice (bitwise reproducible).
 

@@ -1,5 +1,5 @@
 """Footprint class 2 blend kernels (wave per 16x16 tile, four pixels per lane: blend_fwd_tile_kernel and
-blend_bwd_kernel<MODE, 4>) on large-footprint scenes that reach their edge cases: pixels past n_contrib, power > 0,
+blend_bwd_tile_kernel<MODE>) on large-footprint scenes that reach their edge cases: pixels past n_contrib, power > 0,
 alpha just around 1/255, raw = opacity * G above the 0.99 clamp, and (surfel) per-pixel depths clamped on both
 sides and rays near the grazing threshold."""
 import pytest
@@ -26,6 +26,7 @@ def _edge_scene(mode, seed, P=260, W=144, H=96):
 
 def _forward_outputs(sc, mode, ppl, monkeypatch):
     monkeypatch.setenv("PINGS_BLEND_PPL", ppl)
+    monkeypatch.setenv("PINGS_BLEND_SEG", "0")   # no list regrouped into parallel segments by the quadrant forward
     monkeypatch.setenv("PINGS_BLEND_BWD", "pixel")
     hr, prep, fs, radii, per_g = _hip_forward(sc, mode, True)
     pl, rg, fT, nc = hr.debug_lists(fs)
@@ -37,12 +38,12 @@ def _forward_outputs(sc, mode, ppl, monkeypatch):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode,seed", [("surfel", 41), ("surfel", 42), ("3dgs", 43)])
-def test_tile_forward_bit_identical_to_workgroup_forward(mode, seed, monkeypatch):
-    """Both kernels blend each pixel serially front to back with the same operations: every image plane, final_T and
-    n_contrib must agree bit for bit."""
+def test_tile_forward_bit_identical_to_quadrant_forward(mode, seed, monkeypatch):
+    """The wave-per-tile and the wave-per-quadrant forward blend each pixel serially front to back with the same
+    operations: every image plane, final_T and n_contrib must agree bit for bit."""
     sc = _edge_scene(mode, seed)
     a = _forward_outputs(sc, mode, "4", monkeypatch)
-    b = _forward_outputs(sc, mode, "1", monkeypatch)
+    b = _forward_outputs(sc, mode, "-1", monkeypatch)
     nc = a["n_contrib"]
     assert int(nc.max()) > 0 and bool((nc < nc.max()).any())   # the scene does reach pixels past n_contrib
     for k in a:
@@ -53,11 +54,9 @@ def _grads(sc, mode, ups, bwd, monkeypatch):
     if bwd == "tile":
         monkeypatch.setenv("PINGS_BLEND_PPL", "4")
         monkeypatch.setenv("PINGS_BLEND_BWD", "pixel")
-        monkeypatch.setenv("PINGS_BLEND_BWD_PPL", "4")
     else:
         monkeypatch.setenv("PINGS_BLEND_PPL", "0")
         monkeypatch.setenv("PINGS_BLEND_BWD", "scan")
-        monkeypatch.delenv("PINGS_BLEND_BWD_PPL", raising=False)
     _, got, _ = _hip_grads(sc, mode, True, ups)
     return [g.detach().cpu().clone() for g in got]
 

@@ -3,7 +3,7 @@ lane four pixels and compute a row's two pixels (x halves 8 apart) as one packed
 row a pair can hold one pixel inside the image and one outside it: the outside pixel must stay inert component-wise
 (no blend, no gradient, transmittance untouched) while its partner blends.  150 x 100 leaves 6 / 4 pixels in the last
 tile (only the left half of a pair inside); 156 x 108 leaves 12 / 12 (left half inside, right half partly).  Same three
-properties as test_blend_class2.py: tile forward bit-identical to the pixel-per-lane forward, class-2 backward within
+properties as test_blend_class2.py: tile forward bit-identical to the wave-per-quadrant forward, class-2 backward within
 1e-4 of the scan backward and under the fp64 oracle gate, bitwise reproducible."""
 import pytest
 import torch
@@ -19,7 +19,7 @@ CASES = [("surfel", 61, 150, 100), ("3dgs", 62, 150, 100), ("surfel", 63, 156, 1
 def test_partial_tile_forward_bit_identical(mode, seed, W, H, monkeypatch):
     sc = _edge_scene(mode, seed, W=W, H=H)
     a = _forward_outputs(sc, mode, "4", monkeypatch)
-    b = _forward_outputs(sc, mode, "1", monkeypatch)
+    b = _forward_outputs(sc, mode, "-1", monkeypatch)
     nc = a["n_contrib"].reshape(H, W)
     # blending reaches into the partial last tile column and row
     assert int(nc[:, W - W % 16:].max()) > 0 and int(nc[H - H % 16:, :].max()) > 0

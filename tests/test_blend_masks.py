@@ -153,7 +153,7 @@ BWD_SURFEL_CASES = ("clamp_lo", "clamp_hi", "mid_hit", "mid_nohit", "pair_two_cl
 @pytest.mark.parametrize("needles", [False, True])
 @pytest.mark.parametrize("mode,seed", CASES)
 def test_tile_forward_masks_bit_identical_and_counts_match_the_oracle(mode, seed, needles, monkeypatch):
-    """Tile kernel against the pixel-per-lane forward, bit for bit, and n_contrib against the fp32 oracle wherever fp32
+    """Tile kernel against the wave-per-quadrant forward, bit for bit, and n_contrib against the fp32 oracle wherever fp32
     can decide the stop rule.  The plain scene reaches every forward case but `power > 0` and is decidable on all but
     a few pixels; the needle scene adds `power > 0` (its footprints make most pixels undecidable for the oracle gate,
     not for the comparison of the two kernels, which evaluate the same fp32 operations)."""
@@ -168,7 +168,7 @@ def test_tile_forward_masks_bit_identical_and_counts_match_the_oracle(mode, seed
     if not needles:
         assert int(pix_flag.sum()) < W * H // 50
     a = _forward_outputs(sc, mode, "4", monkeypatch)
-    b = _forward_outputs(sc, mode, "1", monkeypatch)
+    b = _forward_outputs(sc, mode, "-1", monkeypatch)
     for k in a:
         assert torch.equal(a[k], b[k]), k
     bad = a["n_contrib"].reshape(H, W) != o32["n_contrib"]

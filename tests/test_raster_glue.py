@@ -20,13 +20,13 @@ HERE = Path(__file__).resolve().parent
 # knobs that force the kernels: class-2 pair (wave-per-tile forward, 4-pixels-per-lane backward), class-1 pair (wave per
 # quadrant, scan backward), the scan backward with every tile split over four waves, and the defaults
 SETTINGS = {
-    "class2": {"PINGS_BLEND_PPL": "4", "PINGS_BLEND_BWD": "pixel", "PINGS_BLEND_BWD_PPL": "4"},
+    "class2": {"PINGS_BLEND_PPL": "4", "PINGS_BLEND_BWD": "pixel"},
     "class1": {"PINGS_BLEND_PPL": "-1", "PINGS_BLEND_BWD": "scan"},
     "class1_long": {"PINGS_BLEND_PPL": "-1", "PINGS_BLEND_BWD": "scan", "PINGS_BWD_LONG": "16"},
     "default": {},
 }
-KNOBS = ("PINGS_BLEND_PPL", "PINGS_BLEND_BWD", "PINGS_BLEND_BWD_PPL", "PINGS_BWD_LONG", "PINGS_DEPTH_SORT",
-         "PINGS_RASTER_OCCLUSION", "PINGS_BLEND_SEG")
+KNOBS = ("PINGS_BLEND_PPL", "PINGS_BLEND_BWD", "PINGS_BWD_LONG", "PINGS_DEPTH_SORT", "PINGS_RASTER_OCCLUSION",
+         "PINGS_BLEND_SEG")
 
 
 def _child(spec, env, tmp_path, tag):

@@ -65,7 +65,7 @@ def long_paths(fs, rg, nc):
     ppl = _env_int("PINGS_BLEND_PPL", 0)
     bwd = os.environ.get("PINGS_BLEND_BWD")
     scan = fs.fclass != 2 if bwd is None else bwd != "pixel"
-    wave_fwd = ppl not in (1, 2, 4) and not (ppl == 0 and fs.fclass == 2 and not scan)
+    wave_fwd = ppl != 4 and not (ppl == 0 and fs.fclass == 2 and not scan)
     seg = _env_int("PINGS_BLEND_SEG", SEG_ENTRIES) & 0xFFFFFFFF
     seg_on = wave_fwd and seg > 0 and I > num_tiles * (seg // SEG_FRAME_DIV) and I > 2 * seg
     seg_mask = lens > SEG_TILE_UNITS * seg if seg_on else torch.zeros_like(lens, dtype=torch.bool)

@@ -18,8 +18,8 @@ import pytest
 import torch
 
 HERE = Path(__file__).resolve().parent
-KNOBS = ("PINGS_RASTER_SCAN", "PINGS_BLEND_PPL", "PINGS_BLEND_BWD", "PINGS_BLEND_BWD_PPL", "PINGS_BWD_LONG",
-         "PINGS_DEPTH_SORT", "PINGS_TILE_SORT", "PINGS_RASTER_OCCLUSION", "PINGS_BLEND_SEG")
+KNOBS = ("PINGS_RASTER_SCAN", "PINGS_BLEND_PPL", "PINGS_BLEND_BWD", "PINGS_BWD_LONG", "PINGS_DEPTH_SORT",
+         "PINGS_TILE_SORT", "PINGS_RASTER_OCCLUSION", "PINGS_BLEND_SEG")
 
 BLOCK = 4096                    # SCAN_BLOCK of csrc/raster_common.hpp: elements per workgroup, 4 per thread
 LONG_TILES_MAX, TOP_BIN = 2048, 1023   # raster_bwd.hip, tile_order_body
@@ -228,7 +228,7 @@ def _worker_scenes(spec):
     from scenes import make_scene
     from test_raster_glue import _binning_field
 
-    class2 = {"PINGS_BLEND_PPL": "4", "PINGS_BLEND_BWD": "pixel", "PINGS_BLEND_BWD_PPL": "4"}
+    class2 = {"PINGS_BLEND_PPL": "4", "PINGS_BLEND_BWD": "pixel"}
     class1 = {"PINGS_BLEND_PPL": "-1", "PINGS_BLEND_BWD": "scan"}
     one = make_scene(1, 96, 64, seed=3, surfel=True, behind_frac=0.0)
     V = one["cam"]["viewmatrix"].to(one["means"].dtype)

@@ -9,7 +9,7 @@ for f in ("gpurun_out/pmcb/a/a_counter_collection.csv","gpurun_out/pmcb/b/b_coun
     agg=collections.defaultdict(lambda: collections.defaultdict(float)); n=collections.Counter()
     for r in csv.DictReader(open(f)):
         k=r["Kernel_Name"]
-        if "blend_bwd_kernel" in k or "blend_fwd_wave" in k or "occl_budget" in k:
+        if "blend_bwd_tile_kernel" in k or "blend_fwd_wave" in k or "occl_budget" in k:
             key=k.split("(")[0][-40:]
             agg[key][r["Counter_Name"]]+=float(r["Counter_Value"])
     for k,v in agg.items():

@@ -2,7 +2,7 @@
 `roofline.valu.flops_per_valu_inst`):
   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt -Iinclude -Ipings_amd/csrc \
         -DPINGS_BUILDING_DLL --save-temps -c pings_amd/csrc/raster_bwd.hip -o /tmp/rb.o
-  python tools/valu_mix.py raster_bwd-hip-amdgcn-amd-amdhsa-gfx950.s blend_bwd_kernelILi0ELi4E
+  python tools/valu_mix.py raster_bwd-hip-amdgcn-amd-amdhsa-gfx950.s blend_bwd_tile_kernelILi0E
 The loop is the innermost one that holds the kernel's v_exp_f32; an fma counts two operations, a packed instruction two lanes."""
 import re
 import sys
