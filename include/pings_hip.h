@@ -1243,6 +1243,75 @@ PINGS_API int pings_pool_window(const float* points, int64_t n, const float* ori
                                 int32_t range_filter_2d, const void* scratch, int64_t* rows, int64_t capacity,
                                 void* stream);
 
+/* ------------------------------------------------------------- the pool part of `Mapper.process_frame`
+ * What utils/mapper.py:270-284 and :340-426 do once per mapped frame, on the caller's own buffers (no state is kept
+ * here).  Plain stores, no float atomics, no LDS: every result is bitwise reproducible.  A pose is a DEVICE [4,4]
+ * row-major matrix, fp32 or fp64 (rounded to fp32 first, as `transformation.to(points)` does); a transformed row is
+ * ((R_i0 x + R_i1 y) + R_i2 z) + t_i, the order of pings_pool_transform.
+ *
+ * pings_pool_append: rows [n, n + m) of every pool tensor in one launch (:340-366): global_coord = R coord + t,
+ *   time = frame_id, sdf_label / weight / sem / color / normal copied.  sem, color and normal are nullable together
+ *   with their pools; `capacity` is the number of rows every pool buffer holds (n + m <= capacity is checked).
+ * pings_pool_discard_mark: keep[r[j]] = 0 for j < discard_count (:395-399; `keep` is n bytes the caller has set to 1,
+ *   `r` the int64 draw, duplicates expected).  An r[j] outside [0, n) is not dereferenced and sets bit 0 of the device
+ *   word `status` (nullable; the caller zeroes it).
+ * pings_pool_compact_count / pings_pool_compact: the boolean-mask indexing of :404-423 for every pool tensor, stable,
+ *   OUT OF PLACE.  A wave owns 2048 consecutive rows; _count writes the per-wave numbers of kept rows to `scratch`
+ *   (pings_pool_compact_scratch_bytes(n): 16 B per 2048 rows), one wave scans them, and counts2 (HOST, two int64; one
+ *   polled read-back) receives the number of kept rows and the number of kept rows among the last `tail`.
+ *   pings_pool_compact then moves the rows: dst_g[rank] = src_g[row] for every job g in one launch (blockIdx.y = g,
+ *   any row width); jobs[g].rows is the number of rows dst_g holds, never written past.  src and dst must not overlap.
+ * pings_pool_select_count / pings_pool_select_update: the update points of :262-284.  Selected: the rows with
+ *   |sdf_label| < fp32(thr), or every row with `select_all` (then no count is needed: rank = row).  _count fills
+ *   `scratch` (pings_pool_select_scratch_bytes(n)) and returns their number in *count (HOST; one polled read-back).
+ *   pings_pool_select_update writes, in ascending row order and never past `capacity` rows: out_points = R coord + t,
+ *   out_color = the colour row, out_normal = R normal (no translation); color / normal are nullable with their
+ *   outputs. */
+typedef struct pings_pool_append_args {
+  int64_t n, m, capacity;
+  int32_t frame_id, color_channels, pose_is_f64, reserved;
+  const void* pose;            /* DEVICE [4,4] */
+  const float* coord;          /* [m,3], sensor frame */
+  const float* sdf_label;      /* [m] */
+  const float* weight;         /* [m] */
+  const int32_t* sem;          /* [m] or NULL */
+  const float* color;          /* [m,color_channels] or NULL */
+  const float* normal;         /* [m,3] or NULL */
+  float* global_coord_pool;    /* [capacity,3] */
+  float* sdf_label_pool;       /* [capacity] */
+  float* weight_pool;          /* [capacity] */
+  int32_t* time_pool;          /* [capacity] */
+  int32_t* sem_label_pool;     /* [capacity] or NULL */
+  float* color_pool;           /* [capacity,color_channels] or NULL */
+  float* normal_label_pool;    /* [capacity,3] or NULL */
+} pings_pool_append_args;
+typedef struct pings_pool_select_args {
+  int64_t n, capacity;
+  int32_t color_channels, pose_is_f64, select_all, reserved;
+  double thr;
+  const void* pose;            /* DEVICE [4,4] */
+  const float* coord;          /* [n,3] */
+  const float* sdf_label;      /* [n]; NULL with select_all */
+  const float* color;          /* [n,color_channels] or NULL */
+  const float* normal;         /* [n,3] or NULL */
+  const void* scratch;         /* filled by pings_pool_select_count; NULL with select_all */
+  float* out_points;           /* [capacity,3] */
+  float* out_color;            /* [capacity,color_channels] or NULL */
+  float* out_normal;           /* [capacity,3] or NULL */
+} pings_pool_select_args;
+PINGS_API int pings_pool_append(const pings_pool_append_args* args, void* stream);
+PINGS_API int pings_pool_discard_mark(const int64_t* r, int64_t discard_count, int64_t n, uint8_t* keep,
+                                      int32_t* status, void* stream);
+PINGS_API size_t pings_pool_compact_scratch_bytes(int64_t n);
+PINGS_API int pings_pool_compact_count(const uint8_t* keep, int64_t n, int64_t tail, void* scratch, int64_t* counts2,
+                                       void* stream);
+PINGS_API int pings_pool_compact(const pings_gather_job* jobs, int njobs, const uint8_t* keep, int64_t n,
+                                 const void* scratch, void* stream);
+PINGS_API size_t pings_pool_select_scratch_bytes(int64_t n);
+PINGS_API int pings_pool_select_count(const float* sdf_label, int64_t n, double thr, void* scratch, int64_t* count,
+                                      void* stream);
+PINGS_API int pings_pool_select_update(const pings_pool_select_args* args, void* stream);
+
 /* ------------------------------------------------------------- frame-time point tests
  * Three per-frame query steps of the reference's `Mapper`, on the caller's own tensors (no state is kept here).  Every
  * threshold is the double the reference forms between python scalars; it is rounded to fp32 once, as torch does with a

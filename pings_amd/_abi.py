@@ -153,6 +153,22 @@ class PoolSampleArgs(C.Structure):
                                   "coord", "sdf_label", "weight", "out_normal", "out_sem", "out_color")]
 
 
+class PoolAppendArgs(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n", "m", "capacity")] + \
+               [(n, C.c_int32) for n in ("frame_id", "color_channels", "pose_is_f64", "reserved")] + \
+               [(n, vp) for n in ("pose", "coord", "sdf_label", "weight", "sem", "color", "normal", "global_coord_pool",
+                                  "sdf_label_pool", "weight_pool", "time_pool", "sem_label_pool", "color_pool",
+                                  "normal_label_pool")]
+
+
+class PoolSelectArgs(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n", "capacity")] + \
+               [(n, C.c_int32) for n in ("color_channels", "pose_is_f64", "select_all", "reserved")] + \
+               [("thr", C.c_double)] + \
+               [(n, vp) for n in ("pose", "coord", "sdf_label", "color", "normal", "scratch", "out_points", "out_color",
+                                  "out_normal")]
+
+
 # ---------------------------------------------------------------- entry points: {name: (restype, argtypes)}
 SIGNATURES = {
     # general
@@ -341,6 +357,15 @@ SIGNATURES = {
     "pings_pool_window_scratch_bytes": (sz, [i64]),
     "pings_pool_window_count": (i32, [vp, i64, vp, f32, i32, vp, C.POINTER(i64), vp]),
     "pings_pool_window": (i32, [vp, i64, vp, f32, i32, vp, vp, i64, vp]),
+    # the pool part of Mapper.process_frame
+    "pings_pool_append": (i32, [C.POINTER(PoolAppendArgs), vp]),
+    "pings_pool_discard_mark": (i32, [vp, i64, i64, vp, vp, vp]),
+    "pings_pool_compact_scratch_bytes": (sz, [i64]),
+    "pings_pool_compact_count": (i32, [vp, i64, i64, vp, C.POINTER(i64), vp]),
+    "pings_pool_compact": (i32, [C.POINTER(GatherJob), i32, vp, i64, vp, vp]),
+    "pings_pool_select_scratch_bytes": (sz, [i64]),
+    "pings_pool_select_count": (i32, [vp, i64, f64, vp, C.POINTER(i64), vp]),
+    "pings_pool_select_update": (i32, [C.POINTER(PoolSelectArgs), vp]),
     # frame-time point tests
     "pings_frame_new_scratch_bytes": (sz, [i64]),
     "pings_frame_new_count": (i32, [C.POINTER(KnnMap), vp, i64, vp, vp, i64, f64, f64, f64, vp, C.POINTER(i64), vp]),
