@@ -4,28 +4,44 @@
 // (gaussian_splatting/utils/loss_utils.py:189-219; window loss_utils.py:53-55,
 // 182-186): depth-wise 11x11 Gaussian (sigma 1.5, normalised) convolution with
 // zero padding 5, C1 = 0.01^2, C2 = 0.03^2, mean over every element.  The 2-D
-// window is an outer product, so both passes here are separable 11-tap
-// convolutions staged through LDS.
+// window is an outer product, so both directions are separable 11-tap passes.
 //
-// Layout: images are [planes, H, W] fp32.  One 256-thread workgroup produces a
-// 32x32 output tile of one plane: the 42x42 halo tile of both images is staged
-// in LDS (coalesced row loads), the horizontal pass leaves five running
-// statistics per (row, col) in LDS, the vertical pass finishes them per pixel.
-// HBM traffic per pixel: fwd 8 B read (+12 B written when train), bwd 20 B read
-// + 4 B written; the kernel is HBM/L2-stream bound, the 1.72x halo re-read is
-// served by L2.
+// Layout: images are [planes, H, W] fp32.  The kernels that run (ssim_fwd_vf_kernel, ssim_bwd_vf_kernel) use no LDS
+// image and no barrier: a WAVE is the unit of work.  It owns a strip of SW_OUT = 54 output columns — its 64 lanes hold
+// the input columns x0 - 5 .. x0 + 58 — and walks a band of RB rows (ssim_plan below), one input row per step:
+//   loads       one 256-byte row segment per map and input row, issued four rows ahead into a register ring;
+//   vertical    FIRST: the input row's values (forward: the raw moments a, b, a^2, b^2, ab, formed once per input
+//               pixel; backward: the three derivative maps) are added at once into the eleven output rows they belong
+//               to — eleven accumulator sets in registers, slots static through an 11-fold unroll, pairs of them in
+//               packed fp32 (v_pk_fma_f32: two IEEE operations, the scalar forms' roundings);
+//   horizontal  only a finished OUTPUT row of the band takes it (39 of the 49 steps of a 39-row band), across the lanes
+//               in transposed form: acc <- wave_shr:1(acc) + w_k v, the shift a DPP operand of the add.  The result for
+//               column x lands five lanes to the right, so lanes 10..63 hold the strip's 54 outputs.
+// A unit is (plane, band, strip); the forward leaves one partial sum per unit and ssim_reduce_kernel adds them in a
+// fixed order in fp64.  HBM traffic per pixel: fwd 8 B read (+12 B written when train), bwd 20 B read + 4 B written;
+// neighbouring units re-read 10 columns / 10 rows of each other, which the unit numbering and the walk order keep in
+// one L2 (PMC: 1.06x the algorithmic bytes).  What bounds the kernels is vector issue, not memory.
+//
+// Lineage (figures and profiles: DESIGN §2.2).  The first generation worked on 32x32 output tiles with the 42x42 halo
+// tiles in LDS: 1.02x the algorithmic bytes, but most of its 0.074 / 0.050 ms (1080p x 3, forward / backward) went
+// into the phase structure stage -> barrier -> horizontal -> barrier -> vertical, three workgroups per CU by 42 KB of LDS
+// each.  Its forward is no longer in the tree; its backward, ssim_bwd_kernel, still is (PINGS_SSIM_BWD=tile).  The
+// first sliding-window kernels, ssim_fwd_sw_kernel / ssim_bwd_sw_kernel (PINGS_SSIM_FWD=sw / PINGS_SSIM_BWD=sw), have
+// the walk above with the horizontal pass first, on every INPUT row: 0.062 / 0.046 ms.  Vertical first, the backward
+// takes 0.038 ms and the forward is unchanged within noise.  Neither older path is selected by the product.
 #include <cstdlib>
 
 #include "common.hpp"
 
 namespace {
 
-constexpr int TS = 32;            // output tile edge
 constexpr int HALO = 5;           // window radius
+constexpr int NT = 256;
+// the tile backward (ssim_bwd_kernel) only:
+constexpr int TS = 32;            // output tile edge
 constexpr int IN = TS + 2 * HALO; // 42
 constexpr int INP = IN + 1;       // padded LDS row
-constexpr int NT = 256;
-constexpr int PERSISTENT_WGS = 256 * 3;   // three workgroups per CU fit by LDS (42 KB each)
+constexpr int PERSISTENT_WGS = 256 * 3;   // persistent workgroups: three per CU
 
 // Which tiles a persistent workgroup walks.  Workgroups b and b + 8 share an XCD and with it an L2 (observed dispatch,
 // MI355X_MICROARCH.md: a speed matter only); tiles are numbered row-major.  Giving every XCD label a contiguous band
@@ -55,167 +71,16 @@ __device__ inline float wave_sum(float v) {
   return v;
 }
 
-template <bool TRAIN>
-__global__ __launch_bounds__(NT, 3) void ssim_fwd_kernel(
-    const float* __restrict__ img1, const float* __restrict__ img2, int planes, int H, int W,
-    float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq,
-    float* __restrict__ dm_dsigma12, float* __restrict__ partials) {
-  __shared__ float sA[IN][INP];
-  __shared__ float sB[IN][INP];
-  __shared__ float sH[5][IN][TS + 1];
-  __shared__ float sRed[NT / 64];
-
-  const int tid = threadIdx.x;
-  constexpr int PF = (IN * IN + NT - 1) / NT;   // halo-tile elements per thread
-  const int GX = (W + TS - 1) / TS, GY = (H + TS - 1) / TS;
-  const long long ntiles = (long long)GX * GY * planes;
-  // Persistent workgroups over the tiles with a register prefetch: the next tile's halo tile is in flight while the
-  // current one is convolved (first version: one tile per workgroup, three workgroups per CU by LDS, every tile's
-  // global loads exposed: 0.092 ms forward at 1080p x 3 against a 0.04 ms traffic floor).
-  float ra[PF], rb[PF];
-  auto fetch = [&](long long t) {
-    const int bx = (int)(t % GX), by = (int)((t / GX) % GY);
-    const size_t off = (size_t)(t / ((long long)GX * GY)) * H * W;
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      const int i = tid + u * NT;
-      const int r = i / IN, c = i - r * IN;
-      const int gy = by * TS + r - HALO, gx = bx * TS + c - HALO;
-      const bool in = i < IN * IN && gy >= 0 && gy < H && gx >= 0 && gx < W;
-      ra[u] = in ? img1[off + (size_t)gy * W + gx] : 0.f;
-      rb[u] = in ? img2[off + (size_t)gy * W + gx] : 0.f;
-    }
-  };
-  const TileWalk tw = tile_walk(ntiles);
-  if (tw.first < tw.end) fetch(tw.first);
-  for (long long t = tw.first; t < tw.end; t += tw.step) {
-    const int x0 = (int)(t % GX) * TS, y0 = (int)((t / GX) % GY) * TS;
-    const size_t plane_off = (size_t)(t / ((long long)GX * GY)) * H * W;
-#pragma unroll
-    for (int u = 0; u < PF; ++u) {
-      const int i = tid + u * NT;
-      if (i < IN * IN) {
-        const int r = i / IN, c = i - r * IN;
-        sA[r][c] = ra[u];
-        sB[r][c] = rb[u];
-      }
-    }
-    __syncthreads();
-    if (t + tw.step < tw.end) fetch(t + tw.step);
-
-    // horizontal pass: 42 rows x 32 cols, five statistics each.  A thread owns FOUR adjacent output columns of a row:
-    // the 14 inputs they share are read from LDS once (7 reads per output and image instead of 22; the pass was
-    // LDS-read bound: 84 ds_read_b32 per pixel over both passes).  Every output still accumulates its 11 taps in
-    // the order k = 0..10 with the same operations, so the statistics are bit-identical to the one-output form.
-    for (int i = tid; i < IN * (TS / 4); i += NT) {
-      const int r = i / (TS / 4), c0 = 4 * (i - r * (TS / 4));
-      float m1[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f}, s11[4] = {0.f, 0.f, 0.f, 0.f},
-            s22[4] = {0.f, 0.f, 0.f, 0.f}, s12[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int j = 0; j < 14; ++j) {
-        const float a = sA[r][c0 + j], b = sB[r][c0 + j];
-#pragma unroll
-        for (int o = 0; o < 4; ++o) {
-          const int k = j - o;
-          if (k >= 0 && k < 11) {
-            const float w = kWin[k];
-            const float wa = w * a, wb = w * b;
-            m1[o] += wa;
-            m2[o] += wb;
-            s11[o] = fmaf(wa, a, s11[o]);
-            s22[o] = fmaf(wb, b, s22[o]);
-            s12[o] = fmaf(wa, b, s12[o]);
-          }
-        }
-      }
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        sH[0][r][c0 + o] = m1[o];
-        sH[1][r][c0 + o] = m2[o];
-        sH[2][r][c0 + o] = s11[o];
-        sH[3][r][c0 + o] = s22[o];
-        sH[4][r][c0 + o] = s12[o];
-      }
-    }
-    __syncthreads();
-
-    // vertical pass: a thread owns FOUR adjacent rows of one column (32 columns x 8 row groups = the 256 threads): 14
-    // rows of the five statistics are read once for four outputs (17.5 LDS reads per output instead of 55), taps
-    // again accumulated in the order k = 0..10
-    float local = 0.f;
-    float vmu1[4] = {0.f, 0.f, 0.f, 0.f}, vmu2[4] = {0.f, 0.f, 0.f, 0.f}, ve11[4] = {0.f, 0.f, 0.f, 0.f},
-          ve22[4] = {0.f, 0.f, 0.f, 0.f}, ve12[4] = {0.f, 0.f, 0.f, 0.f};
-    const int vc = tid & (TS - 1), vr0 = 4 * (tid / TS);
-#pragma unroll
-    for (int j = 0; j < 14; ++j) {
-      const float h0 = sH[0][vr0 + j][vc], h1 = sH[1][vr0 + j][vc], h2 = sH[2][vr0 + j][vc],
-                  h3 = sH[3][vr0 + j][vc], h4 = sH[4][vr0 + j][vc];
-#pragma unroll
-      for (int o = 0; o < 4; ++o) {
-        const int k = j - o;
-        if (k >= 0 && k < 11) {
-          const float w = kWin[k];
-          vmu1[o] = fmaf(w, h0, vmu1[o]);
-          vmu2[o] = fmaf(w, h1, vmu2[o]);
-          ve11[o] = fmaf(w, h2, ve11[o]);
-          ve22[o] = fmaf(w, h3, ve22[o]);
-          ve12[o] = fmaf(w, h4, ve12[o]);
-        }
-      }
-    }
-#pragma unroll
-    for (int o = 0; o < 4; ++o) {
-      const int r = vr0 + o, c = vc;
-      const int gy = y0 + r, gx = x0 + c;
-      if (gy >= H || gx >= W) continue;
-      const float mu1 = vmu1[o], mu2 = vmu2[o], e11 = ve11[o], e22 = ve22[o], e12 = ve12[o];
-      const float mu1_sq = mu1 * mu1, mu2_sq = mu2 * mu2, mu12 = mu1 * mu2;
-      const float sig1 = e11 - mu1_sq, sig2 = e22 - mu2_sq, sig12 = e12 - mu12;
-      const float A1 = 2.f * mu12 + kC1;
-      const float A2 = 2.f * sig12 + kC2;
-      const float B1 = mu1_sq + mu2_sq + kC1;
-      const float B2 = sig1 + sig2 + kC2;
-      const float inv_B1 = __builtin_amdgcn_rcpf(B1), inv_B2 = __builtin_amdgcn_rcpf(B2);   // as ssim_fwd_sw_kernel
-      const float m = (A1 * A2) * (inv_B1 * inv_B2);
-      local += m;
-      if (TRAIN) {
-        // partials of the map w.r.t. (mu1, E[x^2], E[xy]) at this pixel; the
-        // chain through sigma1^2 = E[x^2]-mu1^2 and sigma12 = E[xy]-mu1*mu2 is
-        // folded into d/dmu1.
-        const float d_s1 = -m * inv_B2;               // dm/dsigma1_sq
-        const float d_s12 = 2.f * A1 * inv_B1 * inv_B2;  // dm/dsigma12
-        const float d_mu1 = 2.f * mu2 * A2 * inv_B1 * inv_B2 - 2.f * mu1 * m * inv_B1 -
-                            2.f * mu1 * d_s1 - mu2 * d_s12;
-        const size_t o = plane_off + (size_t)gy * W + gx;
-        dm_dmu1[o] = d_mu1;
-        dm_dsigma1_sq[o] = d_s1;
-        dm_dsigma12[o] = d_s12;
-      }
-    }
-    local = wave_sum(local);
-    if ((tid & 63) == 0) sRed[tid >> 6] = local;
-    __syncthreads();
-    if (tid == 0) {
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < NT / 64; ++i) s += sRed[i];
-      partials[t] = s;
-    }
-    __syncthreads();   // sA / sB / sH / sRed are rewritten by the next tile
-    }
-  }
-
-// ---------------------------------------------------------------- forward, sliding window (round 4)
-// The tile kernel above spends most of its 72 us in its phase structure (stage -> barrier -> horizontal -> barrier ->
-// vertical, three workgroups per CU by the 42 KB of LDS each), not in memory: PMC traffic is 1.02x the algorithmic
-// bytes.  Here there is no LDS image and no barrier.  A WAVE owns a strip of SW_OUT = 54 output columns (lanes 5..58;
-// all 64 lanes hold input columns x0 - 5 .. x0 + 58) and walks a band of rows top to bottom:
+// ---------------------------------------------------------------- forward, sliding window, horizontal pass first
+// (PINGS_SSIM_FWD=sw; A/B runs only.)  The tile forward this replaced spent most of its 72 us in its phase structure,
+// not in memory (see the lineage above).  Here there is no LDS image and no barrier.  A WAVE owns a strip of
+// SW_OUT = 54 output columns (lanes 5..58; all 64 lanes hold input columns x0 - 5 .. x0 + 58) and walks a band of rows:
 //   horizontal  the 11 taps of a row come from the neighbouring lanes through full-wave DPP shifts of the two input
-//               values (ten shifts per image), every output accumulates its taps in the order k = 0..10 with the tile
-//               kernel's operations;
+//               values (ten shifts per image), every output accumulates its taps in the order k = 0..10;
 //   vertical    an input row's five statistics are added at once into the eleven output rows it belongs to (eleven
 //               accumulator sets in registers, slots static through an 11-fold unroll); output row r receives its taps
-//               in the order k = 0..10 as well, so every statistic is bit-identical to the tile kernel's;
+//               in the order k = 0..10 as well: the order of the first-generation tile forward, whose statistics these
+//               reproduced bit for bit;
 //   loads       one 256-byte row segment per image and input row, issued four rows ahead into a register ring.
 // Per input row and lane: 2 loads, 20 DPP moves, ~130 vector operations.
 constexpr int SW_OUT = 64 - 2 * HALO;   // output columns per wave
@@ -232,9 +97,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_sw_kernel(
     int bands, int alt, float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12,
     float* __restrict__ partials) {
   const int lane = threadIdx.x & 63;
-  // units = (plane, band, strip), strips fastest; the four waves of a workgroup take four neighbouring strips of one
-  // band, and every XCD label (blockIdx & 7) a contiguous range of workgroups, so that the 10-column / 10-row overlaps
-  // of neighbouring units meet in one L2 (see tile_walk above)
+  // the unit numbering of ssim_fwd_vf_kernel (explained there)
   const long long units = (long long)planes * bands * strips;
   const long long nblk = gridDim.x;
   long long blk = blockIdx.x;
@@ -341,9 +204,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_sw_kernel(
           const float A2 = 2.f * sig12 + kC2;
           const float B1 = mu1_sq + mu2_sq + kC1;
           const float B2 = sig1 + sig2 + kC2;
-          // 1-ulp reciprocals (v_rcp_f32) instead of two IEEE divisions (ten instructions each under
-          // -fhip-fp32-correctly-rounded-divide-sqrt): B1, B2 >= C1, C2 > 0; 1.2e-7 relative, the tolerance is 1e-4
-          const float inv_B1 = __builtin_amdgcn_rcpf(B1), inv_B2 = __builtin_amdgcn_rcpf(B2);
+          const float inv_B1 = __builtin_amdgcn_rcpf(B1), inv_B2 = __builtin_amdgcn_rcpf(B2);   // as ssim_fwd_vf_kernel
           const float m = (A1 * A2) * (inv_B1 * inv_B2);
           local += m;
           if (TRAIN) {
@@ -370,16 +231,21 @@ __global__ __launch_bounds__(256) void ssim_fwd_sw_kernel(
 // ab: formed once per input pixel) are added into the pending rows first, and a finished OUTPUT row takes the horizontal
 // pass — 39 rows of a 49-step band instead of 49, on five values instead of on two images x three products per tap.
 // Same strips, bands, prefetch ring and alternating band direction; the sums associate differently (fp32: ~1e-7
-// relative against the tile kernel, nothing is bit-identical to it any more).
+// relative against ssim_fwd_sw_kernel).
 template <bool TRAIN>
 __global__ __launch_bounds__(256) void ssim_fwd_vf_kernel(
     const float* __restrict__ img1, const float* __restrict__ img2, int planes, int H, int W, int RB, int strips,
     int bands, int alt, float* __restrict__ dm_dmu1, float* __restrict__ dm_dsigma1_sq, float* __restrict__ dm_dsigma12,
     float* __restrict__ partials) {
   const int lane = threadIdx.x & 63;
-  // units = (plane, band, strip), strips fastest; the four waves of a workgroup take four neighbouring strips of one
-  // band, and every XCD label (blockIdx & 7) a contiguous range of workgroups, so that the 10-column / 10-row overlaps
-  // of neighbouring units meet in one L2 (see tile_walk above)
+  // Unit numbering.  A unit is (plane, band, strip) with strips fastest, and the four waves of a workgroup take four
+  // consecutive units: four neighbouring strips of one band, which share ten input columns pairwise.  Workgroups b and
+  // b + 8 share an XCD and with it an L2 (observed dispatch order; a speed matter only, any order is correct).  So the
+  // launch rounds the grid up to a multiple of eight (the surplus workgroups return at once) and XCD label blockIdx & 7
+  // takes the contiguous range [label * nblk / 8, (label + 1) * nblk / 8) of the numbering: the 10-column / 10-row
+  // overlaps of neighbouring units then meet in ONE L2.  Dealt round-robin, every neighbour sits behind another L2 and
+  // the overlap comes from HBM again (measured on tiles: 96.5 MB fetched for 49.8 MB of images, 26.8 MB once
+  // contiguous).
   const long long units = (long long)planes * bands * strips;
   const long long nblk = gridDim.x;
   long long blk = blockIdx.x;
@@ -485,7 +351,9 @@ __global__ __launch_bounds__(256) void ssim_fwd_vf_kernel(
             const float A2 = 2.f * sig12 + kC2;
             const float B1 = mu1_sq + mu2_sq + kC1;
             const float B2 = sig1 + sig2 + kC2;
-            const float inv_B1 = __builtin_amdgcn_rcpf(B1), inv_B2 = __builtin_amdgcn_rcpf(B2);   // as ssim_fwd_sw_kernel
+            // 1-ulp reciprocals (v_rcp_f32) instead of two IEEE divisions (ten instructions each under
+            // -fhip-fp32-correctly-rounded-divide-sqrt): B1, B2 >= C1, C2 > 0; 1.2e-7 relative, the tolerance is 1e-4
+            const float inv_B1 = __builtin_amdgcn_rcpf(B1), inv_B2 = __builtin_amdgcn_rcpf(B2);
             const float m = (A1 * A2) * (inv_B1 * inv_B2);
             local += m;
             if (TRAIN) {
@@ -534,7 +402,7 @@ __global__ __launch_bounds__(256) void ssim_fwd_vf_kernel(
     constexpr int PF = (IN * IN + NT - 1) / NT;
     const int GX = (W + TS - 1) / TS, GY = (H + TS - 1) / TS;
     const long long ntiles = (long long)GX * GY * planes;
-    float r0[PF], r1[PF], r2[PF];   // the next tile's three derivative maps, prefetched (see ssim_fwd_kernel)
+    float r0[PF], r1[PF], r2[PF];   // the next tile's three derivative maps, in flight while this tile is convolved
     auto fetch = [&](long long t) {
       const int bx = (int)(t % GX), by = (int)((t / GX) % GY);
       const size_t off = (size_t)(t / ((long long)GX * GY)) * H * W;
@@ -567,8 +435,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_vf_kernel(
     }
     __syncthreads();
     if (t + tw.step < tw.end) fetch(t + tw.step);
-    // four adjacent outputs per thread in both passes (see ssim_fwd_kernel): same taps in the same order, 3.1x fewer
-    // LDS reads
+    // four adjacent outputs per thread in both passes: the 14 inputs they share are read from LDS once (3.1x fewer
+    // LDS reads), and every output still adds its 11 taps in the order k = 0..10 with the same operations
     for (int i = tid; i < IN * (TS / 4); i += NT) {
       const int r = i / (TS / 4), c0 = 4 * (i - r * (TS / 4));
       float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f}, d[4] = {0.f, 0.f, 0.f, 0.f};
@@ -627,8 +495,8 @@ __global__ __launch_bounds__(256) void ssim_fwd_vf_kernel(
 
 // ---------------------------------------------------------------- backward, sliding window (round 4)
 // The same walk as ssim_fwd_sw_kernel for the adjoint: the three derivative maps are filtered with the window in both
-// directions (taps in the order k = 0..10, fused multiply-adds as in the tile kernel: bit-identical), the output row
-// r = y - 5 is finished with the two images at (r, x):  dL/dimg1 = g (A + 2 img1 B + img2 D).
+// directions (taps in the order k = 0..10, fused multiply-adds as in ssim_bwd_kernel: bit-identical to it with every
+// band top-down), the output row r = y - 5 is finished with the two images at (r, x):  dL/dimg1 = g (A + 2 img1 B + img2 D).
 __global__ __launch_bounds__(256) void ssim_bwd_sw_kernel(
     const float* __restrict__ img1, const float* __restrict__ img2, int planes, int H, int W, int RB, int strips,
     int bands, int alt, const float* __restrict__ dL_dmean, float inv_count, const float* __restrict__ dm_dmu1,
@@ -756,7 +624,7 @@ __global__ __launch_bounds__(256) void ssim_bwd_vf_kernel(
   const int xo = x - HALO;                                  // the horizontal pass leaves column x - 5 on this lane
   const bool x_out = lane >= 2 * HALO && xo < W;
   const int yb = band * RB, ye = min(H, yb + RB);
-  const bool up = alt && (band & 1);                       // odd bands bottom-up, see ssim_fwd_sw_kernel
+  const bool up = alt && (band & 1);                       // odd bands bottom-up, see ssim_fwd_vf_kernel
   const int y_first = up ? ye + HALO - 1 : yb - HALO, y_step = up ? -1 : 1;
   const int r_first = up ? ye + 2 * HALO - 1 : yb - 2 * HALO;
   const size_t col = plane_off + (x_in ? x : 0);
@@ -838,127 +706,100 @@ __global__ __launch_bounds__(256) void ssim_bwd_vf_kernel(
   }
 }
 
-  }  // namespace
+// ---------------------------------------------------------------- the launch plan of the sliding-window kernels
+// One geometry for the forward, the backward and the size of the partials buffer.  Both variables are read on every
+// call.
+struct SsimPlan {
+  int rb, strips, bands, alt;   // rows per band, 54-column strips, bands per plane, odd bands bottom-up
+  size_t units;                 // planes * bands * strips: one wave and one partial sum each
+  unsigned nblk;                // workgroups of four units, a multiple of eight (the XCD-contiguous numbering)
+};
 
-  namespace {
-  // rows per band of the sliding-window forward: enough waves to fill the chip six deep, at least 16 rows per band
-  // (a band re-reads 10 halo rows).  PINGS_SSIM_RB overrides (A/B runs); PINGS_SSIM_FWD=tile keeps the tile kernel.
-  int sw_rows_per_band(int planes, int H, int W) {
-    if (const char* e = getenv("PINGS_SSIM_RB")) { const int v = atoi(e); if (v > 0) return v; }
-    // about three waves per SIMD in all (the kernels hold four): fewer, taller bands re-read fewer halo rows, more bands
-    // balance the chip better.  1080p x 3, forward / backward ms by band height: 20 rows 0.075 / 0.049, 24 0.069 / 0.046,
-    // 28 0.071 / 0.048, 32 0.066 / 0.044, 40 0.063 / 0.042, 64 0.065 / 0.043 (the round-3 tile kernels: 0.074 / 0.050)
-    const long long strips = pings::ceil_div(W, SW_OUT);
-    const long long want_bands = (256LL * 4 * 3) / (strips * planes);
+SsimPlan ssim_plan(int planes, int H, int W) {
+  SsimPlan p;
+  p.strips = pings::ceil_div(W, SW_OUT);
+  // Rows per band: about three waves per SIMD in all (the kernels hold four): fewer, taller bands re-read fewer of the
+  // ten halo rows, more bands balance the chip better; at least 16 rows unless the image is shorter.  1080p x 3, forward
+  // / backward ms by band height: 20 rows 0.075 / 0.049, 24 0.069 / 0.046, 28 0.071 / 0.048, 32 0.066 / 0.044,
+  // 40 0.063 / 0.042, 64 0.065 / 0.043.  PINGS_SSIM_RB > 0 overrides, unclamped (band-height sweeps, geometry tests).
+  const char* e = getenv("PINGS_SSIM_RB");
+  const int forced = e ? atoi(e) : 0;
+  if (forced > 0) {
+    p.rb = forced;
+  } else {
+    const long long want_bands = (256LL * 4 * 3) / ((long long)p.strips * planes);
     long long rb = pings::ceil_div<long long>(H, want_bands > 0 ? want_bands : 1);
     if (rb < 16) rb = 16;
     if (rb > H) rb = H;
-    return (int)rb;
+    p.rb = (int)rb;
   }
-  // odd bands bottom-up (halo rows meet in L2); PINGS_SSIM_ALT=0: every band top-down (bit-identical to the tile kernels)
-  int sw_alternate() {
-    if (const char* e = getenv("PINGS_SSIM_ALT")) return atoi(e) != 0;
-    return 1;
-  }
-  size_t sw_units(int planes, int H, int W) {
-    const int rb = sw_rows_per_band(planes, H, W);
-    return (size_t)planes * pings::ceil_div(H, rb) * pings::ceil_div(W, SW_OUT);
-  }
-  }  // namespace
+  p.bands = pings::ceil_div(H, p.rb);
+  p.units = (size_t)planes * p.bands * p.strips;
+  p.nblk = ((unsigned)pings::ceil_div<size_t>(p.units, 4) + 7u) & ~7u;
+  // PINGS_SSIM_ALT=0: every band top-down (the horizontal-first kernels are then bit-identical to the tile backward)
+  e = getenv("PINGS_SSIM_ALT");
+  p.alt = e ? atoi(e) != 0 : 1;
+  return p;
+}
 
-  PINGS_API size_t pings_ssim_partials_count(int planes, int H, int W) {
-    if (planes <= 0 || H <= 0 || W <= 0) return 0;
-    const size_t tiles = (size_t)planes * pings::ceil_div(H, TS) * pings::ceil_div(W, TS);
-    const size_t units = sw_units(planes, H, W);
-    return tiles > units ? tiles : units;      // either forward kernel fits
-  }
+}  // namespace
 
-  PINGS_API int pings_ssim_forward(const float* img1, const float* img2, int planes, int H, int W,
-                                   int train, float* out_mean, float* dm_dmu1,
-                                   float* dm_dsigma1_sq, float* dm_dsigma12, float* partials,
-                                   void* stream) {
-    PINGS_ARG_CHECK(img1 && img2 && out_mean && partials, "null pointer");
-    PINGS_ARG_CHECK(planes > 0 && H > 0 && W > 0, "empty image");
-    PINGS_ARG_CHECK(planes <= 65535, "too many planes");
-    PINGS_ARG_CHECK(!train || (dm_dmu1 && dm_dsigma1_sq && dm_dsigma12),
-                    "train=1 needs the three derivative maps");
-    hipStream_t st = pings::as_stream(stream);
-    const char* fwd_env = getenv("PINGS_SSIM_FWD");
-    if (!(fwd_env && fwd_env[0] == 't')) {      // default: the sliding-window kernel
-      const int rb = sw_rows_per_band(planes, H, W);
-      const int strips = pings::ceil_div(W, SW_OUT), bands = pings::ceil_div(H, rb);
-      const size_t units = (size_t)planes * bands * strips;
-      unsigned nblk = (unsigned)pings::ceil_div<size_t>(units, 4);
-      nblk = (nblk + 7u) & ~7u;                  // a multiple of eight: the XCD-contiguous numbering above
-      pings::prof::Scope ps("ssim_fwd", st);
-      const bool hfirst = fwd_env && fwd_env[0] == 's';   // PINGS_SSIM_FWD=sw: the horizontal-first kernel (A/B runs)
-#define PINGS_SSIM_FWD_LAUNCH(K_, T_, A_, B_, C_)                                                                   \
-  hipLaunchKernelGGL(K_<T_>, dim3(nblk), dim3(256), 0, st, img1, img2, planes, H, W, rb, strips, bands, sw_alternate(), \
-                     A_, B_, C_, partials)
-      if (train) {
-        if (hfirst) PINGS_SSIM_FWD_LAUNCH(ssim_fwd_sw_kernel, true, dm_dmu1, dm_dsigma1_sq, dm_dsigma12);
-        else PINGS_SSIM_FWD_LAUNCH(ssim_fwd_vf_kernel, true, dm_dmu1, dm_dsigma1_sq, dm_dsigma12);
-      } else {
-        if (hfirst) PINGS_SSIM_FWD_LAUNCH(ssim_fwd_sw_kernel, false, (float*)nullptr, (float*)nullptr, (float*)nullptr);
-        else PINGS_SSIM_FWD_LAUNCH(ssim_fwd_vf_kernel, false, (float*)nullptr, (float*)nullptr, (float*)nullptr);
-      }
-#undef PINGS_SSIM_FWD_LAUNCH
-      PINGS_LAUNCH_CHECK();
-      const double inv_count = 1.0 / ((double)planes * H * W);
-      hipLaunchKernelGGL(ssim_reduce_kernel, dim3(1), dim3(NT), 0, st, partials, units, inv_count, out_mean);
-      PINGS_LAUNCH_CHECK();
-      return PINGS_OK;
-    }
+PINGS_API size_t pings_ssim_partials_count(int planes, int H, int W) {
+  if (planes <= 0 || H <= 0 || W <= 0) return 0;
+  return ssim_plan(planes, H, W).units;
+}
+
+PINGS_API int pings_ssim_forward(const float* img1, const float* img2, int planes, int H, int W,
+                                 int train, float* out_mean, float* dm_dmu1,
+                                 float* dm_dsigma1_sq, float* dm_dsigma12, float* partials,
+                                 void* stream) {
+  PINGS_ARG_CHECK(img1 && img2 && out_mean && partials, "null pointer");
+  PINGS_ARG_CHECK(planes > 0 && H > 0 && W > 0, "empty image");
+  PINGS_ARG_CHECK(planes <= 65535, "too many planes");
+  PINGS_ARG_CHECK(!train || (dm_dmu1 && dm_dsigma1_sq && dm_dsigma12),
+                  "train=1 needs the three derivative maps");
+  hipStream_t st = pings::as_stream(stream);
+  const SsimPlan p = ssim_plan(planes, H, W);
+  const char* fwd_env = getenv("PINGS_SSIM_FWD");
+  const bool hfirst = fwd_env && fwd_env[0] == 's';   // PINGS_SSIM_FWD=sw: the horizontal-first kernel (A/B runs)
+  const auto kernel = train ? (hfirst ? ssim_fwd_sw_kernel<true> : ssim_fwd_vf_kernel<true>)
+                            : (hfirst ? ssim_fwd_sw_kernel<false> : ssim_fwd_vf_kernel<false>);
+  float* const none = nullptr;
+  pings::prof::Scope ps("ssim_fwd", st);
+  hipLaunchKernelGGL(kernel, dim3(p.nblk), dim3(256), 0, st, img1, img2, planes, H, W, p.rb, p.strips, p.bands, p.alt,
+                     train ? dm_dmu1 : none, train ? dm_dsigma1_sq : none, train ? dm_dsigma12 : none, partials);
+  PINGS_LAUNCH_CHECK();
+  const double inv_count = 1.0 / ((double)planes * H * W);
+  hipLaunchKernelGGL(ssim_reduce_kernel, dim3(1), dim3(NT), 0, st, partials, p.units, inv_count, out_mean);
+  PINGS_LAUNCH_CHECK();
+  return PINGS_OK;
+}
+
+PINGS_API int pings_ssim_backward(const float* img1, const float* img2, int planes, int H, int W,
+                                  const float* dL_dmean, const float* dm_dmu1,
+                                  const float* dm_dsigma1_sq, const float* dm_dsigma12,
+                                  float* dL_dimg1, void* stream) {
+  PINGS_ARG_CHECK(img1 && img2 && dL_dmean && dm_dmu1 && dm_dsigma1_sq && dm_dsigma12 && dL_dimg1,
+                  "null pointer");
+  PINGS_ARG_CHECK(planes > 0 && H > 0 && W > 0, "empty image");
+  PINGS_ARG_CHECK(planes <= 65535, "too many planes");
+  hipStream_t st = pings::as_stream(stream);
+  const float inv_count = (float)(1.0 / ((double)planes * H * W));
+  const char* bwd_env = getenv("PINGS_SSIM_BWD");
+  pings::prof::Scope ps("ssim_bwd", st);
+  if (bwd_env && bwd_env[0] == 't') {           // PINGS_SSIM_BWD=tile: the LDS-tile kernel (A/B runs)
     const size_t n = (size_t)planes * pings::ceil_div(H, TS) * pings::ceil_div(W, TS);
     const dim3 grid((unsigned)(n < (size_t)PERSISTENT_WGS ? n : (size_t)PERSISTENT_WGS));
-    pings::prof::Scope ps("ssim_fwd", st);
-    if (train) {
-      hipLaunchKernelGGL(ssim_fwd_kernel<true>, grid, dim3(NT), 0, st, img1, img2, planes, H, W, dm_dmu1,
-                         dm_dsigma1_sq, dm_dsigma12, partials);
-    } else {
-      hipLaunchKernelGGL(ssim_fwd_kernel<false>, grid, dim3(NT), 0, st, img1, img2, planes, H, W,
-                         (float*)nullptr, (float*)nullptr, (float*)nullptr, partials);
-    }
-    PINGS_LAUNCH_CHECK();
-    const double inv_count = 1.0 / ((double)planes * H * W);
-    hipLaunchKernelGGL(ssim_reduce_kernel, dim3(1), dim3(NT), 0, st, partials, n, inv_count,
-                       out_mean);
-    PINGS_LAUNCH_CHECK();
-    return PINGS_OK;
-  }
-
-  PINGS_API int pings_ssim_backward(const float* img1, const float* img2, int planes, int H, int W,
-                                    const float* dL_dmean, const float* dm_dmu1,
-                                    const float* dm_dsigma1_sq, const float* dm_dsigma12,
-                                    float* dL_dimg1, void* stream) {
-    PINGS_ARG_CHECK(img1 && img2 && dL_dmean && dm_dmu1 && dm_dsigma1_sq && dm_dsigma12 && dL_dimg1,
-                    "null pointer");
-    PINGS_ARG_CHECK(planes > 0 && H > 0 && W > 0, "empty image");
-    PINGS_ARG_CHECK(planes <= 65535, "too many planes");
-    hipStream_t st = pings::as_stream(stream);
-    const float inv_count = (float)(1.0 / ((double)planes * H * W));
-    const char* bwd_env = getenv("PINGS_SSIM_BWD");
-    if (!(bwd_env && bwd_env[0] == 't')) {      // default: the sliding-window kernel
-      const int rb = sw_rows_per_band(planes, H, W);
-      const int strips = pings::ceil_div(W, SW_OUT), bands = pings::ceil_div(H, rb);
-      const size_t units = (size_t)planes * bands * strips;
-      unsigned nblk = (unsigned)pings::ceil_div<size_t>(units, 4);
-      nblk = (nblk + 7u) & ~7u;
-      pings::prof::Scope ps("ssim_bwd", st);
-      if (bwd_env && bwd_env[0] == 's')              // PINGS_SSIM_BWD=sw: the horizontal-first kernel (A/B runs)
-        hipLaunchKernelGGL(ssim_bwd_sw_kernel, dim3(nblk), dim3(256), 0, st, img1, img2, planes, H, W, rb, strips, bands,
-                           sw_alternate(), dL_dmean, inv_count, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dimg1);
-      else
-        hipLaunchKernelGGL(ssim_bwd_vf_kernel, dim3(nblk), dim3(256), 0, st, img1, img2, planes, H, W, rb, strips, bands,
-                           sw_alternate(), dL_dmean, inv_count, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dimg1);
-      PINGS_LAUNCH_CHECK();
-      return PINGS_OK;
-    }
-    const size_t n = (size_t)planes * pings::ceil_div(H, TS) * pings::ceil_div(W, TS);
-    const dim3 grid((unsigned)(n < (size_t)PERSISTENT_WGS ? n : (size_t)PERSISTENT_WGS));
-    pings::prof::Scope ps("ssim_bwd", st);
     hipLaunchKernelGGL(ssim_bwd_kernel, grid, dim3(NT), 0, st, img1, img2, planes, H, W, dL_dmean,
                        inv_count, dm_dmu1, dm_dsigma1_sq, dm_dsigma12, dL_dimg1);
-    PINGS_LAUNCH_CHECK();
-    return PINGS_OK;
+  } else {
+    const SsimPlan p = ssim_plan(planes, H, W);
+    const bool hfirst = bwd_env && bwd_env[0] == 's';   // PINGS_SSIM_BWD=sw: the horizontal-first kernel (A/B runs)
+    hipLaunchKernelGGL(hfirst ? ssim_bwd_sw_kernel : ssim_bwd_vf_kernel, dim3(p.nblk), dim3(256), 0, st, img1, img2,
+                       planes, H, W, p.rb, p.strips, p.bands, p.alt, dL_dmean, inv_count, dm_dmu1, dm_dsigma1_sq,
+                       dm_dsigma12, dL_dimg1);
   }
+  PINGS_LAUNCH_CHECK();
+  return PINGS_OK;
+}
+

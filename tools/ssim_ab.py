@@ -1,5 +1,5 @@
-"""A/B of the fused-SSIM forward kernels at 1080p x 3: python tools/ssim_ab.py
-(tile kernel of rounds 1-3 vs the sliding-window kernel at several band heights; bit-equality of the map statistics)"""
+"""A/B of the fused-SSIM sliding-window kernels at 1080p x 3: python tools/ssim_ab.py
+(horizontal pass first vs vertical pass first at several band heights; value and gradient against the first entry's)"""
 import json
 import os
 import sys
@@ -15,8 +15,8 @@ g = torch.Generator(device=dev).manual_seed(1)
 a = torch.rand(1, 3, 1080, 1920, generator=g, device=dev, requires_grad=True)
 b = torch.rand(1, 3, 1080, 1920, generator=g, device=dev)
 ref = None
-# "tile": rounds 1-3; "sw": sliding window, horizontal pass first; "vf": sliding window, vertical pass first (default)
-for fwd, rb in (("tile", None), ("sw", None), ("vf", None), ("vf", 28), ("vf", 32), ("vf", 48), ("vf", 64), ("sw", 32), ("sw", 64)):
+# "sw": sliding window, horizontal pass first; "vf": sliding window, vertical pass first (default)
+for fwd, rb in (("sw", None), ("vf", None), ("vf", 28), ("vf", 32), ("vf", 48), ("vf", 64), ("sw", 32), ("sw", 64)):
     os.environ["PINGS_SSIM_FWD"] = fwd
     os.environ["PINGS_SSIM_BWD"] = fwd
     if rb is None:
