@@ -895,21 +895,21 @@ __device__ inline uint32_t wave_reduce_sum_u32(uint32_t v) {
 }
 
 // Per-Gaussian sum of its per-instance values (contiguous run of `tiles` slots).  One lane per
-// depth rank (neighbouring lanes own neighbouring runs); runs longer than SMALL_RUN are summed by
-// the whole wave.  Fixed summation order -> bitwise reproducible.
+// depth rank; runs longer than SMALL_RUN are summed by the whole wave.  Fixed summation order -> bitwise reproducible.
 constexpr int SMALL_RUN = 16;
 template <typename T>
 __global__ __launch_bounds__(256) void per_gaussian_sum_kernel(
-    int P, const uint4* __restrict__ rect, const uint32_t* __restrict__ rank_of,
+    int P, const uint32_t* __restrict__ gidx_sorted, const uint32_t* __restrict__ nvalid,
     const uint32_t* __restrict__ offsets_sorted, const uint32_t* __restrict__ tiles_sorted,
     const T* __restrict__ inst, T* __restrict__ out) {
-  // one lane per Gaussian in INDEX order (coalesced output; depth order is random in the index, so long runs are
-  // spread over the waves anyway); the run of a surviving Gaussian is found through its depth rank
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  // one lane per DEPTH RANK, all P of them: gidx_sorted is a permutation of the Gaussians (the culled ones fill the
+  // ranks from nvalid on), so every entry of `out` is written exactly once and neither the rectangle nor the rank of
+  // a Gaussian is looked up.  The run of rank r is found with two coalesced words; the long runs sit at neighbouring
+  // ranks and are dealt to different waves (strided_rank).
+  const int r = strided_rank(P);
   const int lane = threadIdx.x & 63;
   uint32_t n = 0, base = 0;
-  if (g < P && rect[g].w != 0u) {
-    const uint32_t r = rank_of[g];
+  if (r >= 0 && (uint32_t)r < *nvalid) {
     n = tiles_sorted[r];
     base = offsets_sorted[r] - n;
   }
@@ -939,7 +939,7 @@ __global__ __launch_bounds__(256) void per_gaussian_sum_kernel(
     }
     if (lane == src) sum = acc;
   }
-  if (g < P) out[g] = sum;
+  if (r >= 0) out[gidx_sorted[r]] = sum;
 }
 
 // ---------------------------------------------------------------- host: the forward kernels of a BlendPlan
@@ -1022,11 +1022,11 @@ int launch_blend_fwd(int mode, const KParams& kp, const BlendPlan& plan, int P, 
     if (I == 0) {
       PINGS_HIP_CHECK(hipMemsetAsync(per_gaussian, 0, 4 * (size_t)P, st));
     } else if (mode == PINGS_RASTER_SURFEL) {
-      hipLaunchKernelGGL(per_gaussian_sum_kernel<float>, grid, block, 0, st, P, gs.rect, gs.rank_of,
+      hipLaunchKernelGGL(per_gaussian_sum_kernel<float>, grid, block, 0, st, P, gs.gidx_sorted, gs.nvalid,
                          gs.offsets_sorted, gs.tiles_sorted, (const float*)bs.inst_w,
                          reinterpret_cast<float*>(per_gaussian));
     } else {
-      hipLaunchKernelGGL(per_gaussian_sum_kernel<uint32_t>, grid, block, 0, st, P, gs.rect, gs.rank_of,
+      hipLaunchKernelGGL(per_gaussian_sum_kernel<uint32_t>, grid, block, 0, st, P, gs.gidx_sorted, gs.nvalid,
                          gs.offsets_sorted, gs.tiles_sorted, (const uint32_t*)bs.inst_cnt,
                          reinterpret_cast<uint32_t*>(per_gaussian));
     }

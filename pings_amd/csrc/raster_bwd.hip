@@ -14,11 +14,12 @@
 //                         pixel instead of a reduction per record; one row per (live instance, quadrant).
 //   row_chunk_sum_kernel  balanced first level of the per-Gaussian sum: one 16-lane group per
 //                         (Gaussian, chunk of <= 64 rows) pair, lane = column, streaming 64-B rows.
-//   gaussian_bwd_kernel   per Gaussian (in index order, rows located through its depth rank): adds its chunk partials, then chains
-//                         through conic / EWA projection / quaternion / scale / camera transform to
-//                         the input gradients and the pose-tangent terms (block-reduced, fixed order).
+//   gaussian_bwd_*_kernel per Gaussian: adds its chunk partials, then chains through conic / EWA projection /
+//                         quaternion / scale / camera transform to the input gradients and the pose-tangent terms
+//                         (block-reduced, fixed order).  _rank_: over the depth ranks that own a pair, behind grad_zero_kernel (few
+//                         Gaussians own a row); _index_: in index order, rows located through the depth rank (most do).
 //   tau_reduce_kernel     final fixed-order reduction of the pose-tangent partials.  (Run by the last workgroup of
-//                         gaussian_bwd_kernel instead, behind a device-scope fence and a ticket, it saved the launch
+//                         the chain kernel instead, behind a device-scope fence and a ticket, it saved the launch
 //                         and cost 640 us: the release writes back the L2 of the workgroup's XCD, once per workgroup,
 //                         while the gradient stores of the others keep it dirty.)
 //
@@ -735,237 +736,274 @@ __global__ __launch_bounds__(256) void blend_bwd_scan_kernel(
 // ---------------------------------------------------------------- balanced per-Gaussian row sums
 // LiveOp, RowRanges: raster_common.hpp; pair_off and pair_owner: raster_scan_chunks
 
-// one 16-lane group per (Gaussian, chunk) pair; lane = column of the 16-float row
+// one 16-lane group per (Gaussian, chunk) pair; lane = column of the 16-float row.  The number of pairs lives on the
+// device (pair_off[P]): a bounded grid (PINGS_ROWSUM_WGS workgroups) strides over them, instead of a grid for the
+// host's upper bound np_max whose workgroups mostly read the count and leave.
 __global__ __launch_bounds__(256) void row_chunk_sum_kernel(RowRanges rr, const uint32_t* __restrict__ pair_off,
                                                              const uint32_t* __restrict__ pair_owner,
                                                              const float* __restrict__ rows,
                                                              float* __restrict__ partials) {
-  const uint32_t q = (uint32_t)((blockIdx.x * (size_t)blockDim.x + threadIdx.x) >> 4);
   const int c = threadIdx.x & 15;
-  if (q >= pair_off[rr.P]) return;
-  const uint32_t r = pair_owner[q];
-  const uint32_t j = q - pair_off[r];
-  const uint32_t row_end = rr.row_end(r);
-  uint32_t row = rr.row_begin(r) + j * (uint32_t)CH;
-  const uint32_t stop = min(row + (uint32_t)CH, row_end);
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  for (; row + 4 <= stop; row += 4) {
-    a0 += rows[(size_t)row * 16 + c];
-    a1 += rows[(size_t)(row + 1) * 16 + c];
-    a2 += rows[(size_t)(row + 2) * 16 + c];
-    a3 += rows[(size_t)(row + 3) * 16 + c];
+  const uint32_t npairs = pair_off[rr.P];
+  const uint32_t stride = gridDim.x * (256u / 16u);
+  for (uint32_t q = blockIdx.x * (256u / 16u) + (threadIdx.x >> 4); q < npairs; q += stride) {
+    const uint32_t r = pair_owner[q];
+    const uint32_t j = q - pair_off[r];
+    const uint32_t row_end = rr.row_end(r);
+    uint32_t row = rr.row_begin(r) + j * (uint32_t)CH;
+    const uint32_t stop = min(row + (uint32_t)CH, row_end);
+    float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+    for (; row + 4 <= stop; row += 4) {
+      a0 += rows[(size_t)row * 16 + c];
+      a1 += rows[(size_t)(row + 1) * 16 + c];
+      a2 += rows[(size_t)(row + 2) * 16 + c];
+      a3 += rows[(size_t)(row + 3) * 16 + c];
+    }
+    for (; row < stop; ++row) a0 += rows[(size_t)row * 16 + c];
+    partials[(size_t)q * 16 + c] = (a0 + a1) + (a2 + a3);
   }
-  for (; row < stop; ++row) a0 += rows[(size_t)row * 16 + c];
-  partials[(size_t)q * 16 + c] = (a0 + a1) + (a2 + a3);
 }
 
 // ---------------------------------------------------------------- per-Gaussian chain
+// The six gradient arrays start at zero: all but a few per cent of the Gaussians own no live row (culled, or no tile
+// kept behind the occlusion bound, or never blended), and gaussian_bwd_rank_kernel only visits the depth ranks that do.
+// 16-byte stores, no reads; an array's unaligned head and its tail go out as single floats.
+struct GradFill {
+  float* ptr[6];
+  size_t count[6];   // floats
+};
+__global__ __launch_bounds__(256) void grad_zero_kernel(GradFill f) {
+  const size_t tid = (size_t)blockIdx.x * 256u + threadIdx.x, nthreads = (size_t)gridDim.x * 256u;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    float* const p = f.ptr[a];
+    const size_t n = f.count[a];
+    const size_t head = min(n, (size_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2);
+    const size_t nvec = (n - head) >> 2;
+    float4* const body = reinterpret_cast<float4*>(p + head);
+    for (size_t i = tid; i < nvec; i += nthreads) body[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+    const size_t tail = head + 4 * nvec;   // fewer than four floats each: the first threads take them
+    if (tid < head) p[tid] = 0.f;
+    if (tid < n - tail) p[tail + tid] = 0.f;
+  }
+}
+
+// G += the chunk partials [qa, qb) of one Gaussian, in ascending order; AHEAD rows are loaded before their adds (the
+// adds keep their order, so the sums keep their bits)
+template <int AHEAD>
+__device__ inline void sum_partials(const float* __restrict__ partials, uint32_t qa, uint32_t qb, float (&G)[16]) {
+  const float4* prow = reinterpret_cast<const float4*>(partials);
+  uint32_t k = qa;
+  if (AHEAD > 1) {
+    for (; k + AHEAD <= qb; k += AHEAD) {
+      float4 ld[AHEAD][4];
+#pragma unroll
+      for (int u = 0; u < AHEAD; ++u)
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) ld[u][q4] = prow[(size_t)(k + u) * 4 + q4];
+#pragma unroll
+      for (int u = 0; u < AHEAD; ++u)
+#pragma unroll
+        for (int q4 = 0; q4 < 4; ++q4) {
+          G[q4 * 4 + 0] += ld[u][q4].x;
+          G[q4 * 4 + 1] += ld[u][q4].y;
+          G[q4 * 4 + 2] += ld[u][q4].z;
+          G[q4 * 4 + 3] += ld[u][q4].w;
+        }
+    }
+  }
+  for (; k < qb; ++k) {
+#pragma unroll
+    for (int q4 = 0; q4 < 4; ++q4) {
+      const float4 r = prow[(size_t)k * 4 + q4];
+      G[q4 * 4 + 0] += r.x;
+      G[q4 * 4 + 1] += r.y;
+      G[q4 * 4 + 2] += r.z;
+      G[q4 * 4 + 3] += r.w;
+    }
+  }
+}
+
+// The gradient row of Gaussian g from its summed blend gradients G: the chain through projection, covariance and
+// quaternion when the Gaussian has a live row (`live`), zeros otherwise; tau = its pose-tangent terms.
 template <int MODE>
-__global__ __launch_bounds__(256, 4) void gaussian_bwd_kernel(
-    BParams p, const float* __restrict__ means3D, const float* __restrict__ scales,
-    const float* __restrict__ rotations, const uint4* __restrict__ rect, const uint32_t* __restrict__ rank_of,
-    const uint32_t* __restrict__ tiles_sorted, const uint32_t* __restrict__ pair_off,
-    const float* __restrict__ partials, float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dcolors,
-    float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales,
-    float* __restrict__ dL_drotations, float* __restrict__ tau_partials) {
-  __shared__ float sTau[256 / 64][6];
-  // one thread per Gaussian in INDEX order: parameters are read and gradients written coalesced; only the two
-  // words that locate the Gaussian's chunk partials go through its depth rank
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-  if (g < p.P) {
-    uint32_t n_tiles = 0u, qa = 0u, qb = 0u;
-    if (rect[g].w != 0u) {  // survived culling: has a depth rank
-      const uint32_t rank = rank_of[g];
-      n_tiles = tiles_sorted[rank];
-      qa = pair_off[rank];
-      qb = pair_off[rank + 1];
-    }
-    float G[16];
-#pragma unroll
-    for (int k = 0; k < 16; ++k) G[k] = 0.f;
-    const float4* prow = reinterpret_cast<const float4*>(partials);
-    for (uint32_t k = qa; k < qb; ++k) {
-#pragma unroll
-      for (int q4 = 0; q4 < 4; ++q4) {
-        const float4 r = prow[(size_t)k * 4 + q4];
-        G[q4 * 4 + 0] += r.x;
-        G[q4 * 4 + 1] += r.y;
-        G[q4 * 4 + 2] += r.z;
-        G[q4 * 4 + 3] += r.w;
-      }
-    }
-
-    float gm[3] = {0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f}, gq4[4] = {0.f, 0.f, 0.f, 0.f};
-    float g2d[2] = {0.f, 0.f};
-    if (n_tiles > 0 && qb > qa) {
-      const float* V = p.view;
-      const float* Pm = p.proj_raw;
-      const float x = means3D[3 * g], y = means3D[3 * g + 1], z = means3D[3 * g + 2];
-      const float px = ((V[0] * x + V[4] * y) + V[8] * z) + V[12];
-      const float py = ((V[1] * x + V[5] * y) + V[9] * z) + V[13];
-      const float pz = ((V[2] * x + V[6] * y) + V[10] * z) + V[14];
-      float gp[3] = {0.f, 0.f, 0.f};
-      // ---- 2-D mean
-      {
-        const float hx = ((Pm[0] * px + Pm[4] * py) + Pm[8] * pz) + Pm[12];
-        const float hy = ((Pm[1] * px + Pm[5] * py) + Pm[9] * pz) + Pm[13];
-        const float hw = ((Pm[3] * px + Pm[7] * py) + Pm[11] * pz) + Pm[15];
-        const float pw = 1.0f / (hw + 1e-7f);
-        const float gndx = 0.5f * (float)p.W * G[G_MX];
-        const float gndy = 0.5f * (float)p.H * G[G_MY];
-        g2d[0] = gndx;
-        g2d[1] = gndy;
-        const float kx = hx * pw * pw, ky = hy * pw * pw;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-          gp[i] = gndx * (Pm[4 * i + 0] * pw - kx * Pm[4 * i + 3]) +
-                  gndy * (Pm[4 * i + 1] * pw - ky * Pm[4 * i + 3]);
-      }
-      // ---- covariance
-      const float qr = rotations[4 * g], qx = rotations[4 * g + 1], qy = rotations[4 * g + 2],
-                  qz = rotations[4 * g + 3];
-      float R[3][3];
-      R[0][0] = 1.0f - 2.0f * (qy * qy + qz * qz); R[0][1] = 2.0f * (qx * qy - qr * qz); R[0][2] = 2.0f * (qx * qz + qr * qy);
-      R[1][0] = 2.0f * (qx * qy + qr * qz); R[1][1] = 1.0f - 2.0f * (qx * qx + qz * qz); R[1][2] = 2.0f * (qy * qz - qr * qx);
-      R[2][0] = 2.0f * (qx * qz - qr * qy); R[2][1] = 2.0f * (qy * qz + qr * qx); R[2][2] = 1.0f - 2.0f * (qx * qx + qy * qy);
-      const float S[3] = {p.scale_mod * scales[3 * g], p.scale_mod * scales[3 * g + 1],
-                          p.scale_mod * scales[3 * g + 2]};
-      float RS[3][3], Mc[3][3];
+__device__ inline void gaussian_row(const BParams& p, int g, bool live, const float (&G)[16],
+                                    const float* __restrict__ means3D, const float* __restrict__ scales,
+                                    const float* __restrict__ rotations, float* __restrict__ dL_dmeans3D,
+                                    float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dcolors,
+                                    float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales,
+                                    float* __restrict__ dL_drotations, float (&tau)[6]) {
+  float gm[3] = {0.f, 0.f, 0.f}, gs[3] = {0.f, 0.f, 0.f}, gq4[4] = {0.f, 0.f, 0.f, 0.f};
+  float g2d[2] = {0.f, 0.f};
+  if (live) {
+    const float* V = p.view;
+    const float* Pm = p.proj_raw;
+    const float x = means3D[3 * g], y = means3D[3 * g + 1], z = means3D[3 * g + 2];
+    const float px = ((V[0] * x + V[4] * y) + V[8] * z) + V[12];
+    const float py = ((V[1] * x + V[5] * y) + V[9] * z) + V[13];
+    const float pz = ((V[2] * x + V[6] * y) + V[10] * z) + V[14];
+    float gp[3] = {0.f, 0.f, 0.f};
+    // ---- 2-D mean
+    {
+      const float hx = ((Pm[0] * px + Pm[4] * py) + Pm[8] * pz) + Pm[12];
+      const float hy = ((Pm[1] * px + Pm[5] * py) + Pm[9] * pz) + Pm[13];
+      const float hw = ((Pm[3] * px + Pm[7] * py) + Pm[11] * pz) + Pm[15];
+      const float pw = 1.0f / (hw + 1e-7f);
+      const float gndx = 0.5f * (float)p.W * G[G_MX];
+      const float gndy = 0.5f * (float)p.H * G[G_MY];
+      g2d[0] = gndx;
+      g2d[1] = gndy;
+      const float kx = hx * pw * pw, ky = hy * pw * pw;
 #pragma unroll
       for (int i = 0; i < 3; ++i)
+        gp[i] = gndx * (Pm[4 * i + 0] * pw - kx * Pm[4 * i + 3]) +
+                gndy * (Pm[4 * i + 1] * pw - ky * Pm[4 * i + 3]);
+    }
+    // ---- covariance
+    const float qr = rotations[4 * g], qx = rotations[4 * g + 1], qy = rotations[4 * g + 2],
+                qz = rotations[4 * g + 3];
+    float R[3][3];
+    R[0][0] = 1.0f - 2.0f * (qy * qy + qz * qz); R[0][1] = 2.0f * (qx * qy - qr * qz); R[0][2] = 2.0f * (qx * qz + qr * qy);
+    R[1][0] = 2.0f * (qx * qy + qr * qz); R[1][1] = 1.0f - 2.0f * (qx * qx + qz * qz); R[1][2] = 2.0f * (qy * qz - qr * qx);
+    R[2][0] = 2.0f * (qx * qz - qr * qy); R[2][1] = 2.0f * (qy * qz + qr * qx); R[2][2] = 1.0f - 2.0f * (qx * qx + qy * qy);
+    const float S[3] = {p.scale_mod * scales[3 * g], p.scale_mod * scales[3 * g + 1],
+                        p.scale_mod * scales[3 * g + 2]};
+    float RS[3][3], Mc[3][3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) RS[i][k] = R[i][k] * S[k];
+    for (int i = 0; i < 3; ++i)
 #pragma unroll
-      for (int a = 0; a < 3; ++a)
+      for (int k = 0; k < 3; ++k) RS[i][k] = R[i][k] * S[k];
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-          Mc[a][k] = (V[a] * RS[0][k] + V[4 + a] * RS[1][k]) + V[8 + a] * RS[2][k];
-      const float txz = px / pz, tyz = py / pz;
-      const bool clx = (txz < -p.limx) || (txz > p.limx), cly = (tyz < -p.limy) || (tyz > p.limy);
-      const float tx = fminf(p.limx, fmaxf(-p.limx, txz)) * pz;
-      const float ty = fminf(p.limy, fmaxf(-p.limy, tyz)) * pz;
-      const float iz = 1.0f / pz, iz2 = iz * iz;
-      const float J00 = p.fx * iz, J02 = -(p.fx * tx) * iz2, J11 = p.fy * iz, J12 = -(p.fy * ty) * iz2;
-      float T0[3], T1[3];
+    for (int a = 0; a < 3; ++a)
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        T0[k] = J00 * Mc[0][k] + J02 * Mc[2][k];
-        T1[k] = J11 * Mc[1][k] + J12 * Mc[2][k];
-      }
-      const float ca = ((T0[0] * T0[0] + T0[1] * T0[1]) + T0[2] * T0[2]) + LOWPASS;
-      const float cb = (T0[0] * T1[0] + T0[1] * T1[1]) + T0[2] * T1[2];
-      const float cc = ((T1[0] * T1[0] + T1[1] * T1[1]) + T1[2] * T1[2]) + LOWPASS;
-      // the blend pass accumulated dL/d(cov2D) directly: a = cov_xx, b = cov_xy (the single
-      // off-diagonal parameter), c = cov_yy
-      (void)ca; (void)cb; (void)cc;
-      const float ga = G[G_CONX], gb = G[G_CONY], gc = G[G_CONZ];
-      float gT0[3], gT1[3], gMc[3][3];
-      float gJ00 = 0.f, gJ02 = 0.f, gJ11 = 0.f, gJ12 = 0.f;
+      for (int k = 0; k < 3; ++k)
+        Mc[a][k] = (V[a] * RS[0][k] + V[4 + a] * RS[1][k]) + V[8 + a] * RS[2][k];
+    const float txz = px / pz, tyz = py / pz;
+    const bool clx = (txz < -p.limx) || (txz > p.limx), cly = (tyz < -p.limy) || (tyz > p.limy);
+    const float tx = fminf(p.limx, fmaxf(-p.limx, txz)) * pz;
+    const float ty = fminf(p.limy, fmaxf(-p.limy, tyz)) * pz;
+    const float iz = 1.0f / pz, iz2 = iz * iz;
+    const float J00 = p.fx * iz, J02 = -(p.fx * tx) * iz2, J11 = p.fy * iz, J12 = -(p.fy * ty) * iz2;
+    float T0[3], T1[3];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        gT0[k] = 2.0f * ga * T0[k] + gb * T1[k];
-        gT1[k] = 2.0f * gc * T1[k] + gb * T0[k];
-        gJ00 += gT0[k] * Mc[0][k];
-        gJ02 += gT0[k] * Mc[2][k];
-        gJ11 += gT1[k] * Mc[1][k];
-        gJ12 += gT1[k] * Mc[2][k];
-        gMc[0][k] = J00 * gT0[k];
-        gMc[1][k] = J11 * gT1[k];
-        gMc[2][k] = J02 * gT0[k] + J12 * gT1[k];
-      }
-      // J -> camera point
-      gp[2] += -p.fx * iz2 * gJ00 - p.fy * iz2 * gJ11;
-      gp[2] += 2.0f * p.fx * tx * iz2 * iz * gJ02 + 2.0f * p.fy * ty * iz2 * iz * gJ12;
-      const float gtx = -p.fx * iz2 * gJ02, gty = -p.fy * iz2 * gJ12;
-      if (clx) gp[2] += gtx * tx * iz; else gp[0] += gtx;
-      if (cly) gp[2] += gty * ty * iz; else gp[1] += gty;
-      // Mc = Wc RS
-      float gRS[3][3], gWc[3][3];
+    for (int k = 0; k < 3; ++k) {
+      T0[k] = J00 * Mc[0][k] + J02 * Mc[2][k];
+      T1[k] = J11 * Mc[1][k] + J12 * Mc[2][k];
+    }
+    const float ca = ((T0[0] * T0[0] + T0[1] * T0[1]) + T0[2] * T0[2]) + LOWPASS;
+    const float cb = (T0[0] * T1[0] + T0[1] * T1[1]) + T0[2] * T1[2];
+    const float cc = ((T1[0] * T1[0] + T1[1] * T1[1]) + T1[2] * T1[2]) + LOWPASS;
+    // the blend pass accumulated dL/d(cov2D) directly: a = cov_xx, b = cov_xy (the single
+    // off-diagonal parameter), c = cov_yy
+    (void)ca; (void)cb; (void)cc;
+    const float ga = G[G_CONX], gb = G[G_CONY], gc = G[G_CONZ];
+    float gT0[3], gT1[3], gMc[3][3];
+    float gJ00 = 0.f, gJ02 = 0.f, gJ11 = 0.f, gJ12 = 0.f;
 #pragma unroll
-      for (int b = 0; b < 3; ++b)
+    for (int k = 0; k < 3; ++k) {
+      gT0[k] = 2.0f * ga * T0[k] + gb * T1[k];
+      gT1[k] = 2.0f * gc * T1[k] + gb * T0[k];
+      gJ00 += gT0[k] * Mc[0][k];
+      gJ02 += gT0[k] * Mc[2][k];
+      gJ11 += gT1[k] * Mc[1][k];
+      gJ12 += gT1[k] * Mc[2][k];
+      gMc[0][k] = J00 * gT0[k];
+      gMc[1][k] = J11 * gT1[k];
+      gMc[2][k] = J02 * gT0[k] + J12 * gT1[k];
+    }
+    // J -> camera point
+    gp[2] += -p.fx * iz2 * gJ00 - p.fy * iz2 * gJ11;
+    gp[2] += 2.0f * p.fx * tx * iz2 * iz * gJ02 + 2.0f * p.fy * ty * iz2 * iz * gJ12;
+    const float gtx = -p.fx * iz2 * gJ02, gty = -p.fy * iz2 * gJ12;
+    if (clx) gp[2] += gtx * tx * iz; else gp[0] += gtx;
+    if (cly) gp[2] += gty * ty * iz; else gp[1] += gty;
+    // Mc = Wc RS
+    float gRS[3][3], gWc[3][3];
 #pragma unroll
-        for (int k = 0; k < 3; ++k)
-          gRS[b][k] = (V[4 * b + 0] * gMc[0][k] + V[4 * b + 1] * gMc[1][k]) + V[4 * b + 2] * gMc[2][k];
+    for (int b = 0; b < 3; ++b)
 #pragma unroll
-      for (int a = 0; a < 3; ++a)
+      for (int k = 0; k < 3; ++k)
+        gRS[b][k] = (V[4 * b + 0] * gMc[0][k] + V[4 * b + 1] * gMc[1][k]) + V[4 * b + 2] * gMc[2][k];
 #pragma unroll
-        for (int b = 0; b < 3; ++b)
-          gWc[a][b] = (gMc[a][0] * RS[b][0] + gMc[a][1] * RS[b][1]) + gMc[a][2] * RS[b][2];
-      float gR[3][3];
-      float gS[3] = {0.f, 0.f, 0.f};
-#pragma unroll
-      for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-          gS[k] += gRS[i][k] * R[i][k];
-          gR[i][k] = gRS[i][k] * S[k];
-        }
-      float gpz_direct = G[G_PZ];
-      if (MODE == MODE_SURFEL) {
-        // normal n = sgn * Wc R[:,2], q = n . p
-        float nx = (V[0] * R[0][2] + V[4] * R[1][2]) + V[8] * R[2][2];
-        float ny = (V[1] * R[0][2] + V[5] * R[1][2]) + V[9] * R[2][2];
-        float nz = (V[2] * R[0][2] + V[6] * R[1][2]) + V[10] * R[2][2];
-        const float q = (nx * px + ny * py) + nz * pz;
-        float sgn = 1.0f;
-        if (!p.front_only && q > 0.0f) sgn = -1.0f;
-        nx *= sgn; ny *= sgn; nz *= sgn;
-        const float gq = G[G_Q];
-        const float gn[3] = {G[G_NX] + gq * px, G[G_NY] + gq * py, G[G_NZ] + gq * pz};
-        gp[0] += gq * nx;
-        gp[1] += gq * ny;
-        gp[2] += gq * nz;
-#pragma unroll
-        for (int b = 0; b < 3; ++b) {
-          gR[b][2] += sgn * ((V[4 * b + 0] * gn[0] + V[4 * b + 1] * gn[1]) + V[4 * b + 2] * gn[2]);
-#pragma unroll
-          for (int a = 0; a < 3; ++a) gWc[a][b] += sgn * gn[a] * R[b][2];
-        }
-        // depth clamp window zlo = pz - rz, zhi = pz + rz, rz = 3 max(S0, S1)
-        gpz_direct += G[G_ZLO] + G[G_ZHI];
-        const float grz = 3.0f * (G[G_ZHI] - G[G_ZLO]);
-        if (S[0] > S[1]) gS[0] += grz;
-        else if (S[1] > S[0]) gS[1] += grz;
-        else { gS[0] += 0.5f * grz; gS[1] += 0.5f * grz; }
-      }
-      gp[2] += gpz_direct;
-      // quaternion
-      gq4[0] = 2.0f * (-qz * gR[0][1] + qy * gR[0][2] + qz * gR[1][0] - qx * gR[1][2] - qy * gR[2][0] + qx * gR[2][1]);
-      gq4[1] = 2.0f * (qy * gR[0][1] + qz * gR[0][2] + qy * gR[1][0] - 2.0f * qx * gR[1][1] - qr * gR[1][2] + qz * gR[2][0] + qr * gR[2][1] - 2.0f * qx * gR[2][2]);
-      gq4[2] = 2.0f * (-2.0f * qy * gR[0][0] + qx * gR[0][1] + qr * gR[0][2] + qx * gR[1][0] + qz * gR[1][2] - qr * gR[2][0] + qz * gR[2][1] - 2.0f * qy * gR[2][2]);
-      gq4[3] = 2.0f * (-2.0f * qz * gR[0][0] - qr * gR[0][1] + qx * gR[0][2] + qr * gR[1][0] - 2.0f * qz * gR[1][1] + qy * gR[1][2] + qx * gR[2][0] + qy * gR[2][1]);
-#pragma unroll
-      for (int k = 0; k < 3; ++k) gs[k] = p.scale_mod * gS[k];
-      // world mean: p = Wc m + t
+    for (int a = 0; a < 3; ++a)
 #pragma unroll
       for (int b = 0; b < 3; ++b)
-        gm[b] = (V[4 * b + 0] * gp[0] + V[4 * b + 1] * gp[1]) + V[4 * b + 2] * gp[2];
-      // pose tangent at tau = 0: d rho = gp ; d theta = p x gp + sum_b Wc[:,b] x gWc[:,b]
-      tau[0] = gp[0]; tau[1] = gp[1]; tau[2] = gp[2];
-      float th0 = py * gp[2] - pz * gp[1];
-      float th1 = pz * gp[0] - px * gp[2];
-      float th2 = px * gp[1] - py * gp[0];
+        gWc[a][b] = (gMc[a][0] * RS[b][0] + gMc[a][1] * RS[b][1]) + gMc[a][2] * RS[b][2];
+    float gR[3][3];
+    float gS[3] = {0.f, 0.f, 0.f};
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+      for (int k = 0; k < 3; ++k) {
+        gS[k] += gRS[i][k] * R[i][k];
+        gR[i][k] = gRS[i][k] * S[k];
+      }
+    float gpz_direct = G[G_PZ];
+    if (MODE == MODE_SURFEL) {
+      // normal n = sgn * Wc R[:,2], q = n . p
+      float nx = (V[0] * R[0][2] + V[4] * R[1][2]) + V[8] * R[2][2];
+      float ny = (V[1] * R[0][2] + V[5] * R[1][2]) + V[9] * R[2][2];
+      float nz = (V[2] * R[0][2] + V[6] * R[1][2]) + V[10] * R[2][2];
+      const float q = (nx * px + ny * py) + nz * pz;
+      float sgn = 1.0f;
+      if (!p.front_only && q > 0.0f) sgn = -1.0f;
+      nx *= sgn; ny *= sgn; nz *= sgn;
+      const float gq = G[G_Q];
+      const float gn[3] = {G[G_NX] + gq * px, G[G_NY] + gq * py, G[G_NZ] + gq * pz};
+      gp[0] += gq * nx;
+      gp[1] += gq * ny;
+      gp[2] += gq * nz;
 #pragma unroll
       for (int b = 0; b < 3; ++b) {
-        const float w0 = V[4 * b + 0], w1 = V[4 * b + 1], w2 = V[4 * b + 2];
-        th0 += w1 * gWc[2][b] - w2 * gWc[1][b];
-        th1 += w2 * gWc[0][b] - w0 * gWc[2][b];
-        th2 += w0 * gWc[1][b] - w1 * gWc[0][b];
+        gR[b][2] += sgn * ((V[4 * b + 0] * gn[0] + V[4 * b + 1] * gn[1]) + V[4 * b + 2] * gn[2]);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) gWc[a][b] += sgn * gn[a] * R[b][2];
       }
-      tau[3] = th0; tau[4] = th1; tau[5] = th2;
+      // depth clamp window zlo = pz - rz, zhi = pz + rz, rz = 3 max(S0, S1)
+      gpz_direct += G[G_ZLO] + G[G_ZHI];
+      const float grz = 3.0f * (G[G_ZHI] - G[G_ZLO]);
+      if (S[0] > S[1]) gS[0] += grz;
+      else if (S[1] > S[0]) gS[1] += grz;
+      else { gS[0] += 0.5f * grz; gS[1] += 0.5f * grz; }
     }
-    dL_dmeans3D[3 * g] = gm[0]; dL_dmeans3D[3 * g + 1] = gm[1]; dL_dmeans3D[3 * g + 2] = gm[2];
-    dL_dmeans2D[3 * g] = g2d[0]; dL_dmeans2D[3 * g + 1] = g2d[1]; dL_dmeans2D[3 * g + 2] = 0.f;
-    dL_dcolors[3 * g] = G[G_R]; dL_dcolors[3 * g + 1] = G[G_G]; dL_dcolors[3 * g + 2] = G[G_B];
-    dL_dopacities[g] = G[G_OPAC];
-    dL_dscales[3 * g] = gs[0]; dL_dscales[3 * g + 1] = gs[1]; dL_dscales[3 * g + 2] = gs[2];
-    dL_drotations[4 * g] = gq4[0]; dL_drotations[4 * g + 1] = gq4[1];
-    dL_drotations[4 * g + 2] = gq4[2]; dL_drotations[4 * g + 3] = gq4[3];
+    gp[2] += gpz_direct;
+    // quaternion
+    gq4[0] = 2.0f * (-qz * gR[0][1] + qy * gR[0][2] + qz * gR[1][0] - qx * gR[1][2] - qy * gR[2][0] + qx * gR[2][1]);
+    gq4[1] = 2.0f * (qy * gR[0][1] + qz * gR[0][2] + qy * gR[1][0] - 2.0f * qx * gR[1][1] - qr * gR[1][2] + qz * gR[2][0] + qr * gR[2][1] - 2.0f * qx * gR[2][2]);
+    gq4[2] = 2.0f * (-2.0f * qy * gR[0][0] + qx * gR[0][1] + qr * gR[0][2] + qx * gR[1][0] + qz * gR[1][2] - qr * gR[2][0] + qz * gR[2][1] - 2.0f * qy * gR[2][2]);
+    gq4[3] = 2.0f * (-2.0f * qz * gR[0][0] - qr * gR[0][1] + qx * gR[0][2] + qr * gR[1][0] - 2.0f * qz * gR[1][1] + qy * gR[1][2] + qx * gR[2][0] + qy * gR[2][1]);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) gs[k] = p.scale_mod * gS[k];
+    // world mean: p = Wc m + t
+#pragma unroll
+    for (int b = 0; b < 3; ++b)
+      gm[b] = (V[4 * b + 0] * gp[0] + V[4 * b + 1] * gp[1]) + V[4 * b + 2] * gp[2];
+    // pose tangent at tau = 0: d rho = gp ; d theta = p x gp + sum_b Wc[:,b] x gWc[:,b]
+    tau[0] = gp[0]; tau[1] = gp[1]; tau[2] = gp[2];
+    float th0 = py * gp[2] - pz * gp[1];
+    float th1 = pz * gp[0] - px * gp[2];
+    float th2 = px * gp[1] - py * gp[0];
+#pragma unroll
+    for (int b = 0; b < 3; ++b) {
+      const float w0 = V[4 * b + 0], w1 = V[4 * b + 1], w2 = V[4 * b + 2];
+      th0 += w1 * gWc[2][b] - w2 * gWc[1][b];
+      th1 += w2 * gWc[0][b] - w0 * gWc[2][b];
+      th2 += w0 * gWc[1][b] - w1 * gWc[0][b];
+    }
+    tau[3] = th0; tau[4] = th1; tau[5] = th2;
   }
+  dL_dmeans3D[3 * g] = gm[0]; dL_dmeans3D[3 * g + 1] = gm[1]; dL_dmeans3D[3 * g + 2] = gm[2];
+  dL_dmeans2D[3 * g] = g2d[0]; dL_dmeans2D[3 * g + 1] = g2d[1]; dL_dmeans2D[3 * g + 2] = 0.f;
+  dL_dcolors[3 * g] = G[G_R]; dL_dcolors[3 * g + 1] = G[G_G]; dL_dcolors[3 * g + 2] = G[G_B];
+  dL_dopacities[g] = G[G_OPAC];
+  dL_dscales[3 * g] = gs[0]; dL_dscales[3 * g + 1] = gs[1]; dL_dscales[3 * g + 2] = gs[2];
+  dL_drotations[4 * g] = gq4[0]; dL_drotations[4 * g + 1] = gq4[1];
+  dL_drotations[4 * g + 2] = gq4[2]; dL_drotations[4 * g + 3] = gq4[3];
+}
 
-  // block reduction of the pose-tangent terms (fixed order -> deterministic)
+// block reduction of the pose-tangent terms (fixed order -> deterministic)
+__device__ inline void store_tau_partial(const float (&tau)[6], float* __restrict__ tau_partials) {
+  __shared__ float sTau[256 / 64][6];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
@@ -979,8 +1017,86 @@ __global__ __launch_bounds__(256, 4) void gaussian_bwd_kernel(
   }
 }
 
-__global__ __launch_bounds__(256) void tau_reduce_kernel(const float* __restrict__ partials, int nblocks,
+// The per-Gaussian chain, two launch plans (pings_raster_backward picks by the blend plan):
+//
+// BY OWNER OF A CHUNK PAIR, behind grad_zero_kernel — for frames in which few Gaussians own a gradient row (footprint
+// class 2: the occlusion bound leaves most survivors without a tile; headline: 951 of 332,253 survivors own one, in
+// 8,925 (Gaussian, chunk) pairs).  One thread per pair q of the chunk scan; the thread of a Gaussian's FIRST pair
+// (pair_off[owner] == q) runs its chain, the others leave.  pair_owner and pair_off are indexed by pair and by depth
+// rank and read coalesced; neither the rectangle nor the rank of a Gaussian is looked up, and a depth rank without a
+// live row costs nothing.  A Gaussian with a loop over n chunk partials is followed by n - 1 idle threads, so the long
+// loops of the nearest Gaussians (up to num_tiles * 4 / CH partials each, neighbours in depth rank) spread over the
+// waves by themselves: a wave never sums more than 64 + the longest loop's partials.  The grid is sized for the host's
+// bound np_max; the number of pairs is a device word and the workgroups behind it leave after one scalar load.  Rows
+// are stored for the Gaussians with a live row only, as scattered single floats.
+// The pose-tangent partial of a workgroup sums the owners among ITS 256 pairs: the grouping depends on the live rows
+// alone, not on how many Gaussians survived culling or what rank they got, so frames that blend the same instances
+// (the tile-rectangle rules, the two depth sorts) sum the pose gradient in the same order.
+constexpr int PART_AHEAD = 8;
+template <int MODE>
+__global__ __launch_bounds__(256, 2) void gaussian_bwd_rank_kernel(
+    BParams p, const float* __restrict__ means3D, const float* __restrict__ scales,
+    const float* __restrict__ rotations, const uint32_t* __restrict__ gidx_sorted,
+    const uint32_t* __restrict__ pair_off, const uint32_t* __restrict__ pair_owner,
+    const float* __restrict__ partials, float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dcolors,
+    float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales,
+    float* __restrict__ dL_drotations, float* __restrict__ tau_partials) {
+  const uint32_t npairs = pair_off[p.P];
+  if (blockIdx.x * 256u >= npairs) return;   // tau_reduce_kernel sums the workgroups in front of this one
+  const uint32_t q = blockIdx.x * 256u + threadIdx.x;
+  float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (q < npairs) {
+    const uint32_t r = pair_owner[q];
+    if (pair_off[r] == q) {
+      float G[16];
+#pragma unroll
+      for (int k = 0; k < 16; ++k) G[k] = 0.f;
+      sum_partials<PART_AHEAD>(partials, q, pair_off[r + 1], G);
+      gaussian_row<MODE>(p, (int)gidx_sorted[r], true, G, means3D, scales, rotations, dL_dmeans3D, dL_dmeans2D,
+                         dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, tau);
+    }
+  }
+  store_tau_partial(tau, tau_partials);
+}
+
+// BY GAUSSIAN INDEX — for frames in which most survivors own a row (small footprints, nothing saturates: C3 has
+// 814,949 survivors of 1M).  Parameters are read and all gradient rows written coalesced, zeros included; only the
+// words that locate the Gaussian's chunk partials go through its depth rank.  (By rank such a frame scatters seventeen
+// floats per Gaussian over six arrays: C3's chain 0.070 -> 0.165 ms, profiles/r15.)
+template <int MODE>
+__global__ __launch_bounds__(256, 4) void gaussian_bwd_index_kernel(
+    BParams p, const float* __restrict__ means3D, const float* __restrict__ scales,
+    const float* __restrict__ rotations, const uint4* __restrict__ rect, const uint32_t* __restrict__ rank_of,
+    const uint32_t* __restrict__ tiles_sorted, const uint32_t* __restrict__ pair_off,
+    const float* __restrict__ partials, float* __restrict__ dL_dmeans3D, float* __restrict__ dL_dmeans2D, float* __restrict__ dL_dcolors,
+    float* __restrict__ dL_dopacities, float* __restrict__ dL_dscales,
+    float* __restrict__ dL_drotations, float* __restrict__ tau_partials) {
+  const int g = blockIdx.x * blockDim.x + threadIdx.x;
+  float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (g < p.P) {
+    uint32_t n_tiles = 0u, qa = 0u, qb = 0u;
+    if (rect[g].w != 0u) {  // survived culling: has a depth rank
+      const uint32_t rank = rank_of[g];
+      n_tiles = tiles_sorted[rank];
+      qa = pair_off[rank];
+      qb = pair_off[rank + 1];
+    }
+    float G[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) G[k] = 0.f;
+    sum_partials<1>(partials, qa, qb, G);
+    gaussian_row<MODE>(p, g, n_tiles > 0 && qb > qa, G, means3D, scales, rotations, dL_dmeans3D, dL_dmeans2D,
+                       dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, tau);
+  }
+  store_tau_partial(tau, tau_partials);
+}
+
+// sums the per-workgroup partials in fp64: of the workgroups that hold a pair (gaussian_bwd_rank_kernel; npairs != nullptr)
+// or of all `nblocks_all` (gaussian_bwd_index_kernel)
+__global__ __launch_bounds__(256) void tau_reduce_kernel(const float* __restrict__ partials,
+                                                          const uint32_t* __restrict__ npairs, int nblocks_all,
                                                           float* __restrict__ dL_dtau) {
+  const int nblocks = npairs ? (int)((*npairs + 255u) / 256u) : nblocks_all;
   __shared__ double sRed[4][6];
   double s[6] = {0, 0, 0, 0, 0, 0};
   for (int i = threadIdx.x; i < nblocks; i += 256) {
@@ -1100,22 +1216,42 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
   }
   {
     pings::prof::Scope ps("row_chunk_sum", st);
-    const size_t groups = bw.np_max;
-    hipLaunchKernelGGL(row_chunk_sum_kernel, dim3((unsigned)pings::ceil_div<size_t>(groups * 16, 256)),
-                       block, 0, st, rr, bw.pair_off, bw.pair_owner, bw.rows, bw.partials);
+    hipLaunchKernelGGL(row_chunk_sum_kernel, dim3(knobs.rowsum_wgs), block, 0, st, rr, bw.pair_off, bw.pair_owner,
+                       bw.rows, bw.partials);
     PINGS_LAUNCH_CHECK();
   }
   const int nblocks = pings::ceil_div(P, 256);
   {
     pings::prof::Scope ps_g("gaussian_bwd", st);
+    // The chain's launch plan follows the blend plan.  The pixel-per-lane backward is the plan of footprint class 2:
+    // large footprints, so the occlusion bound leaves few Gaussians a tile and fewer a live row — zeros are streamed
+    // and the chain runs over the owners of the chunk pairs.  The scan backward is the plan of small footprints, where most
+    // survivors own a row: the chain runs in index order and writes every row itself.
+    const bool by_rank = !plan.bwd_scan;
+    if (by_rank) {
+      GradFill fill;
+      float* const grads[6] = {dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations};
+      const size_t per[6] = {3, 3, 3, 1, 3, 4};
+      for (int a = 0; a < 6; ++a) { fill.ptr[a] = grads[a]; fill.count[a] = per[a] * (size_t)P; }
+      // 17 P floats as 16-byte stores, eight or so to a thread
+      const unsigned fill_grid = (unsigned)std::min<size_t>(2048, pings::ceil_div<size_t>((size_t)P * 17, 4 * 256));
+      hipLaunchKernelGGL(grad_zero_kernel, dim3(fill_grid), block, 0, st, fill);
+      PINGS_LAUNCH_CHECK();
+    }
     with_mode(s->mode, [&](auto m) {
-      hipLaunchKernelGGL(gaussian_bwd_kernel<m()>, dim3(nblocks), block, 0, st, bp, means3D,
-                         scales, rotations, gs.rect, gs.rank_of, gs.tiles_sorted, bw.pair_off, bw.partials,
-                         dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales,
-                         dL_drotations, bw.tau_partials);
+      if (by_rank)
+        hipLaunchKernelGGL(gaussian_bwd_rank_kernel<m()>, dim3((unsigned)pings::ceil_div<size_t>(bw.np_max, 256)), block,
+                           0, st, bp, means3D, scales, rotations, gs.gidx_sorted, bw.pair_off, bw.pair_owner,
+                           bw.partials, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations,
+                           bw.tau_partials);
+      else
+        hipLaunchKernelGGL(gaussian_bwd_index_kernel<m()>, dim3(nblocks), block, 0, st, bp, means3D, scales, rotations,
+                           gs.rect, gs.rank_of, gs.tiles_sorted, bw.pair_off, bw.partials, dL_dmeans3D, dL_dmeans2D,
+                           dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, bw.tau_partials);
     });
     PINGS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(tau_reduce_kernel, dim3(1), block, 0, st, bw.tau_partials, nblocks, dL_dtau);
+    hipLaunchKernelGGL(tau_reduce_kernel, dim3(1), block, 0, st, bw.tau_partials,
+                       by_rank ? (const uint32_t*)(bw.pair_off + P) : (const uint32_t*)nullptr, nblocks, dL_dtau);
     PINGS_LAUNCH_CHECK();
   }
   return PINGS_OK;

@@ -270,21 +270,6 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
   }
 }
 
-// Depth ranks -> lanes.  The nearest Gaussians cover the most tiles and sit at neighbouring ranks: dealt out in rank
-// order they would all land in the first waves.  The first quarter of the ranks is therefore dealt round-robin,
-// one rank per wave at a time (lane l < 16 of wave w: rank l num_waves + w); behind it the footprints are small and
-// even, and ranks go out in runs of 16 (quarter q >= 1 of wave w: ranks 16 (q num_waves + w) .. + 15), so that the
-// per-rank loads and stores are 64-byte segments instead of one memory transaction per lane.  (Runs of 16 from rank
-// 0 on: Metric-1's duplicate pass 0.054 -> 0.168 ms — sixteen screen-filling footprints in one wave; C3 0.078 ->
-// 0.037 ms either way.)
-__device__ inline int strided_rank(int P) {
-  const int num_waves = (int)(gridDim.x * (blockDim.x >> 6));
-  const int wave = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
-  const int lane = (int)(threadIdx.x & 63);
-  const int r = lane < 16 ? lane * num_waves + wave : ((lane >> 4) * num_waves + wave) * 16 + (lane & 15);
-  return r < P ? r : -1;
-}
-
 constexpr int SMALL_RECT = 8;
 constexpr int STAT_SHARDS = 256;
 

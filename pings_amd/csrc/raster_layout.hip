@@ -138,7 +138,7 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
   b.pair_off = c.take<uint32_t>(np + 1);
   b.pair_owner = c.take<uint32_t>(b.np_max);
   b.partials = c.take<float>(b.np_max * GRAD_ROW);
-  b.tau_partials = c.take<float>((size_t)ceil_div((int)np, 256) * 6);
+  b.tau_partials = c.take<float>(ceil_div<size_t>(std::max(np, b.np_max), 256) * 6);   // per workgroup of the chain: over P or over the pairs
   b.temp_bytes = std::max(raster_scan_bytes((int64_t)ni + 1), raster_scan_bytes((int64_t)np + 1));
   b.temp = c.take<char>(b.temp_bytes);
   b.rows = c.take<float>(n * GRAD_ROW);
@@ -170,6 +170,8 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
 //   PINGS_RASTER_RECT       tight | 3(sigma) | e(llipse)  bench, tests  tile-rectangle rule of preprocess_kernel, by first letter
 //   PINGS_MARK_VISIBLE      frustum | d(epth)         tests         first letter d: mark_visible tests depth only, the variant in which
 //                                                                   upstream's frustum test stays commented out (assumption 2)
+//   PINGS_ROWSUM_WGS        2048 | n                  tests         workgroups of row_chunk_sum_kernel, which stride over the (Gaussian,
+//                                                                   chunk) pairs, 1 .. 65535 (1: one workgroup walks them all)
 RasterKnobs read_knobs() {
   RasterKnobs k;   // the defaults: raster_common.hpp
   if (const char* e = getenv("PINGS_BLEND_PPL")) k.blend_ppl = atoi(e);
@@ -200,6 +202,7 @@ RasterKnobs read_knobs() {
   if (const char* e = getenv("PINGS_OCC_WALK")) k.occ_walk_lanes = e[0] == 'l';
   if (const char* e = getenv("PINGS_RASTER_RECT")) k.rect_rule = e[0] == '3' ? RECT_3SIGMA : e[0] == 'e' ? RECT_ELLIPSE : RECT_TIGHT;
   if (const char* e = getenv("PINGS_MARK_VISIBLE")) k.mark_depth_only = e[0] == 'd';
+  if (const char* e = getenv("PINGS_ROWSUM_WGS")) k.rowsum_wgs = (unsigned)std::min(std::max(atoi(e), 1), 65535);
   return k;
 }
 
