@@ -1412,4 +1412,64 @@ PINGS_API int pings_loop_context_distance(const float* sc1, const float* sc2, in
 PINGS_API int pings_loop_read_record(const int32_t* record_dev, const float* win_tran_dev, int32_t* record_host,
                                      void* stream);
 
+/* ------------------------------------------------------------- LiDAR frame front-end
+ * What dataset/slam_dataset.py:584-621 (`filter_and_correct`), utils/tools.py:1088-1177 (`deskewing`, `slerp_pose`),
+ * :1242-1351 (`project_points_to_cam_torch`) and gaussian_splatting/utils/cameras.py:233-243 (`set_depth_img`) compute,
+ * on caller-owned buffers (no state is kept here).  A point cloud is fp32 rows of `stride` floats whose first three are
+ * x, y, z.  Bitwise deterministic: the only atomic is an integer maximum.  No entry waits for the device.
+ *
+ * pings_lidar_crop: mask[i] = min_range < dist < max_range && min_z < z < max_z, all strict, in fp32 with the four
+ *   thresholds rounded to fp32 once; dist = sqrt(x^2 + y^2 [+ z^2 unless on_xy_plane]).  A NaN row gives 0.
+ * pings_lidar_deskew: in place on x, y, z.  s_i = (ts_i - min ts) / (max ts - min ts) - ts_ref_pose in fp64, rounded to
+ *   fp32 (ts [n] fp32 or fp64; max == min gives NaN coordinates).  pose: DEVICE [4,4] row-major (fp32 or fp64),
+ *   T_last<-cur = (R, t); with (a, theta) the axis and angle of R, theta in [0, pi], R(s) is the rotation by s theta about
+ *   a (the shortest-arc slerp from the identity, any real s; theta == 0 gives the identity exactly) and
+ *   p_i <- R(s_i) p_i + s_i t.  Axis and angle are formed in fp64 by the first wave of each workgroup, the per-point
+ *   Rodrigues formula runs in fp32.  num_other > 0 is the multi-LiDAR branch: lidar_idx[n] (int32 or int64) names the
+ *   LiDAR of a row; 0 takes the formula above, k in [1, num_other] takes T = T_l_lm[k-1] (HOST [num_other,16] row-major
+ *   fp64, last row 0 0 0 1), pose_k = T pose T^-1, s = s_i + ts_diff[k-1] (HOST, nullable) and
+ *   p <- T^-1 (R_k(s) (T p) + s t_k); any other index leaves the row alone.  num_other <= PINGS_LIDAR_MAX_LIDARS.
+ *   Two launches: per-workgroup (min, max) partials into `scratch` (pings_lidar_deskew_scratch_bytes()), then the apply
+ *   launch, which reduces them.  n == 0 is an argument error (the reference's torch.min raises).
+ * pings_lidar_slerp_pose: out[4,4] = [R(s), s t; 0 1] of pose (s = ts - ts_ref_pose, formed by the caller), its rigid
+ *   inverse with `invert`, and left-multiplied by `left` (DEVICE [4,4], nullable) after that; fp64 arithmetic, rounded
+ *   once to out's type.  One 64-lane launch.
+ * pings_lidar_project: every point into every camera in one launch.  Per camera c (K: DEVICE [3,3], T: DEVICE >= 12
+ *   floats, rows 0..2 of T_c_l, both fp32 row-major): P = R p + t, q = K P, d = q_z (d == 0 becomes -1e-6),
+ *   u = rint(q_x / |d|), v = rint(q_y / |d|) (half to even; -0 is pixel 0); the point is visible iff 0 <= u < W,
+ *   0 <= v < H, d > min_depth, d < max_depth (false for non-finite values).  A visible point raises keys[v W + u]
+ *   (uint32; the caller zero-fills it once per frame, all cameras in one buffer) to ~bits(d): since d > min_depth >= 0
+ *   the largest key is the smallest depth and 0 means no hit.  The point takes image[:, v, u] of the LAST camera that
+ *   sees it: rgb[i rgb_stride + 0..2], 0 to indicator[i indicator_stride] (nullable).  A point no camera sees gets -1 in
+ *   all of them with `init`, and is left alone without.  visible[i] (nullable) = seen by any camera.  rgb may point into
+ *   the cloud's own colour columns.  ncam <= PINGS_LIDAR_MAX_CAMS; l0..l3 and src are not read.
+ * pings_lidar_depth_pyramid: per camera, level 0 = keys decoded (0 for no hit), or `src` [H,W] when keys is NULL; level
+ *   k = 1..3 [H >> k, W >> k] takes level-0 pixel (2^k i + 2^k - 1, 2^k j + 2^k - 1), which is three chained
+ *   F.interpolate(scale_factor=0.5, mode='nearest-exact').  Each of l0..l3 is nullable.  One launch for all cameras. */
+#define PINGS_LIDAR_MAX_CAMS 8
+#define PINGS_LIDAR_MAX_LIDARS 8
+typedef struct pings_lidar_cam {
+  const float* image;          /* [3,H,W] */
+  const float* K;              /* DEVICE [3,3] */
+  const float* T;              /* DEVICE [4,4] T_c_l (12 floats read) */
+  uint32_t* keys;              /* [H*W] depth keys */
+  const float* src;            /* [H,W]: the pyramid's source when keys is NULL */
+  float *l0, *l1, *l2, *l3;    /* pyramid levels */
+  int32_t H, W;
+} pings_lidar_cam;
+PINGS_API int pings_lidar_crop(const float* points, int64_t n, int64_t stride, double min_z, double max_z,
+                               double min_range, double max_range, int32_t on_xy_plane, uint8_t* mask, void* stream);
+PINGS_API size_t pings_lidar_deskew_scratch_bytes(void);
+PINGS_API int pings_lidar_deskew(float* points, int64_t n, int64_t stride, const void* ts, int32_t ts_is_f64,
+                                 const void* pose, int32_t pose_is_f64, double ts_ref_pose, const void* lidar_idx,
+                                 int32_t lidar_idx_is_i64, int32_t num_other, const double* T_l_lm,
+                                 const double* ts_diff, void* scratch, void* stream);
+PINGS_API int pings_lidar_slerp_pose(const void* pose, int32_t pose_is_f64, double s, const void* left,
+                                     int32_t left_is_f64, int32_t invert, void* out, int32_t out_is_f64, void* stream);
+PINGS_API int pings_lidar_project(const float* points, int64_t n, int64_t stride, const pings_lidar_cam* cams,
+                                  int32_t ncam, double min_depth, double max_depth, float* rgb, int64_t rgb_stride,
+                                  float* indicator, int64_t indicator_stride, uint8_t* visible, int32_t init,
+                                  void* stream);
+PINGS_API int pings_lidar_depth_pyramid(const pings_lidar_cam* cams, int32_t ncam, void* stream);
+
 #endif /* PINGS_HIP_H_ */

@@ -21,6 +21,7 @@ EVAL_VIEW_RECORD, EVAL_PAIR_RECORD = 9, 12                        # PINGS_EVAL_*
 EVAL_EXTENT = 1                                                   # PINGS_EVAL_EXTENT: status bit of the eval grids
 LOOP_MAX_R, LOOP_MAX_S, LOOP_MAX_D = 32, 128, 16                  # PINGS_LOOP_MAX_*: limits of the pings_loop_* entries
 LOOP_MAX_Q, LOOP_MAX_C = 16, 65536                                # poses / queries per call, candidates per search
+LIDAR_MAX_CAMS, LIDAR_MAX_LIDARS = 8, 8                           # PINGS_LIDAR_MAX_*: cameras per launch, other LiDARs
 
 vp = C.c_void_p     # device pointers and the hipStream_t travel as integers (tensor.data_ptr())
 i32, i64, f32, f64, sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
@@ -167,6 +168,11 @@ class PoolSelectArgs(C.Structure):
                [("thr", C.c_double)] + \
                [(n, vp) for n in ("pose", "coord", "sdf_label", "color", "normal", "scratch", "out_points", "out_color",
                                   "out_normal")]
+
+
+class LidarCam(C.Structure):
+    _fields_ = [(n, vp) for n in ("image", "K", "T", "keys", "src", "l0", "l1", "l2", "l3")] + \
+               [("H", C.c_int32), ("W", C.c_int32)]
 
 
 # ---------------------------------------------------------------- entry points: {name: (restype, argtypes)}
@@ -381,4 +387,12 @@ SIGNATURES = {
     "pings_loop_search": (i32, [vp, vp, i64, vp, i32, vp, vp, i32, i32, i32, i32, i32, f64, vp, vp, vp, vp]),
     "pings_loop_context_distance": (i32, [vp, vp, i32, i32, i32, vp, vp]),
     "pings_loop_read_record": (i32, [vp, vp, vp, vp]),
+    # LiDAR frame front-end
+    "pings_lidar_crop": (i32, [vp, i64, i64, f64, f64, f64, f64, i32, vp, vp]),
+    "pings_lidar_deskew_scratch_bytes": (sz, []),
+    "pings_lidar_deskew": (i32, [vp, i64, i64, vp, i32, vp, i32, f64, vp, i32, i32, C.POINTER(f64), C.POINTER(f64), vp,
+                                 vp]),
+    "pings_lidar_slerp_pose": (i32, [vp, i32, f64, vp, i32, i32, vp, i32, vp]),
+    "pings_lidar_project": (i32, [vp, i64, i64, C.POINTER(LidarCam), i32, f64, f64, vp, i64, vp, i64, vp, i32, vp]),
+    "pings_lidar_depth_pyramid": (i32, [C.POINTER(LidarCam), i32, vp]),
 }
