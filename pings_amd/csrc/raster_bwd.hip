@@ -16,8 +16,9 @@
 //                         (Gaussian, chunk of <= 64 rows) pair, lane = column, streaming 64-B rows.
 //   gaussian_bwd_*_kernel per Gaussian: adds its chunk partials, then chains through conic / EWA projection /
 //                         quaternion / scale / camera transform to the input gradients and the pose-tangent terms
-//                         (block-reduced, fixed order).  _rank_: over the depth ranks that own a pair, behind grad_zero_kernel (few
-//                         Gaussians own a row); _index_: in index order, rows located through the depth rank (most do).
+//                         (block-reduced, fixed order).  _rank_: over the depth ranks that own a pair, behind the zero
+//                         fill of the blend launch's trailing workgroups (few Gaussians own a row); _index_: in index
+//                         order, rows located through the depth rank (most do).
 //   tau_reduce_kernel     final fixed-order reduction of the pose-tangent partials.  (Run by the last workgroup of
 //                         the chain kernel instead, behind a device-scope fence and a ticket, it saved the launch
 //                         and cost 640 us: the release writes back the L2 of the workgroup's XCD, once per workgroup,
@@ -311,10 +312,41 @@ __device__ __forceinline__ void blend_bwd_tile_body(
   }
 }
 
+// Zeros for the six per-Gaussian gradient arrays (why they start at zero: the per-Gaussian chain, below).  One workgroup
+// writes slice `part` of `nparts`: 16-byte stores, no reads; an array's unaligned head and its tail go out as single
+// floats.  The stores are nontemporal: nobody reads the zeros soon, and as ordinary stores at the end of the blend
+// launch the 68 P bytes pushed the gradient rows out of the cache in front of row_chunk_sum_kernel, which reads them
+// next (headline: 9.8 -> 12.5 - 14.3 us; nontemporal 9.8 - 10.2 us, profiles/r16).
+struct GradFill {
+  float* ptr[6];
+  size_t count[6];   // floats
+};
+typedef float v4f __attribute__((ext_vector_type(4)));
+__device__ inline void grad_fill_part(const GradFill& f, uint32_t part, uint32_t nparts) {
+  const size_t tid = (size_t)part * blockDim.x + threadIdx.x, nthreads = (size_t)nparts * blockDim.x;
+#pragma unroll
+  for (int a = 0; a < 6; ++a) {
+    float* const p = f.ptr[a];
+    const size_t n = f.count[a];
+    const size_t head = min(n, (size_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2);
+    const size_t nvec = (n - head) >> 2;
+    v4f* const body = reinterpret_cast<v4f*>(p + head);
+    for (size_t i = tid; i < nvec; i += nthreads) __builtin_nontemporal_store(v4f{0.f, 0.f, 0.f, 0.f}, body + i);
+    const size_t tail = head + 4 * nvec;   // fewer than four floats each: the first threads take them
+    if (tid < head) p[tid] = 0.f;
+    if (tid < n - tail) p[tail + tid] = 0.f;
+  }
+}
+
 // The kernel is its body inlined (as blend_fwd_wave_kernel is blend_fwd_wave_body).  With the body written straight
 // into the __global__ function the compiler handles `p` differently (kernel argument, not a by-value copy), and the
 // record loop came out with other operand orders and a slightly different schedule: 0.306 -> 0.311 ms on the Metric-1
 // cloud in one A/B, at the edge of the run-to-run spread.  This form compiles to the same instructions as before.
+//
+// The workgroups behind the last tile (blockIdx.x >= num_tiles; none when the grid is num_tiles) write the zeros of
+// the six per-Gaussian gradient arrays and leave: workgroups are dispatched in order, so they start when the last
+// tile waves have started and the longest-first schedule begins to free wave slots, and their stores go out beside
+// the tail of the tile waves instead of in a launch of their own.  No tile wave runs an instruction more.
 template <int MODE>
 __global__ __launch_bounds__(64, 3) void blend_bwd_tile_kernel(
     BParams p, const uint2* __restrict__ ranges, const uint32_t* __restrict__ point_list,
@@ -322,7 +354,11 @@ __global__ __launch_bounds__(64, 3) void blend_bwd_tile_kernel(
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ out_depth, const float* __restrict__ dL_dcolor,
     const float* __restrict__ dL_dnormal, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha,
     const float* __restrict__ inst_w, const uint32_t* __restrict__ cidx, float* __restrict__ rows,
-    const uint32_t* __restrict__ tile_order) {
+    const uint32_t* __restrict__ tile_order, uint32_t num_tiles, GradFill fill) {
+  if (blockIdx.x >= num_tiles) {
+    grad_fill_part(fill, blockIdx.x - num_tiles, gridDim.x - num_tiles);
+    return;
+  }
   blend_bwd_tile_body<MODE>(p, ranges, point_list, rec, gval, final_T, n_contrib, out_depth, dL_dcolor, dL_dnormal,
                             dL_ddepth, dL_dalpha, inst_w, cidx, rows, tile_order);
 }
@@ -767,26 +803,9 @@ __global__ __launch_bounds__(256) void row_chunk_sum_kernel(RowRanges rr, const 
 // ---------------------------------------------------------------- per-Gaussian chain
 // The six gradient arrays start at zero: all but a few per cent of the Gaussians own no live row (culled, or no tile
 // kept behind the occlusion bound, or never blended), and gaussian_bwd_rank_kernel only visits the depth ranks that do.
-// 16-byte stores, no reads; an array's unaligned head and its tail go out as single floats.
-struct GradFill {
-  float* ptr[6];
-  size_t count[6];   // floats
-};
-__global__ __launch_bounds__(256) void grad_zero_kernel(GradFill f) {
-  const size_t tid = (size_t)blockIdx.x * 256u + threadIdx.x, nthreads = (size_t)gridDim.x * 256u;
-#pragma unroll
-  for (int a = 0; a < 6; ++a) {
-    float* const p = f.ptr[a];
-    const size_t n = f.count[a];
-    const size_t head = min(n, (size_t)((16u - (uint32_t)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u) >> 2);
-    const size_t nvec = (n - head) >> 2;
-    float4* const body = reinterpret_cast<float4*>(p + head);
-    for (size_t i = tid; i < nvec; i += nthreads) body[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-    const size_t tail = head + 4 * nvec;   // fewer than four floats each: the first threads take them
-    if (tid < head) p[tid] = 0.f;
-    if (tid < n - tail) p[tail + tid] = 0.f;
-  }
-}
+// The zeros ride in the blend-backward launch when there is one (grad_fill_part, in front of blend_bwd_tile_kernel);
+// a frame without instances has no blend launch and runs this kernel (as does PINGS_GRAD_FILL=l).
+__global__ __launch_bounds__(256) void grad_zero_kernel(GradFill f) { grad_fill_part(f, blockIdx.x, gridDim.x); }
 
 // G += the chunk partials [qa, qb) of one Gaussian, in ascending order; AHEAD rows are loaded before their adds (the
 // adds keep their order, so the sums keep their bits)
@@ -1019,8 +1038,8 @@ __device__ inline void store_tau_partial(const float (&tau)[6], float* __restric
 
 // The per-Gaussian chain, two launch plans (pings_raster_backward picks by the blend plan):
 //
-// BY OWNER OF A CHUNK PAIR, behind grad_zero_kernel — for frames in which few Gaussians own a gradient row (footprint
-// class 2: the occlusion bound leaves most survivors without a tile; headline: 951 of 332,253 survivors own one, in
+// BY OWNER OF A CHUNK PAIR, behind the zero fill (grad_fill_part) — for frames in which few Gaussians own a gradient row
+// (footprint class 2: the occlusion bound leaves most survivors without a tile; headline: 951 of 332,253 survivors own one, in
 // 8,925 (Gaussian, chunk) pairs).  One thread per pair q of the chunk scan; the thread of a Gaussian's FIRST pair
 // (pair_off[owner] == q) runs its chain, the others leave.  pair_owner and pair_off are indexed by pair and by depth
 // rank and read coalesced; neither the rectangle nor the rank of a Gaussian is looked up, and a depth rank without a
@@ -1032,8 +1051,62 @@ __device__ inline void store_tau_partial(const float (&tau)[6], float* __restric
 // The pose-tangent partial of a workgroup sums the owners among ITS 256 pairs: the grouping depends on the live rows
 // alone, not on how many Gaussians survived culling or what rank they got, so frames that blend the same instances
 // (the tile-rectangle rules, the two depth sorts) sum the pose gradient in the same order.
+//
+// G, the sum of an owner's chunk partials [pair_off[r], pair_off[r + 1]), is formed BY 16-LANE GROUPS (GROUP_SUM): the
+// owners among the workgroup's 256 pairs are dealt round-robin to its sixteen groups, lane c of a group adds component
+// c of the partials in ascending order, GROUP_AHEAD rows in flight, each row one coalesced 64-byte request; the sums
+// go to LDS at the owner's slot and the owner thread takes them from there.  A lane alone (sum_partials, the other
+// instance: PINGS_CHAIN_SUM=l) fetches a row as four 16-byte loads of its own and keeps PART_AHEAD rows in flight: the
+// 123 partials of the headline's nearest Gaussians were sixteen dependent round trips of one lane while its wave and
+// most of the GPU waited.  Either way a component is 0 + p[qa] + p[qa + 1] + ... in this order: the same bits.  A loop
+// that runs past the workgroup's last pair is summed whole by its group; nothing is taken from another workgroup.
 constexpr int PART_AHEAD = 8;
-template <int MODE>
+constexpr int GROUP_AHEAD = 16;
+constexpr int G_PITCH = 17;   // floats per owner slot of sG: the owners' 16 reads fall into different banks
+// q: the thread's pair; owner: it is the first pair of a Gaussian, whose partials end at qb
+__device__ inline void sum_partials_by_group(const float* __restrict__ partials, uint32_t q, bool owner, uint32_t qb,
+                                             float (&G)[16]) {
+  __shared__ float sG[256 * G_PITCH];
+  __shared__ uint32_t sSlot[256], sEnd[256];   // the workgroup's owners, compacted: thread, end of its partials
+  __shared__ uint32_t sCount[256 / 64];
+  const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+  const unsigned long long owners = __ballot(owner);
+  if (lane == 0) sCount[wave] = (uint32_t)__popcll(owners);
+  __syncthreads();
+  uint32_t at = (uint32_t)__popcll(owners & ((1ull << lane) - 1ull)), n_owners = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < 256 / 64; ++w) {
+    if (w < wave) at += sCount[w];
+    n_owners += sCount[w];
+  }
+  if (owner) {
+    sSlot[at] = t;
+    sEnd[at] = qb;
+  }
+  __syncthreads();
+  const uint32_t c = t & 15u, q0 = q - t;
+  for (uint32_t o = t >> 4; o < n_owners; o += 256 / 16) {
+    const uint32_t slot = sSlot[o], end = sEnd[o];
+    float acc = 0.f;
+    for (uint32_t k = q0 + slot; k < end; k += GROUP_AHEAD) {
+      float ld[GROUP_AHEAD];
+#pragma unroll
+      for (int u = 0; u < GROUP_AHEAD; ++u)
+        if (k + u < end) ld[u] = partials[(size_t)(k + u) * 16 + c];
+#pragma unroll
+      for (int u = 0; u < GROUP_AHEAD; ++u)
+        if (k + u < end) acc += ld[u];
+    }
+    sG[slot * G_PITCH + c] = acc;
+  }
+  __syncthreads();
+  if (owner) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) G[k] = sG[t * G_PITCH + k];
+  }
+}
+
+template <int MODE, bool GROUP_SUM>
 __global__ __launch_bounds__(256, 2) void gaussian_bwd_rank_kernel(
     BParams p, const float* __restrict__ means3D, const float* __restrict__ scales,
     const float* __restrict__ rotations, const uint32_t* __restrict__ gidx_sorted,
@@ -1045,16 +1118,17 @@ __global__ __launch_bounds__(256, 2) void gaussian_bwd_rank_kernel(
   if (blockIdx.x * 256u >= npairs) return;   // tau_reduce_kernel sums the workgroups in front of this one
   const uint32_t q = blockIdx.x * 256u + threadIdx.x;
   float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (q < npairs) {
-    const uint32_t r = pair_owner[q];
-    if (pair_off[r] == q) {
-      float G[16];
+  const uint32_t r = q < npairs ? pair_owner[q] : 0u;
+  const bool owner = q < npairs && pair_off[r] == q;
+  float G[16];
 #pragma unroll
-      for (int k = 0; k < 16; ++k) G[k] = 0.f;
-      sum_partials<PART_AHEAD>(partials, q, pair_off[r + 1], G);
-      gaussian_row<MODE>(p, (int)gidx_sorted[r], true, G, means3D, scales, rotations, dL_dmeans3D, dL_dmeans2D,
-                         dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, tau);
-    }
+  for (int k = 0; k < 16; ++k) G[k] = 0.f;
+  const uint32_t qb = owner ? pair_off[r + 1] : 0u;
+  if (GROUP_SUM) sum_partials_by_group(partials, q, owner, qb, G);
+  if (owner) {
+    if (!GROUP_SUM) sum_partials<PART_AHEAD>(partials, q, qb, G);
+    gaussian_row<MODE>(p, (int)gidx_sorted[r], true, G, means3D, scales, rotations, dL_dmeans3D, dL_dmeans2D,
+                       dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, tau);
   }
   store_tau_partial(tau, tau_partials);
 }
@@ -1193,6 +1267,17 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
     if (int e = raster_scan_chunks(rr, bw.pair_off, bw.pair_owner, bw.temp, bw.temp_bytes, knobs.library_scan, st))
       return e;
   }
+  // The pixel-per-lane backward is followed by the chain over the owners of the chunk pairs, which stores the rows of
+  // the Gaussians with a live row only: the rest is zeros (68 P bytes), written by trailing workgroups of the blend
+  // launch or, without a blend launch, by grad_zero_kernel.
+  const bool by_rank = !plan.bwd_scan;
+  GradFill fill;
+  {
+    float* const grads[6] = {dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations};
+    const size_t per[6] = {3, 3, 3, 1, 3, 4};
+    for (int a = 0; a < 6; ++a) { fill.ptr[a] = grads[a]; fill.count[a] = per[a] * (size_t)P; }
+  }
+  const bool fill_in_blend = by_rank && I > 0 && knobs.grad_fill_wgs > 0;
   if (I > 0) {
     pings::prof::Scope ps("blend_bwd", st);
     const uint32_t* order = bs.tile_order + num_tiles;
@@ -1207,9 +1292,11 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
                            bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor, dL_dnormal,
                            dL_ddepth, dL_dalpha, bs.inst_qmask, bw.cidx, bw.rows, order, n_long);
       } else {
-        hipLaunchKernelGGL((blend_bwd_tile_kernel<M>), dim3(num_tiles), dim3(64), 0, st, bp, bs.ranges,
-                           bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor,
-                           dL_dnormal, dL_ddepth, dL_dalpha, bs.inst_w, bw.cidx, bw.rows, order);
+        const unsigned fill_wgs = fill_in_blend ? knobs.grad_fill_wgs : 0u;
+        hipLaunchKernelGGL((blend_bwd_tile_kernel<M>), dim3((unsigned)num_tiles + fill_wgs), dim3(64), 0, st, bp,
+                           bs.ranges, bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor,
+                           dL_dnormal, dL_ddepth, dL_dalpha, bs.inst_w, bw.cidx, bw.rows, order, (uint32_t)num_tiles,
+                           fill);
       }
     });
     PINGS_LAUNCH_CHECK();
@@ -1227,24 +1314,20 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
     // large footprints, so the occlusion bound leaves few Gaussians a tile and fewer a live row — zeros are streamed
     // and the chain runs over the owners of the chunk pairs.  The scan backward is the plan of small footprints, where most
     // survivors own a row: the chain runs in index order and writes every row itself.
-    const bool by_rank = !plan.bwd_scan;
-    if (by_rank) {
-      GradFill fill;
-      float* const grads[6] = {dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations};
-      const size_t per[6] = {3, 3, 3, 1, 3, 4};
-      for (int a = 0; a < 6; ++a) { fill.ptr[a] = grads[a]; fill.count[a] = per[a] * (size_t)P; }
+    if (by_rank && !fill_in_blend) {
       // 17 P floats as 16-byte stores, eight or so to a thread
       const unsigned fill_grid = (unsigned)std::min<size_t>(2048, pings::ceil_div<size_t>((size_t)P * 17, 4 * 256));
       hipLaunchKernelGGL(grad_zero_kernel, dim3(fill_grid), block, 0, st, fill);
       PINGS_LAUNCH_CHECK();
     }
     with_mode(s->mode, [&](auto m) {
-      if (by_rank)
-        hipLaunchKernelGGL(gaussian_bwd_rank_kernel<m()>, dim3((unsigned)pings::ceil_div<size_t>(bw.np_max, 256)), block,
+      if (by_rank) {
+        const auto chain = knobs.chain_sum_lanes ? gaussian_bwd_rank_kernel<m(), false> : gaussian_bwd_rank_kernel<m(), true>;
+        hipLaunchKernelGGL(chain, dim3((unsigned)pings::ceil_div<size_t>(bw.np_max, 256)), block,
                            0, st, bp, means3D, scales, rotations, gs.gidx_sorted, bw.pair_off, bw.pair_owner,
                            bw.partials, dL_dmeans3D, dL_dmeans2D, dL_dcolors, dL_dopacities, dL_dscales, dL_drotations,
                            bw.tau_partials);
-      else
+      } else
         hipLaunchKernelGGL(gaussian_bwd_index_kernel<m()>, dim3(nblocks), block, 0, st, bp, means3D, scales, rotations,
                            gs.rect, gs.rank_of, gs.tiles_sorted, bw.pair_off, bw.partials, dL_dmeans3D, dL_dmeans2D,
                            dL_dcolors, dL_dopacities, dL_dscales, dL_drotations, bw.tau_partials);

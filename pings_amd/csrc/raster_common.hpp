@@ -218,6 +218,8 @@ struct RasterKnobs {
   int rect_rule = RECT_TIGHT;    // PINGS_RASTER_RECT
   bool mark_depth_only = false;  // PINGS_MARK_VISIBLE
   unsigned rowsum_wgs = 2048u;   // PINGS_ROWSUM_WGS
+  unsigned grad_fill_wgs = 512u; // PINGS_GRAD_FILL: fill workgroups behind the blend backward's tiles (0 = own launch)
+  bool chain_sum_lanes = false;  // PINGS_CHAIN_SUM
 };
 RasterKnobs read_knobs();
 

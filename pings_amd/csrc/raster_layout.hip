@@ -172,6 +172,11 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
 //                                                                   upstream's frustum test stays commented out (assumption 2)
 //   PINGS_ROWSUM_WGS        2048 | n                  tests         workgroups of row_chunk_sum_kernel, which stride over the (Gaussian,
 //                                                                   chunk) pairs, 1 .. 65535 (1: one workgroup walks them all)
+//   PINGS_GRAD_FILL         512 | n | l(aunch)        tests, A/B    zeros of the six gradient arrays behind the pixel-per-lane backward: n
+//                                                                   workgroups behind the tiles of its launch, 1 .. 65535; first letter l:
+//                                                                   grad_zero_kernel, a launch of its own (always when there is no instance)
+//   PINGS_CHAIN_SUM         group | l(anes)           tests, A/B    first letter l: gaussian_bwd_rank_kernel sums an owner's chunk partials
+//                                                                   in the owner's lane instead of by 16-lane groups; same bits
 RasterKnobs read_knobs() {
   RasterKnobs k;   // the defaults: raster_common.hpp
   if (const char* e = getenv("PINGS_BLEND_PPL")) k.blend_ppl = atoi(e);
@@ -203,6 +208,8 @@ RasterKnobs read_knobs() {
   if (const char* e = getenv("PINGS_RASTER_RECT")) k.rect_rule = e[0] == '3' ? RECT_3SIGMA : e[0] == 'e' ? RECT_ELLIPSE : RECT_TIGHT;
   if (const char* e = getenv("PINGS_MARK_VISIBLE")) k.mark_depth_only = e[0] == 'd';
   if (const char* e = getenv("PINGS_ROWSUM_WGS")) k.rowsum_wgs = (unsigned)std::min(std::max(atoi(e), 1), 65535);
+  if (const char* e = getenv("PINGS_GRAD_FILL")) k.grad_fill_wgs = e[0] == 'l' ? 0u : (unsigned)std::min(std::max(atoi(e), 1), 65535);
+  if (const char* e = getenv("PINGS_CHAIN_SUM")) k.chain_sum_lanes = e[0] == 'l';
   return k;
 }
 

@@ -261,6 +261,8 @@ class _RasterizeGaussians(torch.autograd.Function):
         ctx.opac_shape = opacities.shape
         ctx.has_pose = (theta is not None, rho is not None)
         ctx.mark_non_differentiable(radii, per_g)
+        # backward gets None for an output nobody used (and for radii / per_g) instead of a zero tensor autograd fills
+        ctx.set_materialize_grads(False)
         # The state object (not save_for_backward) keeps the output tensors: the 3DGS caller
         # divides the returned depth in place (gaussian_renderer/__init__.py:430), which a saved
         # tensor's version check would reject; the 3DGS backward never reads that depth, and the
@@ -288,10 +290,12 @@ class _RasterizeGaussians(torch.autograd.Function):
         P, I = fs.P, fs.I
         f32 = dict(dtype=torch.float32, device=dev)
 
-        def gc(g):
-            return None if g is None else g.detach().to(torch.float32).contiguous()
+        def gc(g, out):
+            return torch.zeros_like(out) if g is None else g.detach().to(torch.float32).contiguous()
 
-        g_color, g_normal, g_depth, g_alpha = gc(g_color), gc(g_normal), gc(g_depth), gc(g_alpha)
+        g_color, g_depth, g_alpha = gc(g_color, fs.color), gc(g_depth, fs.depth), gc(g_alpha, fs.alpha)
+        if prep.mode == MODE_SURFEL:
+            g_normal = gc(g_normal, fs.normal)
         scratch = torch.empty(L.pings_raster_backward_bytes(P, I), dtype=torch.uint8, device=dev)
         d_means3D = torch.empty(P, 3, **f32)
         d_means2D = torch.empty(P, 3, **f32)
@@ -309,8 +313,9 @@ class _RasterizeGaussians(torch.autograd.Function):
             _lib.ptr(d_colors), _lib.ptr(d_opac), _lib.ptr(d_scales), _lib.ptr(d_rot), _lib.ptr(d_tau),
             fs.fclass, _lib.stream_ptr(dev))
         _lib.check(st, "pings_raster_backward")
-        d_theta = d_tau[3:].clone() if ctx.has_pose[0] else None
-        d_rho = d_tau[:3].clone() if ctx.has_pose[1] else None
+        # views of the six floats tau_reduce_kernel wrote
+        d_theta = d_tau[3:] if ctx.has_pose[0] else None
+        d_rho = d_tau[:3] if ctx.has_pose[1] else None
         return (d_means3D, d_means2D, d_colors, d_opac.reshape(ctx.opac_shape), d_scales, d_rot,
                 d_theta, d_rho, None)
 
