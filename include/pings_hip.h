@@ -1057,6 +1057,49 @@ PINGS_API int pings_mc_emit(const float* vol, const uint8_t* mask, int64_t nx, i
                             int flags, const void* scratch, int64_t nv, int64_t nf, int64_t* keys, float* verts,
                             int64_t* faces, void* stream);
 
+/* ------------------------------------------------------ mesh finishing (csrc/mesh.hip)
+ * What utils/mesher.py:500-530 does with Open3D after marching cubes, by the rules of DESIGN §2.7b.  verts fp32
+ * [V, 3], faces int64 [F, 3]; indices are 32-bit inside the kernels, so V >= 2^31 or 3F >= 2^31 is status 1, not a
+ * launch.  Every entry takes a scratch buffer of its `_scratch_bytes` (0 for a bad shape) and no output aliases an
+ * input.  A face corner outside [0, V) never indexes memory: the entries with a host read return status 1 after it.
+ * Integer atomics only; every output is the same bits on every run.
+ *   weld      remove_duplicated_vertices.  Two vertices are the same iff their three coordinates compare equal
+ *             (-0 == +0; a vertex with a non-finite coordinate equals nothing).  The kept vertex of a group is its first
+ *             occurrence, kept vertices keep their order, faces are remapped and none is removed.  verts_out [V, 3] and
+ *             kept [V] (the old index of every new vertex) are filled up to *n_out (HOST, the one read);
+ *             remap [V]: new index of every old vertex; faces_out [F, 3] (F may be 0).
+ *   clusters  cluster_connected_triangles.  Each face has the undirected edges (min, max) of its corner pairs, (a, a)
+ *             included; faces that share an edge key are connected, faces that share only a vertex are not.  A cluster's
+ *             id is the rank of its smallest face index among all clusters' smallest face indices.  labels [F],
+ *             counts [F] filled up to the number of clusters, which goes to *n_clusters (HOST) when that is not NULL;
+ *             with NULL there is no host read and the number stays in the scratch for drop_small.
+ *   drop_small  remove_triangles_by_mask: keeps face f iff counts[labels[f]] >= min_tri, in order, into faces_out
+ *             [F, 3].  `scratch` is the one the clusters call on the same faces used.  totals[2] (HOST, one read):
+ *             clusters, kept faces.
+ *   vertex_normals  compute_vertex_normals(normalized=True): per vertex the sum, in ascending face index and then
+ *             corner order, of the unnormalised (v1 - v0) x (v2 - v0) of every corner that names it, divided by its
+ *             length; (0, 0, 1) where the sum is zero or not finite.  fp32, no host read; a face with a corner outside
+ *             [0, V) contributes nothing.
+ *   compact_vertices  drops the vertices no face names (not in the reference).  verts_out, kept as in weld;
+ *             remap [V] is -1 for a dropped vertex.  *n_out (HOST, one read). */
+PINGS_API size_t pings_mesh_weld_scratch_bytes(int64_t V, int64_t F);
+PINGS_API int pings_mesh_weld(const float* verts, int64_t V, const int64_t* faces, int64_t F, void* scratch,
+                              float* verts_out, int64_t* faces_out, int64_t* remap, int64_t* kept, int64_t* n_out,
+                              void* stream);
+PINGS_API size_t pings_mesh_clusters_scratch_bytes(int64_t F);
+PINGS_API int pings_mesh_clusters(const int64_t* faces, int64_t F, int64_t V, void* scratch, int64_t* labels,
+                                  int64_t* counts, int64_t* n_clusters, void* stream);
+PINGS_API size_t pings_mesh_drop_small_scratch_bytes(int64_t F);
+PINGS_API int pings_mesh_drop_small(const int64_t* faces, int64_t F, const int64_t* labels, const int64_t* counts,
+                                    int64_t min_tri, void* scratch, int64_t* faces_out, int64_t* totals, void* stream);
+PINGS_API size_t pings_mesh_vertex_normals_scratch_bytes(int64_t V, int64_t F);
+PINGS_API int pings_mesh_vertex_normals(const float* verts, int64_t V, const int64_t* faces, int64_t F, void* scratch,
+                                        float* normals, void* stream);
+PINGS_API size_t pings_mesh_compact_vertices_scratch_bytes(int64_t V, int64_t F);
+PINGS_API int pings_mesh_compact_vertices(const float* verts, int64_t V, const int64_t* faces, int64_t F,
+                                          void* scratch, float* verts_out, int64_t* faces_out, int64_t* remap,
+                                          int64_t* kept, int64_t* n_out, void* stream);
+
 /* ------------------------------------------------------ fused AdamW (csrc/optim.hip)
  * One optimiser step of every tensor of every parameter group in ONE launch.  A job is one fp32
  * tensor; its scalars are computed by the host in double and rounded to fp32 once, as torch's single-tensor AdamW

@@ -338,6 +338,17 @@ SIGNATURES = {
     "pings_mc_scratch_bytes": (sz, [i64, i64, i64]),
     "pings_mc_count": (i32, [vp, vp, i64, i64, i64, f32, i32, vp, C.POINTER(i64), vp]),
     "pings_mc_emit": (i32, [vp, vp, i64, i64, i64, f32, i32, vp, i64, i64, vp, vp, vp, vp]),
+    # mesh finishing
+    "pings_mesh_weld_scratch_bytes": (sz, [i64, i64]),
+    "pings_mesh_weld": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64), vp]),
+    "pings_mesh_clusters_scratch_bytes": (sz, [i64]),
+    "pings_mesh_clusters": (i32, [vp, i64, i64, vp, vp, vp, C.POINTER(i64), vp]),
+    "pings_mesh_drop_small_scratch_bytes": (sz, [i64]),
+    "pings_mesh_drop_small": (i32, [vp, i64, vp, vp, i64, vp, vp, C.POINTER(i64), vp]),
+    "pings_mesh_vertex_normals_scratch_bytes": (sz, [i64, i64]),
+    "pings_mesh_vertex_normals": (i32, [vp, i64, vp, i64, vp, vp, vp]),
+    "pings_mesh_compact_vertices_scratch_bytes": (sz, [i64, i64]),
+    "pings_mesh_compact_vertices": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64), vp]),
     # fused AdamW
     "pings_adamw_step": (i32, [C.POINTER(AdamwJob), i32, C.POINTER(i32), vp]),
     # view evaluation

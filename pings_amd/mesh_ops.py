@@ -1,0 +1,293 @@
+"""Mesh finishing on the HIP device: what `Mesher.recon_aabb_collections_mesh` (utils/mesher.py:480-530, :583-636) does
+with Open3D after marching cubes — concatenate the chunks, `remove_duplicated_vertices`, drop the connected clusters
+below `config.min_cluster_vertices` triangles, `compute_vertex_normals`, `global_transform`, write the `.ply` — without
+Open3D.  Kernels: csrc/mesh.hip; rules: DESIGN §2.7b, restated in numpy by tests/mesh_ref.py.
+
+Every primitive takes and returns device tensors (verts fp32 [V, 3], faces int64 [F, 3]); a CPU tensor raises
+`PingsHipError`.  Empty inputs give empty outputs with no launch.  Host reads are recorded with `_lib.note_sync`."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import NamedTuple, Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+
+
+class Mesh(NamedTuple):
+    verts: torch.Tensor                   # [V, 3] fp32
+    faces: torch.Tensor                   # [F, 3] int64
+    normals: Optional[torch.Tensor]       # [V, 3] fp32 or None
+    colors: Optional[torch.Tensor]        # [V, C] or None
+
+
+def _check(verts, faces, what):
+    for t in (verts, faces):
+        if t is not None and not t.is_cuda:
+            raise _lib.PingsHipError(f"{what} runs on the HIP device only (got a CPU tensor); there is no CPU fallback")
+    if verts is not None and (verts.dim() != 2 or verts.shape[1] != 3):
+        raise ValueError(f"{what}: verts must be [V, 3], got shape {tuple(verts.shape)}")
+    if faces.dim() != 2 or faces.shape[1] != 3:
+        raise ValueError(f"{what}: faces must be [F, 3], got shape {tuple(faces.shape)}")
+    if faces.dtype != torch.int64:
+        raise ValueError(f"{what}: faces must be int64, got {faces.dtype}")
+    v = None if verts is None else verts.detach().to(torch.float32).contiguous()
+    return v, faces.detach().contiguous()
+
+
+def _scratch(nbytes, dev, what):
+    if nbytes == 0:
+        raise _lib.PingsHipError(f"{what}: the mesh is too large for 32-bit indices")
+    return torch.empty(nbytes, dtype=torch.uint8, device=dev)
+
+
+def _no_vertices(faces, what):
+    if faces.shape[0]:
+        raise _lib.PingsHipError(f"{what}: faces name vertices of an empty vertex array")
+
+
+def _weld(verts, faces):
+    """-> (verts, faces, remap, kept): kept[j] is the old index of new vertex j (its group's first occurrence)."""
+    verts, faces = _check(verts, faces, "weld")
+    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    if V == 0:
+        _no_vertices(faces, "weld")
+        z = torch.zeros(0, dtype=torch.int64, device=dev)
+        return verts, faces, z, z
+    L = _lib.lib()
+    scratch = _scratch(L.pings_mesh_weld_scratch_bytes(V, F), dev, "weld")
+    vout = torch.empty(V, 3, device=dev)
+    fout = torch.empty(F, 3, dtype=torch.int64, device=dev)
+    remap = torch.empty(V, dtype=torch.int64, device=dev)
+    kept = torch.empty(V, dtype=torch.int64, device=dev)
+    n = C.c_int64(0)
+    _lib.note_sync("mesh_weld")
+    _lib.check(L.pings_mesh_weld(_lib.ptr(verts), V, _lib.ptr(faces) if F else None, F, _lib.ptr(scratch), _lib.ptr(vout),
+                                 _lib.ptr(fout) if F else None, _lib.ptr(remap), _lib.ptr(kept), C.byref(n),
+                                 _lib.stream_ptr(dev)), "pings_mesh_weld")
+    return vout[:n.value], fout, remap, kept[:n.value]
+
+
+def weld(verts, faces):
+    """`remove_duplicated_vertices`: vertices whose three fp32 coordinates compare equal become one (-0 == +0; a vertex
+    with a non-finite coordinate equals nothing), the first occurrence is kept, kept vertices keep their order, faces
+    are remapped and none is removed.  -> (verts, faces, remap [V_in] int64).  One host read."""
+    v, f, remap, _ = _weld(verts, faces)
+    return v, f, remap
+
+
+def _clusters(faces, n_verts, read):
+    dev, F = faces.device, faces.shape[0]
+    L = _lib.lib()
+    scratch = _scratch(L.pings_mesh_clusters_scratch_bytes(F), dev, "cluster_triangles")
+    labels = torch.empty(F, dtype=torch.int64, device=dev)
+    counts = torch.empty(F, dtype=torch.int64, device=dev)
+    k = C.c_int64(0)
+    if read:
+        _lib.note_sync("mesh_clusters")
+    _lib.check(L.pings_mesh_clusters(_lib.ptr(faces), F, int(n_verts), _lib.ptr(scratch), _lib.ptr(labels),
+                                     _lib.ptr(counts), C.byref(k) if read else None, _lib.stream_ptr(dev)),
+               "pings_mesh_clusters")
+    return scratch, labels, counts, k.value
+
+
+def cluster_triangles(faces, n_verts):
+    """`cluster_connected_triangles`: faces that share an undirected edge (min, max) are connected, faces that share
+    only a vertex are not; a cluster's id is the rank of its smallest face index.  -> (labels [F], counts [K]) int64.
+    One host read (K)."""
+    _, faces = _check(None, faces, "cluster_triangles")
+    if faces.shape[0] == 0:
+        z = torch.zeros(0, dtype=torch.int64, device=faces.device)
+        return z, z
+    if n_verts <= 0:
+        _no_vertices(faces, "cluster_triangles")
+    _, labels, counts, k = _clusters(faces, n_verts, True)
+    return labels, counts[:k]
+
+
+def drop_small_clusters(faces, n_verts, min_tri):
+    """`filter_isolated_vertices` (mesher.py:625-636): keeps face f iff its cluster has at least `min_tri` faces, in
+    order.  Vertices are untouched.  One host read (clusters and kept faces together)."""
+    _, faces = _check(None, faces, "drop_small_clusters")
+    F, dev = faces.shape[0], faces.device
+    if F == 0:
+        return faces
+    if n_verts <= 0:
+        _no_vertices(faces, "drop_small_clusters")
+    scratch, labels, counts, _ = _clusters(faces, n_verts, False)
+    L = _lib.lib()
+    out = torch.empty(F, 3, dtype=torch.int64, device=dev)
+    tot = (C.c_int64 * 2)(0, 0)
+    _lib.note_sync("mesh_drop_small")
+    _lib.check(L.pings_mesh_drop_small(_lib.ptr(faces), F, _lib.ptr(labels), _lib.ptr(counts), int(min_tri),
+                                       _lib.ptr(scratch), _lib.ptr(out), tot, _lib.stream_ptr(dev)),
+               "pings_mesh_drop_small")
+    return out[:int(tot[1])]
+
+
+def vertex_normals(verts, faces):
+    """`compute_vertex_normals(normalized=True)`: per vertex the sum, in ascending face and then corner order, of the
+    unnormalised (v1 - v0) x (v2 - v0) of the corners that name it, normalised; (0, 0, 1) where the sum is zero or not
+    finite.  fp32, no host read, so a face that names a vertex outside [0, V) is no error here: it contributes nothing."""
+    verts, faces = _check(verts, faces, "vertex_normals")
+    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    out = torch.empty(V, 3, device=dev)
+    if V == 0:
+        return out
+    L = _lib.lib()
+    scratch = _scratch(L.pings_mesh_vertex_normals_scratch_bytes(V, F), dev, "vertex_normals")
+    _lib.check(L.pings_mesh_vertex_normals(_lib.ptr(verts), V, _lib.ptr(faces) if F else None, F, _lib.ptr(scratch),
+                                           _lib.ptr(out), _lib.stream_ptr(dev)), "pings_mesh_vertex_normals")
+    return out
+
+
+def compact_vertices(verts, faces, *attrs):
+    """Drops the vertices no face names (the reference never does); kept vertices keep their order, per-vertex `attrs`
+    ([V, ...] device tensors, None passed through) follow.  -> (verts, faces, *attrs).  One host read."""
+    verts, faces = _check(verts, faces, "compact_vertices")
+    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    for a in attrs:
+        if a is not None and (not a.is_cuda or a.shape[0] != V):
+            raise ValueError("compact_vertices: every attribute is a device tensor with one row per vertex")
+    if V == 0:
+        _no_vertices(faces, "compact_vertices")
+        return (verts, faces, *attrs)
+    L = _lib.lib()
+    scratch = _scratch(L.pings_mesh_compact_vertices_scratch_bytes(V, F), dev, "compact_vertices")
+    vout = torch.empty(V, 3, device=dev)
+    fout = torch.empty(F, 3, dtype=torch.int64, device=dev)
+    remap = torch.empty(V, dtype=torch.int64, device=dev)
+    kept = torch.empty(V, dtype=torch.int64, device=dev)
+    n = C.c_int64(0)
+    _lib.note_sync("mesh_compact_vertices")
+    _lib.check(L.pings_mesh_compact_vertices(_lib.ptr(verts), V, _lib.ptr(faces) if F else None, F, _lib.ptr(scratch),
+                                             _lib.ptr(vout), _lib.ptr(fout) if F else None, _lib.ptr(remap),
+                                             _lib.ptr(kept), C.byref(n), _lib.stream_ptr(dev)),
+               "pings_mesh_compact_vertices")
+    kept = kept[:n.value]
+    return (vout[:n.value], fout, *(None if a is None else a.index_select(0, kept) for a in attrs))
+
+
+def finish_mesh(parts, min_tri=0, normals=True, colors=None, transform=None, compact=False) -> Mesh:
+    """The reference's order (mesher.py:500-523): concatenate `parts` (a list of device (verts, faces) pairs) with face
+    offsets, weld, drop the clusters below `min_tri` faces when `min_tri > 0`, (with `compact`, an extension, drop the
+    unreferenced vertices,) vertex normals, then the optional 4x4 `transform`: vertices in fp64 and rounded once, normals
+    times its 3x3 block, as Open3D's `transform` does.  `colors` [sum V, C] follows the weld by first occurrence.
+    Two host reads at most, three with `compact`."""
+    parts = [(v, f) for v, f in parts]
+    dev = next((v.device for v, _ in parts), torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available()
+               else torch.device("cpu"))
+    empty = Mesh(torch.zeros(0, 3, device=dev), torch.zeros(0, 3, dtype=torch.int64, device=dev),
+                 torch.zeros(0, 3, device=dev) if normals else None,
+                 None if colors is None else colors[:0])
+    checked, off = [], 0
+    for v, f in parts:
+        v, f = _check(v, f, "finish_mesh")
+        checked.append((v, f + off if off else f))
+        off += v.shape[0]
+    if colors is not None and (not colors.is_cuda or colors.shape[0] != off):
+        raise ValueError("finish_mesh: colors is a device tensor with one row per input vertex")
+    if off == 0 or sum(f.shape[0] for _, f in checked) == 0:
+        return empty
+    verts = torch.cat([v for v, _ in checked])
+    faces = torch.cat([f for _, f in checked])
+    verts, faces, _, kept = _weld(verts, faces)
+    if colors is not None:
+        colors = colors.index_select(0, kept)
+    if min_tri > 0:
+        faces = drop_small_clusters(faces, verts.shape[0], min_tri)
+    if compact:
+        verts, faces, colors = compact_vertices(verts, faces, colors)
+    nrm = vertex_normals(verts, faces) if normals else None
+    if transform is not None:
+        T = torch.as_tensor(np.asarray(transform, dtype=np.float64).reshape(4, 4)).to(dev)
+        # elementwise, left to right (no library matmul): every product and sum is one fp64 rounding, the same anywhere
+        rot = lambda x: x[:, 0:1] * T[:3, 0] + x[:, 1:2] * T[:3, 1] + x[:, 2:3] * T[:3, 2]
+        verts = (rot(verts.double()) + T[:3, 3]).float()
+        if nrm is not None:
+            nrm = rot(nrm.double()).float()
+    return Mesh(verts, faces, nrm, colors)
+
+
+def recon_mesh(mesher, aabbs, voxel_size, query_locally=False, estimate_color=False, mesh_normal=True,
+               filter_isolated_mesh=False, mesh_min_nn=10, mesh_path=None):
+    """`Mesher.recon_aabb_collections_mesh` without Open3D: `mesher_ops.mesh_bbx` per box (chunks past the point cap
+    are skipped), vertex colours per chunk before the weld with `estimate_color`, `finish_mesh` with
+    config.min_cluster_vertices and the mesher's global_transform (skipped when it is the identity), `write_ply` when
+    `mesh_path` is given.  The semantic branch (`estimate_sem`) is not offered.  -> Mesh, or None without boxes."""
+    from . import mesher_ops as MO
+
+    if aabbs is None:
+        return None
+    cfg = mesher.config
+    parts, cols = [], []
+    for bbx in aabbs:
+        bmin, bmax = (bbx.get_min_bound(), bbx.get_max_bound()) if hasattr(bbx, "get_min_bound") else bbx
+        chunk = MO.mesh_bbx(mesher, bmin, bmax, voxel_size, query_locally, mesh_min_nn)
+        if chunk is None:
+            continue
+        parts.append(chunk)
+        if estimate_color:
+            _, _, c, _ = MO._query_device(mesher, chunk[0], cfg.infer_bs, False, False, True, False, query_locally)
+            if getattr(cfg, "color_channel", 3) == 1:
+                c = (c * 2.0).repeat(1, 3)       # mesher.py estimate_vertices_color: np.repeat(color_pred * 2.0, 3, axis=1)
+            cols.append(c)
+    T = np.asarray(getattr(mesher, "global_transform", np.eye(4)), dtype=np.float64)
+    mesh = finish_mesh(parts, min_tri=cfg.min_cluster_vertices if filter_isolated_mesh else 0, normals=mesh_normal,
+                       colors=torch.cat(cols) if cols else None,
+                       transform=None if np.array_equal(T, np.eye(4)) else T)
+    if mesh_path is not None:
+        write_ply(mesh_path, mesh.verts, mesh.faces, mesh.normals, mesh.colors)
+    return mesh
+
+
+def write_ply(path, verts, faces, normals=None, colors=None) -> None:
+    """Binary little-endian PLY with the properties Open3D's writer emits, so the reference's tools read it back:
+    double x y z, double nx ny nz when given, uchar red green blue when given (the colour clamped to [0, 1], times 255,
+    rounded), list uchar uint vertex_indices.  Host code: one copy of each tensor to the host."""
+    host = lambda t: t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+    v = host(verts).astype("<f8").reshape(-1, 3)
+    f = host(faces).reshape(-1, 3)
+    fields = [("x", "<f8"), ("y", "<f8"), ("z", "<f8")]
+    head = ["ply", "format binary_little_endian 1.0", "comment Created by pings_amd", f"element vertex {len(v)}",
+            "property double x", "property double y", "property double z"]
+    if normals is not None:
+        fields += [("nx", "<f8"), ("ny", "<f8"), ("nz", "<f8")]
+        head += ["property double nx", "property double ny", "property double nz"]
+    if colors is not None:
+        fields += [("red", "u1"), ("green", "u1"), ("blue", "u1")]
+        head += ["property uchar red", "property uchar green", "property uchar blue"]
+    head += [f"element face {len(f)}", "property list uchar uint vertex_indices", "end_header"]
+    rec = np.empty(len(v), dtype=fields)
+    rec["x"], rec["y"], rec["z"] = v[:, 0], v[:, 1], v[:, 2]
+    if normals is not None:
+        n = host(normals).astype("<f8").reshape(-1, 3)
+        rec["nx"], rec["ny"], rec["nz"] = n[:, 0], n[:, 1], n[:, 2]
+    if colors is not None:
+        c = host(colors).astype(np.float64).reshape(len(v), -1)
+        if c.shape[1] != 3:
+            raise ValueError(f"write_ply: colours must be [V, 3], got {c.shape}")
+        c = np.rint(np.clip(c, 0.0, 1.0) * 255.0).astype(np.uint8)
+        rec["red"], rec["green"], rec["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    tri = np.empty(len(f), dtype=[("n", "u1"), ("i", "<u4", (3,))])
+    tri["n"], tri["i"] = 3, f
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(head) + "\n").encode("ascii"))
+        fh.write(rec.tobytes())
+        fh.write(tri.tobytes())
+
+
+def to_open3d(mesh: Mesh):
+    """A legacy `open3d.geometry.TriangleMesh` of `mesh` (what the reference's callers expect back).  Open3D is imported
+    here and nowhere else; it is not installed where this package is tested, so this function is untested."""
+    import open3d as o3d
+
+    m = o3d.geometry.TriangleMesh(o3d.utility.Vector3dVector(mesh.verts.cpu().numpy().astype(np.float64)),
+                                  o3d.utility.Vector3iVector(mesh.faces.cpu().numpy().astype(np.int32)))
+    if mesh.normals is not None:
+        m.vertex_normals = o3d.utility.Vector3dVector(mesh.normals.cpu().numpy().astype(np.float64))
+    if mesh.colors is not None:
+        m.vertex_colors = o3d.utility.Vector3dVector(mesh.colors.cpu().numpy().astype(np.float64))
+    return m

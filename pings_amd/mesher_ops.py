@@ -216,10 +216,42 @@ def mesh_bbx(self, bbx_min, bbx_max, voxel_size, query_locally=False, mesh_min_n
     return torch.tensor(origin, dtype=torch.float32, device=coord.device) + verts * voxel_size, faces
 
 
-def install(mesher_module, mc: bool = False) -> None:
+def recon_mesh(self, aabbs, voxel_size, **kw):
+    """`Mesher.recon_mesh`: `mesh_ops.recon_mesh`, the finished mesh as device tensors."""
+    from . import mesh_ops
+
+    return mesh_ops.recon_mesh(self, aabbs, voxel_size, **kw)
+
+
+def _finished(original):
+    def recon_aabb_collections_mesh(self, aabbs, voxel_size, mesh_path=None, query_locally=False, estimate_sem=False,
+                                    estimate_color=False, mesh_normal=True, filter_isolated_mesh=False,
+                                    filter_free_space_vertices=True, mesh_min_nn=10, use_torch_mc=False):
+        from . import mesh_ops
+
+        if estimate_sem:         # colours by label and deletes free-space vertices: stays the reference's
+            return original(self, aabbs, voxel_size, mesh_path, query_locally, estimate_sem, estimate_color, mesh_normal,
+                            filter_isolated_mesh, filter_free_space_vertices, mesh_min_nn, use_torch_mc)
+        mesh = mesh_ops.recon_mesh(self, aabbs, voxel_size, query_locally=query_locally, estimate_color=estimate_color,
+                                   mesh_normal=mesh_normal, filter_isolated_mesh=filter_isolated_mesh,
+                                   mesh_min_nn=mesh_min_nn, mesh_path=mesh_path)
+        return None if mesh is None else mesh_ops.to_open3d(mesh)
+
+    recon_aabb_collections_mesh._pings_original = original
+    return recon_aabb_collections_mesh
+
+
+def install(mesher_module, mc: bool = False, finish: bool = False) -> None:
     """`import utils.mesher as M; install(M)`: Mesher.query_points -> one fused kernel launch per batch.  With mc=True
-    also Mesher.mc_mesh and Mesher.mc_mesh_torch -> marching cubes on the device (csrc/mc.hip)."""
+    also Mesher.mc_mesh and Mesher.mc_mesh_torch -> marching cubes on the device (csrc/mc.hip).  With finish=True also
+    Mesher.recon_aabb_collections_mesh -> `mesh_ops.recon_mesh` (csrc/mesh.hip) returned through `mesh_ops.to_open3d`
+    (the saved original with `estimate_sem`), and a new Mesher.recon_mesh for callers that want the device tensors."""
     mesher_module.Mesher.query_points = query_points
     if mc:
         mesher_module.Mesher.mc_mesh = mc_mesh
         mesher_module.Mesher.mc_mesh_torch = mc_mesh_torch
+    if finish:
+        current = getattr(mesher_module.Mesher, "recon_aabb_collections_mesh", None)
+        original = getattr(current, "_pings_original", current)
+        mesher_module.Mesher.recon_aabb_collections_mesh = _finished(original)
+        mesher_module.Mesher.recon_mesh = recon_mesh
