@@ -1515,4 +1515,62 @@ PINGS_API int pings_lidar_project(const float* points, int64_t n, int64_t stride
                                   void* stream);
 PINGS_API int pings_lidar_depth_pyramid(const pings_lidar_cam* cams, int32_t ncam, void* stream);
 
+/* ------------------------------------------------------ sparse TSDF fusion (csrc/tsdf.hip)
+ * Depth views fused into blocks of PINGS_TSDF_BLOCK^3 voxels, the route of SLAMDataset.o3d_tsdf_fusion.  Grid point g
+ * lies at origin + voxel_length * g, block b = floor(g / 8) has the key (bx + 2^20) << 42 | (by + 2^20) << 21 |
+ * (bz + 2^20).  The caller owns everything:
+ *   table   tkeys [tsize] int64 (-1 = free), tslots [tsize] int32 (-1 = no slot yet), tstamps [tsize] int32 (0 = never
+ *           touched); tsize a power of two in [64, 2^31), at least twice the blocks it will ever hold
+ *   store   block_keys [capacity] int64, tsdf / weight [capacity, 512] fp32, color [capacity, 3, 512] fp32 or NULL;
+ *           voxel (lx, ly, lz) of a block at (lx*8 + ly)*8 + lz.  A block's slot never changes.
+ * intrinsic (HOST) = fx, fy, cx, cy; extrinsic / cam_to_world (HOST) = the first three rows of the world -> camera 4x4
+ * and of its inverse, row-major; origin (HOST) 3 doubles.  All are rounded to fp32 once.  A depth d is valid iff it is
+ * finite and depth_min < d < depth_trunc.  2 sdf_trunc <= 8 voxel_length, else status 1.
+ *   touch    every valid pixel with u % stride == v % stride == 0 names the blocks whose index lies per axis in
+ *            [floor((q - trunc - origin) / (8 voxel)), floor((q + trunc - origin) / (8 voxel))], q its world point;
+ *            absent keys are inserted (slot -1).  touched [list_cap] int32 receives the table entry of every block
+ *            named in this frame once (`frame` >= 1, larger in every call), new_keys [list_cap] the keys without a
+ *            slot, both in no particular order; list_cap >= 8 ceil(width / stride) ceil(height / stride).  counters [4]
+ *            int32 DEVICE workspace; totals[3] (HOST, the frame's one read): touched, new, status bits
+ *            (PINGS_TSDF_EXTENT: a block index outside [-2^20, 2^20) was dropped; PINGS_TSDF_TABLE_FULL).
+ *   assign   sorts new_keys ascending and gives key r the slot base_slot + r: table, block_keys, and the block's
+ *            fields set to tsdf 1, weight 0, colour 0.  scratch of pings_tsdf_assign_scratch_bytes(n_new).
+ *   update   one workgroup per entry of touched: for each voxel p_c = R p + t, skipped unless z > 0;
+ *            iu = floor(fx x / z + cx + 0.5), iv likewise, skipped outside the image or on an invalid depth d;
+ *            sdf = (d - z) sqrt(1 + ((iu - cx) / fx)^2 + ((iv - cy) / fy)^2), skipped unless sdf > -sdf_trunc;
+ *            tsdf <- (tsdf w + min(1, sdf / sdf_trunc)) / (w + 1), colour likewise from image [3, H, W], w <- w + 1.
+ *   table_insert  files block_keys[0 .. nb) with their slots in a cleared table (after the table has grown).
+ *   densify  the box lo + [0, nx) x [0, ny) x [0, nz) of grid points (lo HOST, 3 int64) as out_tsdf, out_weight
+ *            (nullable) [nx, ny, nz] and out_color (nullable) [nx, ny, nz, 3]; a voxel of an absent block reads
+ *            tsdf 1, weight 0, colour 0; out_tsdf is +inf where weight < min_weight (min_weight <= 0: nowhere).
+ *   vertices  keys[nv] of pings_mc_emit on such a box -> verts [nv, 3] = origin + voxel_length (g0 + t axis) with
+ *            t = v0 / (v0 - v1) of the edge's two values (slot 0: the point g0), in fp64 and rounded once; colors
+ *            [nv, 3] = c0 + t (c1 - c0) of col [nx, ny, nz, 3] clamped to [0, 1] (both NULL without colour). */
+#define PINGS_TSDF_BLOCK 8
+#define PINGS_TSDF_EXTENT 1
+#define PINGS_TSDF_TABLE_FULL 2
+PINGS_API int pings_tsdf_table_insert(const int64_t* block_keys, int64_t nb, int64_t* tkeys, int32_t* tslots,
+                                      int64_t tsize, int32_t* status, void* stream);
+PINGS_API int pings_tsdf_touch(const float* depth, int height, int width, const double* intrinsic,
+                               const double* cam_to_world, const double* origin, double voxel_length, double sdf_trunc,
+                               float depth_min, float depth_trunc, int stride, int frame, int64_t* tkeys,
+                               const int32_t* tslots, int32_t* tstamps, int64_t tsize, int64_t list_cap,
+                               int32_t* touched, int64_t* new_keys, int32_t* counters, int64_t* totals, void* stream);
+PINGS_API size_t pings_tsdf_assign_scratch_bytes(int64_t n_new);
+PINGS_API int pings_tsdf_assign(const int64_t* new_keys, int64_t n_new, int64_t base_slot, int64_t capacity,
+                                void* scratch, const int64_t* tkeys, int32_t* tslots, int64_t tsize,
+                                int64_t* block_keys, float* tsdf, float* weight, float* color, void* stream);
+PINGS_API int pings_tsdf_update(const float* depth, const float* image, int height, int width, const double* intrinsic,
+                                const double* extrinsic, const double* origin, double voxel_length, double sdf_trunc,
+                                float depth_min, float depth_trunc, const int32_t* touched, int64_t n_touched,
+                                const int64_t* tkeys, const int32_t* tslots, int64_t tsize, int64_t capacity, float* tsdf,
+                                float* weight, float* color, void* stream);
+PINGS_API int pings_tsdf_densify(const int64_t* tkeys, const int32_t* tslots, int64_t tsize, int64_t capacity,
+                                 const float* tsdf, const float* weight, const float* color, const int64_t* lo,
+                                 int64_t nx, int64_t ny, int64_t nz, float min_weight, float* out_tsdf,
+                                 float* out_weight, float* out_color, void* stream);
+PINGS_API int pings_tsdf_vertices(const int64_t* keys, int64_t nv, const float* vol, const float* col, const int64_t* lo,
+                                  int64_t nx, int64_t ny, int64_t nz, const double* origin, double voxel_length,
+                                  float* verts, float* colors, void* stream);
+
 #endif /* PINGS_HIP_H_ */

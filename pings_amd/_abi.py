@@ -22,6 +22,8 @@ EVAL_EXTENT = 1                                                   # PINGS_EVAL_E
 LOOP_MAX_R, LOOP_MAX_S, LOOP_MAX_D = 32, 128, 16                  # PINGS_LOOP_MAX_*: limits of the pings_loop_* entries
 LOOP_MAX_Q, LOOP_MAX_C = 16, 65536                                # poses / queries per call, candidates per search
 LIDAR_MAX_CAMS, LIDAR_MAX_LIDARS = 8, 8                           # PINGS_LIDAR_MAX_*: cameras per launch, other LiDARs
+TSDF_BLOCK = 8                                                    # PINGS_TSDF_BLOCK: voxels per block edge
+TSDF_EXTENT, TSDF_TABLE_FULL = 1, 2                               # PINGS_TSDF_*: status bits of pings_tsdf_touch
 
 vp = C.c_void_p     # device pointers and the hipStream_t travel as integers (tensor.data_ptr())
 i32, i64, f32, f64, sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
@@ -406,4 +408,14 @@ SIGNATURES = {
     "pings_lidar_slerp_pose": (i32, [vp, i32, f64, vp, i32, i32, vp, i32, vp]),
     "pings_lidar_project": (i32, [vp, i64, i64, C.POINTER(LidarCam), i32, f64, f64, vp, i64, vp, i64, vp, i32, vp]),
     "pings_lidar_depth_pyramid": (i32, [C.POINTER(LidarCam), i32, vp]),
+    # sparse TSDF fusion
+    "pings_tsdf_table_insert": (i32, [vp, i64, vp, vp, i64, vp, vp]),
+    "pings_tsdf_touch": (i32, [vp, i32, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), f64, f64, f32, f32, i32, i32,
+                               vp, vp, vp, i64, i64, vp, vp, vp, C.POINTER(i64), vp]),
+    "pings_tsdf_assign_scratch_bytes": (sz, [i64]),
+    "pings_tsdf_assign": (i32, [vp, i64, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp]),
+    "pings_tsdf_update": (i32, [vp, vp, i32, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), f64, f64, f32, f32, vp,
+                                i64, vp, vp, i64, i64, vp, vp, vp, vp]),
+    "pings_tsdf_densify": (i32, [vp, vp, i64, i64, vp, vp, vp, C.POINTER(i64), i64, i64, i64, f32, vp, vp, vp, vp]),
+    "pings_tsdf_vertices": (i32, [vp, i64, vp, vp, C.POINTER(i64), i64, i64, i64, C.POINTER(f64), f64, vp, vp, vp]),
 }
