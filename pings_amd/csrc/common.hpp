@@ -18,6 +18,24 @@ __host__ __device__ constexpr T ceil_div(T a, T b) { return (a + b - 1) / b; }
 
 constexpr int kWave = 64;  // gfx950 wavefront
 
+inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
+
+// Bump allocator over a caller-owned scratch blob: every field starts on a 256-byte boundary.  With base == nullptr it
+// only measures, so one carve function gives both the exported size (carve(nullptr, ...).total) and the placement.
+// take reserves what it is asked for: a field that must not be empty is asked for with `n > 0 ? n : 1`.
+struct Carver {
+  char* base;
+  size_t off = 0;
+  explicit Carver(void* p) : base(static_cast<char*>(p)) {}
+  template <class T>
+  T* take(size_t count) {
+    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
+    off += align_up(count * sizeof(T));
+    return p;
+  }
+  size_t total() const { return off; }
+};
+
 // Stream-ordered read of up to 8 device words (32 bit each) into host memory WITHOUT a blocking wait inside the HIP
 // runtime: one wave copies the words into pinned, device-mapped host memory behind everything already queued on `st` and
 // the host polls a sequence number (abi.hip).  A blocking hipStreamSynchronize wakes through an interrupt, which on one

@@ -12,15 +12,15 @@
 // Every count that a later stage needs stays on the device (`*_dev` arguments: the live length of a buffer whose
 // capacity the host knows), so a whole eval_pair call reads one record.  No entry point here allocates, copies or waits.
 // Everything is integer / gather / stream work; nothing is shaped for the matrix cores.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 
 #include "common.hpp"
+#include "devprim.hpp"
 
 namespace {
 
+namespace devprim = pings::devprim;
 using i64 = long long;
 using u64 = unsigned long long;
 
@@ -34,7 +34,6 @@ constexpr int kMaxRings = 64;
 constexpr int kReduceBlock = 1024;
 constexpr u64 kPadKey = ~0ull;                 // key of a buffer row past the live count: sorts behind every cell
 
-__host__ __device__ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline unsigned blocks_for(i64 n) { return (unsigned)((n + kBlock - 1) / kBlock); }
 
 // live rows of a buffer of `cap` rows: the device count when there is one, clamped into [0, cap]
@@ -334,31 +333,27 @@ struct GridScratch {
 };
 
 GridScratch carve_grid(void* base, i64 cap, bool search) {
-  char* p = reinterpret_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? p + off : nullptr; off += up256(bytes); return r; };
+  pings::Carver c(base);
   GridScratch s{};
   const size_t n = (size_t)cap;
-  s.partial = (Part*)take(sizeof(Part) * kPartBlocks);
-  s.info = (GridInfo*)take(sizeof(GridInfo));
-  s.key = (u64*)take(8 * n);
-  s.key_sorted = (u64*)take(8 * n);
-  s.val = (uint32_t*)take(4 * n);
-  s.val_sorted = (uint32_t*)take(4 * n);
-  size_t a = 0, b = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (u64*)nullptr, (u64*)nullptr, (uint32_t*)nullptr,
-                                           (uint32_t*)nullptr, (int)n);
+  s.partial = c.take<Part>(kPartBlocks);
+  s.info = c.take<GridInfo>(1);
+  s.key = c.take<u64>(n);
+  s.key_sorted = c.take<u64>(n);
+  s.val = c.take<uint32_t>(n);
+  s.val_sorted = c.take<uint32_t>(n);
+  s.temp_bytes = devprim::sort_pairs_u64_u32_temp_bytes(cap);
   if (search) {
-    s.pts4 = (float4*)take(16 * n);
+    s.pts4 = c.take<float4>(n);
   } else {
-    s.flag = (int*)take(4 * n);
-    s.rank = (int*)take(4 * n);
-    s.start = (int*)take(4 * n);
-    (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, (int*)nullptr, (int*)nullptr, (int)n);
+    s.flag = c.take<int>(n);
+    s.rank = c.take<int>(n);
+    s.start = c.take<int>(n);
+    s.temp_bytes = std::max(s.temp_bytes, devprim::inclusive_sum_i32_temp_bytes(cap));   // the scan follows the sort
   }
-  s.temp_bytes = up256(a > b ? a : b);
-  s.temp = take(s.temp_bytes);
-  s.total = off;
+  s.temp_bytes = pings::align_up(s.temp_bytes);
+  s.temp = c.take<char>(s.temp_bytes);
+  s.total = c.total();
   return s;
 }
 
@@ -372,10 +367,7 @@ int file_points(const float* pts, i64 cap, const int64_t* n_dev, double cell, do
   PINGS_LAUNCH_CHECK();
   key_kernel<<<blocks_for(cap), kBlock, 0, st>>>(pts, cap, s.info, cell, s.key, s.val);
   PINGS_LAUNCH_CHECK();
-  size_t tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(s.temp, tb, s.key, s.key_sorted, s.val, s.val_sorted, (int)cap, 0,
-                                                     64, st));
-  return PINGS_OK;
+  return devprim::sort_pairs_u64_u32(s.temp, s.temp_bytes, s.key, s.key_sorted, s.val, s.val_sorted, cap, 0, 64, st);
 }
 
 // ------------------------------------------------------------------ voxel centroids
@@ -581,11 +573,28 @@ __global__ __launch_bounds__(kReduceBlock) void pair_reduce_kernel(const float* 
 
 bool count_ok(int64_t n) { return n > 0 && n <= kMaxCount; }
 
+struct BpScratch {
+  int *cnt, *off;   // per block: points kept, their inclusive scan
+  void* temp;
+  size_t temp_bytes, total;
+};
+BpScratch carve_backproject(void* base, i64 hw) {
+  pings::Carver c(base);
+  BpScratch s;
+  const size_t nb = (size_t)blocks_for(hw);
+  s.cnt = c.take<int>(nb);
+  s.off = c.take<int>(nb);
+  s.temp_bytes = devprim::inclusive_sum_i32_temp_bytes((i64)nb);
+  s.temp = c.take<char>(s.temp_bytes);
+  s.total = c.total();
+  return s;
+}
+
 }  // namespace
 
 PINGS_API size_t pings_eval_view_metrics_scratch_bytes(int64_t hw) {
   if (hw <= 0) return 0;
-  return up256(sizeof(float) * kViewPart * kPartBlocks);
+  return pings::align_up(sizeof(float) * kViewPart * kPartBlocks);
 }
 
 PINGS_API int pings_eval_view_metrics(const float* rgb, const float* gt, int channels, int64_t hw, const float* depth,
@@ -610,11 +619,7 @@ PINGS_API int pings_eval_view_metrics(const float* rgb, const float* gt, int cha
 }
 
 PINGS_API size_t pings_eval_backproject_scratch_bytes(int64_t hw) {
-  if (!count_ok(hw)) return 0;
-  const size_t nb = (size_t)blocks_for(hw);
-  size_t tb = 0;
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, tb, (int*)nullptr, (int*)nullptr, (int)nb);
-  return 2 * up256(sizeof(int) * nb) + up256(tb);
+  return count_ok(hw) ? carve_backproject(nullptr, hw).total : 0;
 }
 
 PINGS_API int pings_eval_backproject(const float* depth, const float* rgb, const float* alpha, int height, int width,
@@ -637,17 +642,12 @@ PINGS_API int pings_eval_backproject(const float* depth, const float* rgb, const
   for (int k = 0; k < 12; ++k) a.T[k] = cam_to_world[k];
   a.amin = min_alpha;
   const int nb = (int)blocks_for(a.hw);
-  char* base = static_cast<char*>(scratch);
-  int* cnt = reinterpret_cast<int*>(base);
-  int* off = reinterpret_cast<int*>(base + up256(sizeof(int) * nb));
-  void* temp = base + 2 * up256(sizeof(int) * nb);
-  size_t tb = 0;
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, tb, (int*)nullptr, (int*)nullptr, nb);
+  const BpScratch s = carve_backproject(scratch, a.hw);
   pings::prof::Scope sc("eval_backproject", st);
-  bp_count_kernel<<<nb, kBlock, 0, st>>>(a, cnt);
+  bp_count_kernel<<<nb, kBlock, 0, st>>>(a, s.cnt);
   PINGS_LAUNCH_CHECK();
-  PINGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(temp, tb, cnt, off, nb, st));
-  bp_emit_kernel<<<nb, kBlock, 0, st>>>(a, off, nb, points, colors, count);
+  if (int e = devprim::inclusive_sum_i32(s.temp, s.temp_bytes, s.cnt, s.off, nb, st)) return e;
+  bp_emit_kernel<<<nb, kBlock, 0, st>>>(a, s.off, nb, points, colors, count);
   PINGS_LAUNCH_CHECK();
   return PINGS_OK;
 }
@@ -667,8 +667,7 @@ PINGS_API int pings_eval_voxel_centroids(const float* points, int64_t n, const i
   if (int e = file_points(points, n, n_dev, voxel, 0.5, s, status, st)) return e;
   vc_heads_kernel<<<blocks_for(n), kBlock, 0, st>>>(s.key_sorted, n, s.info, s.flag);
   PINGS_LAUNCH_CHECK();
-  size_t tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(s.temp, tb, s.flag, s.rank, (int)n, st));
+  if (int e = devprim::inclusive_sum_i32(s.temp, s.temp_bytes, s.flag, s.rank, n, st)) return e;
   vc_starts_kernel<<<blocks_for(n), kBlock, 0, st>>>(s.flag, s.rank, n, s.info, s.start, count);
   PINGS_LAUNCH_CHECK();
   vc_mean_kernel<<<blocks_for(n), kBlock, 0, st>>>(points, s.val_sorted, s.start, n, s.info, count, out);

@@ -125,17 +125,15 @@ struct NewScratch {
   size_t total;
 };
 NewScratch carve_new(void* blob, i64 n) {
-  char* base = reinterpret_cast<char*>(blob);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off = (off + bytes + 255) & ~(size_t)255; return q; };
+  pings::Carver c(blob);
   NewScratch w;
   w.nchunks = n > 0 ? (n + kChunk - 1) / kChunk : 0;
   const size_t nc = (size_t)(w.nchunks > 0 ? w.nchunks : 1);
-  w.counts = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * nc));
-  w.offsets = reinterpret_cast<i64*>(take(sizeof(i64) * nc));
-  w.total2 = reinterpret_cast<uint32_t*>(take(2 * sizeof(uint32_t)));
-  w.bits = reinterpret_cast<u64*>(take(sizeof(u64) * nc * kSteps));
-  w.total = off;
+  w.counts = c.take<uint32_t>(nc);
+  w.offsets = c.take<i64>(nc);
+  w.total2 = c.take<uint32_t>(2);
+  w.bits = c.take<u64>(nc * kSteps);
+  w.total = c.total();
   return w;
 }
 

@@ -25,8 +25,6 @@ constexpr int kMaxC = PINGS_LOOP_MAX_C;
 constexpr int kSearchThreads = 1024;
 constexpr float kCosEps = 1e-8f;     // F.cosine_similarity's eps
 
-size_t au(size_t v) { return (v + 255) / 256 * 256; }
-
 // fp32 -> uint32 whose unsigned order is the order of the floats; 0 is taken by no finite value (= an empty bin)
 __device__ __forceinline__ uint32_t order_key(float z) {
   const uint32_t b = __float_as_uint(z);
@@ -287,14 +285,32 @@ __global__ __launch_bounds__(kSearchThreads) void shift_kernel(const float* __re
 
 bool shape_ok(int R, int S, int D) { return R >= 1 && R <= kMaxR && S >= 1 && S <= kMaxS && D >= 0 && D <= kMaxD; }
 
+struct ContextScratch {
+  uint32_t* zkey;              // [rows] largest height key per bin
+  uint32_t *keys, *src_row;    // [pairs] bin and point of every (point, pose) pair; with features only
+  pings_rows::Plan plan;       // the feature sums by bin; with features only
+  size_t total;
+};
+ContextScratch carve_context(void* base, int64_t rows, int64_t pairs, bool features) {
+  pings::Carver c(base);
+  ContextScratch s{};
+  s.zkey = c.take<uint32_t>((size_t)rows);
+  if (features) {
+    const size_t n = (size_t)(pairs > 0 ? pairs : 1);
+    s.keys = c.take<uint32_t>(n);
+    s.src_row = c.take<uint32_t>(n);
+    char* plan = c.take<char>(pings_rows::carve(nullptr, pairs, rows).total);
+    s.plan = pings_rows::carve(plan, pairs, rows);
+  }
+  s.total = c.total();
+  return s;
+}
+
 }  // namespace
 
 PINGS_API size_t pings_loop_context_scratch_bytes(int64_t n_points, int32_t M, int32_t R, int32_t S, int32_t D) {
   if (n_points < 0 || M < 1 || M > kMaxQ || !shape_ok(R, S, D) || n_points * M >= 0x7FFFFFF0LL) return 0;
-  const int64_t rows = (int64_t)M * R * S, pairs = n_points * M;
-  size_t total = au((size_t)rows * 4);
-  if (D > 0) total += 2 * au((size_t)(pairs > 0 ? pairs : 1) * 4) + pings_rows::carve(nullptr, pairs, rows).total;
-  return total;
+  return carve_context(nullptr, (int64_t)M * R * S, n_points * M, D > 0).total;
 }
 
 PINGS_API int pings_loop_context_build(const float* points, int64_t n_points, const float* features, int32_t D,
@@ -311,17 +327,9 @@ PINGS_API int pings_loop_context_build(const float* points, int64_t n_points, co
   hipStream_t st = pings::as_stream(stream);
   pings::prof::Scope ps("loop_context_build", st);
   const int64_t rows = (int64_t)M * R * S, pairs = n_points * M;
-  char* base = reinterpret_cast<char*>(scratch);
-  uint32_t* zkey = reinterpret_cast<uint32_t*>(base);
-  size_t off = au((size_t)rows * 4);
-  uint32_t *keys = nullptr, *src_row = nullptr;
-  pings_rows::Plan plan{};
-  if (D > 0) {
-    const size_t pb = au((size_t)(pairs > 0 ? pairs : 1) * 4);
-    keys = reinterpret_cast<uint32_t*>(base + off);
-    src_row = reinterpret_cast<uint32_t*>(base + off + pb);
-    plan = pings_rows::carve(base + off + 2 * pb, pairs, rows);
-  }
+  const ContextScratch s = carve_context(scratch, rows, pairs, D > 0);
+  uint32_t *zkey = s.zkey, *keys = s.keys, *src_row = s.src_row;
+  const pings_rows::Plan& plan = s.plan;
   PINGS_HIP_CHECK(hipMemsetAsync(zkey, 0, (size_t)rows * 4, st));
   if (n_points > 0) {
     const dim3 grid((unsigned)((n_points + 255) / 256), (unsigned)M);

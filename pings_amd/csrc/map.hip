@@ -17,19 +17,17 @@
 //                         full_like(bool, -1) quirk), row gathers of the per-point arrays.
 //   assign_local_to_global  row scatters.
 // All kernels are HBM-stream / gather bound: integer and byte work, nothing here is shaped for the matrix cores.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 #include <cmath>
 
 #include "common.hpp"
+#include "devprim.hpp"
 
 namespace {
 
+namespace devprim = pings::devprim;
 using i64 = long long;
 constexpr int kQuant = 1000;  // distance bins of voxel_down_sample_torch (utils/tools.py:937)
-
-__host__ __device__ inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 // `x ** 2` of a python float: libm's pow, which differs from x * x in the last bit for about one double in a
 // thousand.  The volatile exponent keeps the compiler from folding the call into a multiplication.
@@ -161,28 +159,22 @@ struct VdsScratch {
 constexpr int kBoundBlocks = 512;
 
 VdsScratch carve_vds(void* base, i64 N) {
-  char* p = reinterpret_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p ? p + off : nullptr; off += up256(bytes); return r; };
+  pings::Carver c(base);
   VdsScratch s;
   const size_t n = (size_t)(N > 0 ? N : 1);
-  s.partial = (Bounds*)take(sizeof(Bounds) * kBoundBlocks);
-  s.info = (GridInfo*)take(sizeof(GridInfo));
-  s.key = (i64*)take(8 * n);
-  s.key_sorted = (i64*)take(8 * n);
-  s.uniq = (i64*)take(8 * n);
-  s.val = (unsigned long long*)take(8 * n);
-  s.val_sorted = (unsigned long long*)take(8 * n);
-  s.agg = (unsigned long long*)take(8 * n);
-  s.nruns = (int*)take(sizeof(int));
-  size_t a = 0, b = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (i64*)nullptr, (i64*)nullptr, (unsigned long long*)nullptr,
-                                           (unsigned long long*)nullptr, (int)n);
-  (void)hipcub::DeviceReduce::ReduceByKey(nullptr, b, (i64*)nullptr, (i64*)nullptr, (unsigned long long*)nullptr,
-                                          (unsigned long long*)nullptr, (int*)nullptr, hipcub::Min(), (int)n);
-  s.temp_bytes = up256(a > b ? a : b);
-  s.temp = take(s.temp_bytes);
-  s.total = off;
+  s.partial = c.take<Bounds>(kBoundBlocks);
+  s.info = c.take<GridInfo>(1);
+  s.key = c.take<i64>(n);
+  s.key_sorted = c.take<i64>(n);
+  s.uniq = c.take<i64>(n);
+  s.val = c.take<unsigned long long>(n);
+  s.val_sorted = c.take<unsigned long long>(n);
+  s.agg = c.take<unsigned long long>(n);
+  s.nruns = c.take<int>(1);
+  s.temp_bytes = pings::align_up(std::max(devprim::sort_pairs_i64_u64_temp_bytes(N),   // the two phases share it
+                                          devprim::reduce_min_by_key_i64_u64_temp_bytes(N)));
+  s.temp = c.take<char>(s.temp_bytes);
+  s.total = c.total();
   return s;
 }
 
@@ -479,6 +471,50 @@ __global__ __launch_bounds__(256) void rehash_unpack_kernel(i64 M, const i64* __
   if ((v >> 32) >= 1) table[slot_of[j]] = (i64)(int32_t)(uint32_t)(v & 0xFFFFFFFFll);
 }
 
+struct UpdScratch {
+  i64 *slot, *hidx;
+  int32_t *flag, *pos, *winner;
+  void* temp;
+  size_t temp_bytes, total;
+};
+UpdScratch carve_update(void* base, i64 M, i64 num_points) {
+  pings::Carver c(base);
+  UpdScratch s;
+  const size_t m = (size_t)(M > 0 ? M : 1);
+  s.slot = c.take<i64>(m);
+  s.hidx = c.take<i64>(m);
+  s.flag = c.take<int32_t>(m);
+  s.pos = c.take<int32_t>(m);
+  s.winner = c.take<int32_t>((size_t)(num_points > 0 ? num_points : 1));
+  s.temp_bytes = devprim::exclusive_sum_i32_temp_bytes(M);
+  s.temp = c.take<char>(s.temp_bytes);
+  s.total = c.total();
+  return s;
+}
+
+struct RstScratch {
+  uint8_t* tflag;
+  int32_t *lflag, *lpos;
+  int* tcount;        // [0] total, [1..] shards
+  i64* nlocal_dev;
+  void* temp;
+  size_t temp_bytes, total;
+};
+RstScratch carve_reset(void* base, i64 num_points) {
+  pings::Carver c(base);
+  RstScratch s;
+  const size_t n = (size_t)(num_points > 0 ? num_points : 1);
+  s.tflag = c.take<uint8_t>(n);
+  s.lflag = c.take<int32_t>(n);
+  s.lpos = c.take<int32_t>(n);
+  s.tcount = c.take<int>(1 + kCountShards);
+  s.nlocal_dev = c.take<i64>(1);
+  s.temp_bytes = devprim::exclusive_sum_i32_temp_bytes(num_points);
+  s.temp = c.take<char>(s.temp_bytes);
+  s.total = c.total();
+  return s;
+}
+
 }  // namespace
 
 PINGS_API int pings_map_prune_mask(int64_t N, const float* travel_dist, int64_t num_travel, int32_t cur_ts,
@@ -559,12 +595,11 @@ PINGS_API int pings_voxel_downsample_min_value(const float* points, const float*
   vds_finish_bounds_kernel<<<1, 1, 0, st>>>(s.partial, nb, voxel_size, s.info);
   vds_key_kernel<<<blocks_for(N), 256, 0, st>>>(points, N, voxel_size, s.info, s.key, s.val, value);
   PINGS_LAUNCH_CHECK();
-  size_t tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(s.temp, tb, s.key, s.key_sorted, s.val, s.val_sorted, (int)N, 0,
-                                                     64, st));
-  tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceReduce::ReduceByKey(s.temp, tb, s.key_sorted, s.uniq, s.val_sorted, s.agg, s.nruns,
-                                                    hipcub::Min(), (int)N, st));
+  if (int e = devprim::sort_pairs_i64_u64(s.temp, s.temp_bytes, s.key, s.key_sorted, s.val, s.val_sorted, N, 0, 64, st))
+    return e;
+  if (int e = devprim::reduce_min_by_key_i64_u64(s.temp, s.temp_bytes, s.key_sorted, s.uniq, s.val_sorted, s.agg,
+                                                 s.nruns, N, st))
+    return e;
   vds_unpack_kernel<<<blocks_for(N), 256, 0, st>>>(s.agg, s.nruns, reinterpret_cast<i64*>(sample_idx));
   PINGS_LAUNCH_CHECK();
   uint32_t runs = 0;
@@ -575,10 +610,7 @@ PINGS_API int pings_voxel_downsample_min_value(const float* points, const float*
 }
 
 PINGS_API size_t pings_map_update_scratch_bytes(int64_t M, int64_t num_points) {
-  const size_t m = (size_t)(M > 0 ? M : 1), np = (size_t)(num_points > 0 ? num_points : 1);
-  size_t scan = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan, (int32_t*)nullptr, (int32_t*)nullptr, (int)m);
-  return up256(8 * m) * 2 + up256(4 * m) * 2 + up256(4 * np) + up256(scan) + 256;
+  return carve_update(nullptr, M, num_points).total;
 }
 
 PINGS_API int pings_map_update(const float* sample_points, const float* sample_colors, int64_t M, double resolution,
@@ -597,9 +629,7 @@ PINGS_API int pings_map_update(const float* sample_points, const float* sample_c
                       scratch, "null pointer");
   PINGS_ARG_CHECK(!sample_colors || point_colors, "sample colours without a colour array");
   hipStream_t st = pings::as_stream(stream);
-  char* p = reinterpret_cast<char*>(scratch);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p + off; off += up256(bytes); return r; };
+  const UpdScratch s = carve_update(scratch, M, num_points);
   UpdArgs a{};
   a.M = M; a.Np = num_points; a.S = buffer_size;
   a.res = (float)resolution;                                   // points / res and the hash: the fp32 scalar
@@ -612,15 +642,8 @@ PINGS_API int pings_map_update(const float* sample_points, const float* sample_c
   a.neural_points = neural_points; a.orient = point_orientations; a.cert = point_certainties; a.colors = point_colors;
   a.ts_create = point_ts_create; a.ts_update = point_ts_update;
   a.free_mask = free_gs_mask; a.valid_gs = valid_gs_mask; a.valid_color = valid_color_mask;
-  a.slot = (i64*)take(8 * (size_t)M);
-  a.hidx = (i64*)take(8 * (size_t)M);
-  a.flag = (int32_t*)take(4 * (size_t)M);
-  a.pos = (int32_t*)take(4 * (size_t)M);
-  a.winner = (int32_t*)take(4 * (size_t)(num_points > 0 ? num_points : 1));
+  a.slot = s.slot; a.hidx = s.hidx; a.flag = s.flag; a.pos = s.pos; a.winner = s.winner;
   a.upd_out = update_mask;
-  void* temp = p + off;
-  size_t tb = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (int32_t*)nullptr, (int32_t*)nullptr, (int)M);
   pings::prof::Scope sc("map_update", st);
   if (num_points > 0 && sample_colors)
     PINGS_HIP_CHECK(hipMemsetAsync(a.winner, 0, 4 * (size_t)num_points, st));
@@ -628,7 +651,7 @@ PINGS_API int pings_map_update(const float* sample_points, const float* sample_c
   upd_classify_kernel<<<nb, 256, 0, st>>>(a);
   PINGS_LAUNCH_CHECK();
   upd_color_kernel<<<nb, 256, 0, st>>>(a);
-  PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, a.flag, a.pos, (int)M, st));
+  if (int e = devprim::exclusive_sum_i32(s.temp, s.temp_bytes, a.flag, a.pos, M, st)) return e;
   upd_commit_kernel<<<nb, 256, 0, st>>>(a);
   upd_unpack_kernel<<<nb, 256, 0, st>>>(a);
   PINGS_LAUNCH_CHECK();
@@ -641,10 +664,7 @@ PINGS_API int pings_map_update(const float* sample_points, const float* sample_c
 }
 
 PINGS_API size_t pings_map_reset_local_scratch_bytes(int64_t num_points) {
-  const size_t n = (size_t)(num_points > 0 ? num_points : 1);
-  size_t scan = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan, (int32_t*)nullptr, (int32_t*)nullptr, (int)n);
-  return up256(n) + up256(4 * n) * 2 + up256(scan) + 4096;
+  return carve_reset(nullptr, num_points).total;
 }
 
 PINGS_API int pings_map_reset_local(int64_t num_points, const float* neural_points, const int32_t* point_ts_create,
@@ -661,10 +681,7 @@ PINGS_API int pings_map_reset_local(int64_t num_points, const float* neural_poin
                   "null pointer");
   PINGS_ARG_CHECK(num_points == 0 || (neural_points && point_ts_create && point_ts_update), "null map array");
   hipStream_t st = pings::as_stream(stream);
-  char* p = reinterpret_cast<char*>(scratch);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { void* r = p + off; off += up256(bytes); return r; };
-  const size_t n = (size_t)(num_points > 0 ? num_points : 1);
+  const RstScratch s = carve_reset(scratch, num_points);
   RstArgs a{};
   a.Np = num_points; a.pts = neural_points; a.ts_create = point_ts_create; a.ts_update = point_ts_update;
   a.travel = travel_dist; a.sensor = sensor_position; a.cur_ts = cur_ts;
@@ -673,14 +690,7 @@ PINGS_API int pings_map_reset_local(int64_t num_points, const float* neural_poin
   a.range_2d = range_filter_2d; a.diff_travel = diff_travel_dist_local;
   a.local_r2 = (float)py_square(local_radius);               // radius ** 2 in double, rounded to fp32 once
   a.sur_r2 = (float)py_square(sorrounding_radius);
-  a.tflag = (uint8_t*)take(n);
-  a.lflag = (int32_t*)take(4 * n);
-  a.lpos = (int32_t*)take(4 * n);
-  a.tcount = (int*)take(sizeof(int) * (1 + kCountShards));  // [0] total, [1..] shards
-  a.nlocal_dev = (i64*)take(sizeof(i64));
-  void* temp = p + off;
-  size_t tb = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (int32_t*)nullptr, (int32_t*)nullptr, (int)n);
+  a.tflag = s.tflag; a.lflag = s.lflag; a.lpos = s.lpos; a.tcount = s.tcount; a.nlocal_dev = s.nlocal_dev;
   a.local_mask = local_mask; a.sur_mask = sorrounding_mask; a.g2l = reinterpret_cast<i64*>(global2local); a.lidx = reinterpret_cast<i64*>(local_idx);
   pings::prof::Scope sc("map_reset_local", st);
   PINGS_HIP_CHECK(hipMemsetAsync(a.tcount, 0, sizeof(int) * (1 + kCountShards), st));
@@ -693,7 +703,7 @@ PINGS_API int pings_map_reset_local(int64_t num_points, const float* neural_poin
   rst_mask_kernel<<<blocks_for(num_points + 1), 256, 0, st>>>(a);
   PINGS_LAUNCH_CHECK();
   if (num_points > 0)
-    PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, a.lflag, a.lpos, (int)num_points, st));
+    if (int e = devprim::exclusive_sum_i32(s.temp, s.temp_bytes, a.lflag, a.lpos, num_points, st)) return e;
   rst_index_kernel<<<blocks_for(num_points + 1), 256, 0, st>>>(a);
   PINGS_LAUNCH_CHECK();
   uint32_t nl[2] = {0, 0};
@@ -729,18 +739,13 @@ struct MaskRows {
   size_t temp_bytes, total;
 };
 MaskRows carve_mask_rows(void* blob, i64 n) {
-  char* base = reinterpret_cast<char*>(blob);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off = (off + bytes + 255) & ~(size_t)255; return q; };
+  pings::Carver c(blob);
   MaskRows m;
-  m.num = reinterpret_cast<i64*>(take(sizeof(i64)));
-  m.out2 = reinterpret_cast<uint32_t*>(take(2 * sizeof(uint32_t)));
-  size_t tb = 0;
-  (void)hipcub::DeviceSelect::Flagged(nullptr, tb, hipcub::CountingInputIterator<i64>(0), (const uint8_t*)nullptr,
-                                      (i64*)nullptr, (i64*)nullptr, (int)(n > 0 ? n : 1));
-  m.temp_bytes = tb;
-  m.temp = take(tb);
-  m.total = off;
+  m.num = c.take<i64>(1);
+  m.out2 = c.take<uint32_t>(2);
+  m.temp_bytes = devprim::select_flagged_iota_i64_temp_bytes(n);
+  m.temp = c.take<char>(m.temp_bytes);
+  m.total = c.total();
   return m;
 }
 __global__ void mask_tail_kernel(const uint8_t* __restrict__ mask, i64 n, const i64* __restrict__ num,
@@ -788,9 +793,8 @@ PINGS_API int pings_mask_rows(const uint8_t* mask, int64_t n, void* scratch, int
   PINGS_ARG_CHECK(mask && scratch && rows, "null pointer");
   hipStream_t st = pings::as_stream(stream);
   MaskRows m = carve_mask_rows(scratch, n);
-  size_t tb = m.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceSelect::Flagged(m.temp, tb, hipcub::CountingInputIterator<i64>(0), mask,
-                                                reinterpret_cast<i64*>(rows), m.num, (int)n, st));
+  if (int e = devprim::select_flagged_iota_i64(m.temp, m.temp_bytes, mask, reinterpret_cast<i64*>(rows), m.num, n, st))
+    return e;
   mask_tail_kernel<<<1, 1, 0, st>>>(mask, n, m.num, m.out2);
   PINGS_LAUNCH_CHECK();
   const uint32_t* src[2] = {m.out2, m.out2 + 1};

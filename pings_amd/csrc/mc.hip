@@ -9,9 +9,9 @@
 //   verts   recounts, scans the block, writes keys (sorted by construction) and positions at the block's offset
 //   faces   retriangulates cell p and writes its faces, each key resolved by binary search in its owner block's slice
 // No atomics, no per-cell state: the workspace is O(points / 256).
-#include <hipcub/hipcub.hpp>
 
 #include "common.hpp"
+#include "devprim.hpp"
 
 namespace {
 
@@ -324,22 +324,16 @@ struct Scratch {
 };
 
 Scratch carve(i64 nb, void* base) {
+  pings::Carver c(base);
   Scratch s{};
-  size_t tb = 0;
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, tb, (const i64*)nullptr, (i64*)nullptr, (int)nb);
-  auto al = [](size_t x) { return (x + 255) & ~size_t(255); };
-  const size_t arr = al(sizeof(i64) * (size_t)nb);
-  s.temp_bytes = tb;
-  s.total = 4 * arr + al(2 * sizeof(i64)) + al(tb);
-  char* b = static_cast<char*>(base);
-  if (b) {
-    s.vcnt = reinterpret_cast<i64*>(b);
-    s.fcnt = reinterpret_cast<i64*>(b + arr);
-    s.voff = reinterpret_cast<i64*>(b + 2 * arr);
-    s.foff = reinterpret_cast<i64*>(b + 3 * arr);
-    s.tot = reinterpret_cast<i64*>(b + 4 * arr);
-    s.temp = b + 4 * arr + al(2 * sizeof(i64));
-  }
+  s.vcnt = c.take<i64>((size_t)nb);
+  s.fcnt = c.take<i64>((size_t)nb);
+  s.voff = c.take<i64>((size_t)nb);
+  s.foff = c.take<i64>((size_t)nb);
+  s.tot = c.take<i64>(2);
+  s.temp_bytes = pings::devprim::inclusive_sum_i64_temp_bytes(nb);
+  s.temp = c.take<char>(s.temp_bytes);
+  s.total = c.total();
   return s;
 }
 
@@ -372,10 +366,8 @@ PINGS_API int pings_mc_count(const float* vol, const uint8_t* mask, int64_t nx, 
   pings::prof::Scope sc("mc_count", st);
   hipLaunchKernelGGL(mc_count_kernel, dim3((unsigned)nb), dim3(kBlock), 0, st, g, s.vcnt, s.fcnt);
   PINGS_LAUNCH_CHECK();
-  size_t tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(s.temp, tb, s.vcnt, s.voff, (int)nb, st));
-  tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(s.temp, tb, s.fcnt, s.foff, (int)nb, st));
+  if (int e = pings::devprim::inclusive_sum_i64(s.temp, s.temp_bytes, s.vcnt, s.voff, nb, st)) return e;
+  if (int e = pings::devprim::inclusive_sum_i64(s.temp, s.temp_bytes, s.fcnt, s.foff, nb, st)) return e;
   hipLaunchKernelGGL(mc_totals_kernel, dim3(1), dim3(64), 0, st, s.voff, s.foff, nb, s.tot);
   PINGS_LAUNCH_CHECK();
   const uint32_t* w = reinterpret_cast<const uint32_t*>(s.tot);

@@ -11,15 +11,18 @@
 //   normals   (vertex, corner) pairs sorted by vertex, so that a vertex's corners lie in ascending face, then corner
 //             order; one thread per vertex adds its corners' face normals in that order
 //   compact   used flags, exclusive scan, gather, face rewrite
-// The sorts and scans are hipcub's; there is no float atomic, no wait on another workgroup, no per-thread array.
-#include <hipcub/hipcub.hpp>
-
+// The sorts and scans are the library's (devprim.hpp); there is no float atomic, no wait on another workgroup, no
+// per-thread array.
+#include <algorithm>
 #include <utility>
 
 #include "common.hpp"
+#include "devprim.hpp"
 
 namespace {
 
+namespace devprim = pings::devprim;
+using pings::Carver;
 using i64 = int64_t;
 using u32 = uint32_t;
 using u64 = unsigned long long;
@@ -27,38 +30,10 @@ constexpr int kBlock = 256;
 constexpr i64 kMaxIndex = (i64)0x7FFFFFFF;   // V and 3F stay below: indices are 32-bit inside the kernels
 
 inline unsigned blocks(i64 n) { return (unsigned)pings::ceil_div<i64>(n > 0 ? n : 1, kBlock); }
-inline size_t al(size_t x) { return (x + 255) & ~size_t(255); }
 
-// Bump allocator over the caller's scratch; with base == nullptr it only measures.
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* b) : base(static_cast<char*>(b)) {}
-  template <class T>
-  T* take(size_t n) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off += al(sizeof(T) * (n ? n : 1));
-    return p;
-  }
-};
-
-size_t sort32_temp(i64 n) {
-  size_t b = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (u32*)nullptr, (u32*)nullptr, (u32*)nullptr, (u32*)nullptr,
-                                           (int)(n > 0 ? n : 1));
-  return b;
-}
-size_t sort64_temp(i64 n) {
-  size_t b = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, b, (u64*)nullptr, (u64*)nullptr, (u32*)nullptr, (u32*)nullptr,
-                                           (int)(n > 0 ? n : 1));
-  return b;
-}
+// one size for the two scans of this file: the weld runs both through the same temp field
 size_t scan_temp(i64 n) {
-  size_t a = 0, b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, a, (u32*)nullptr, (u32*)nullptr, (int)(n > 0 ? n : 1));
-  (void)hipcub::DeviceScan::InclusiveScan(nullptr, b, (u32*)nullptr, (u32*)nullptr, hipcub::Max(), (int)(n > 0 ? n : 1));
-  return a > b ? a : b;
+  return std::max(devprim::exclusive_sum_u32_temp_bytes(n), devprim::inclusive_max_u32_temp_bytes(n));
 }
 
 __device__ __forceinline__ i64 gid() { return (i64)blockIdx.x * kBlock + threadIdx.x; }
@@ -162,10 +137,9 @@ WeldScratch carve_weld(i64 V, void* base) {
   s.keep = c.take<u32>(V);
   s.pos = c.take<u32>(V);
   s.tot = c.take<u32>(4);
-  const size_t a = sort32_temp(V), b = scan_temp(V);
-  s.temp_bytes = a > b ? a : b;
+  s.temp_bytes = std::max(devprim::sort_pairs_u32_u32_temp_bytes(V), scan_temp(V));
   s.temp = c.take<char>(s.temp_bytes);
-  s.total = c.off;
+  s.total = c.total();
   return s;
 }
 
@@ -313,10 +287,9 @@ ClusterScratch carve_clusters(i64 F, void* base) {
   s.size = c.take<u32>(F);
   s.isroot = c.take<u32>(F);
   s.rank = c.take<u32>(F);
-  const size_t a = sort64_temp(3 * F), b = scan_temp(F);
-  s.temp_bytes = a > b ? a : b;
+  s.temp_bytes = std::max(devprim::sort_pairs_u64_u32_temp_bytes(3 * F), scan_temp(F));
   s.temp = c.take<char>(s.temp_bytes);
-  s.total = c.off;
+  s.total = c.total();
   return s;
 }
 
@@ -375,13 +348,14 @@ struct NormalScratch {
 NormalScratch carve_normals(i64 F, void* base) {
   Carver c(base);
   NormalScratch s{};
-  s.key = c.take<u32>(3 * F);
-  s.key_sorted = c.take<u32>(3 * F);
-  s.val = c.take<u32>(3 * F);
-  s.val_sorted = c.take<u32>(3 * F);
-  s.temp_bytes = sort32_temp(3 * F);
+  const size_t n = F > 0 ? 3 * (size_t)F : 1;   // a mesh without faces still gets a blob
+  s.key = c.take<u32>(n);
+  s.key_sorted = c.take<u32>(n);
+  s.val = c.take<u32>(n);
+  s.val_sorted = c.take<u32>(n);
+  s.temp_bytes = devprim::sort_pairs_u32_u32_temp_bytes(3 * F);
   s.temp = c.take<char>(s.temp_bytes);
-  s.total = c.off;
+  s.total = c.total();
   return s;
 }
 
@@ -414,7 +388,7 @@ CompactScratch carve_compact(i64 V, void* base) {
   s.tot = c.take<u32>(4);
   s.temp_bytes = scan_temp(V);
   s.temp = c.take<char>(s.temp_bytes);
-  s.total = c.off;
+  s.total = c.total();
   return s;
 }
 
@@ -450,20 +424,18 @@ PINGS_API int pings_mesh_weld(const float* verts, int64_t V, const int64_t* face
     hipLaunchKernelGGL(weld_key_kernel, dim3(nb), dim3(kBlock), 0, st, verts, first ? (const u32*)nullptr : idx_cur, V,
                        axis, s.key_a, first ? idx_cur : (u32*)nullptr);
     PINGS_LAUNCH_CHECK();
-    size_t tb = s.temp_bytes;
-    PINGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(s.temp, tb, s.key_a, s.key_b, idx_cur, idx_next, (int)V, 0, 32, st));
+    if (int e = devprim::sort_pairs_u32_u32(s.temp, s.temp_bytes, s.key_a, s.key_b, idx_cur, idx_next, V, 0, 32, st))
+      return e;
     std::swap(idx_cur, idx_next);
   }
   const u32* idx = idx_cur;
   u32 *head = s.key_a, *headpos = s.key_b;
   hipLaunchKernelGGL(weld_heads_kernel, dim3(nb), dim3(kBlock), 0, st, verts, idx, V, head);
   PINGS_LAUNCH_CHECK();
-  size_t tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceScan::InclusiveScan(s.temp, tb, head, headpos, hipcub::Max(), (int)V, st));
+  if (int e = devprim::inclusive_max_u32(s.temp, s.temp_bytes, head, headpos, V, st)) return e;
   hipLaunchKernelGGL(weld_rep_kernel, dim3(nb), dim3(kBlock), 0, st, idx, (const u32*)headpos, V, s.rep, s.keep);
   PINGS_LAUNCH_CHECK();
-  tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(s.temp, tb, s.keep, s.pos, (int)V, st));
+  if (int e = devprim::exclusive_sum_u32(s.temp, s.temp_bytes, s.keep, s.pos, V, st)) return e;
   hipLaunchKernelGGL(clear_words_kernel, dim3(1), dim3(64), 0, st, s.tot, 4);
   PINGS_LAUNCH_CHECK();
   hipLaunchKernelGGL(gather_kept_kernel, dim3(nb), dim3(kBlock), 0, st, verts, (const u32*)s.rep, (const u32*)s.keep,
@@ -501,17 +473,16 @@ PINGS_API int pings_mesh_clusters(const int64_t* faces, int64_t F, int64_t V, vo
   hipLaunchKernelGGL(edge_keys_kernel, dim3(blocks(n)), dim3(kBlock), 0, st, faces, F, V, s.key, s.val, s.parent, s.size,
                      s.tot);
   PINGS_LAUNCH_CHECK();
-  size_t tb = s.temp_bytes;
   const int vb = bits_for(V);          // both halves of a key are <= V
-  PINGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(s.temp, tb, s.key, s.key_sorted, s.val, s.val_sorted, (int)n, 0,
-                                                     32 + vb, st));
+  if (int e = devprim::sort_pairs_u64_u32(s.temp, s.temp_bytes, s.key, s.key_sorted, s.val, s.val_sorted, n, 0, 32 + vb,
+                                          st))
+    return e;
   hipLaunchKernelGGL(union_kernel, dim3(blocks(n)), dim3(kBlock), 0, st, (const u64*)s.key_sorted,
                      (const u32*)s.val_sorted, n, s.parent);
   PINGS_LAUNCH_CHECK();
   hipLaunchKernelGGL(flatten_kernel, dim3(blocks(F)), dim3(kBlock), 0, st, s.parent, F, s.root, s.size, s.isroot);
   PINGS_LAUNCH_CHECK();
-  tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(s.temp, tb, s.isroot, s.rank, (int)F, st));
+  if (int e = devprim::exclusive_sum_u32(s.temp, s.temp_bytes, s.isroot, s.rank, F, st)) return e;
   hipLaunchKernelGGL(labels_kernel, dim3(blocks(F)), dim3(kBlock), 0, st, (const u32*)s.root, (const u32*)s.rank,
                      (const u32*)s.isroot, (const u32*)s.size, F, labels, counts, s.tot);
   PINGS_LAUNCH_CHECK();
@@ -535,8 +506,7 @@ PINGS_API int pings_mesh_drop_small(const int64_t* faces, int64_t F, const int64
   u32 *keep = s.isroot, *pos = s.rank;
   hipLaunchKernelGGL(keep_faces_kernel, dim3(blocks(F)), dim3(kBlock), 0, st, labels, counts, F, min_tri, keep);
   PINGS_LAUNCH_CHECK();
-  size_t tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(s.temp, tb, keep, pos, (int)F, st));
+  if (int e = devprim::exclusive_sum_u32(s.temp, s.temp_bytes, keep, pos, F, st)) return e;
   hipLaunchKernelGGL(compact_faces_kernel, dim3(blocks(F)), dim3(kBlock), 0, st, faces, (const u32*)keep,
                      (const u32*)pos, F, faces_out, s.tot);
   PINGS_LAUNCH_CHECK();
@@ -566,9 +536,9 @@ PINGS_API int pings_mesh_vertex_normals(const float* verts, int64_t V, const int
   if (n) {
     hipLaunchKernelGGL(corner_keys_kernel, dim3(blocks(n)), dim3(kBlock), 0, st, faces, F, V, s.key, s.val);
     PINGS_LAUNCH_CHECK();
-    size_t tb = s.temp_bytes;
-    PINGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(s.temp, tb, s.key, s.key_sorted, s.val, s.val_sorted, (int)n, 0,
-                                                       bits_for(V), st));
+    if (int e = devprim::sort_pairs_u32_u32(s.temp, s.temp_bytes, s.key, s.key_sorted, s.val, s.val_sorted, n, 0,
+                                            bits_for(V), st))
+      return e;
   }
   hipLaunchKernelGGL(normals_kernel, dim3(blocks(V)), dim3(kBlock), 0, st, verts, faces, (const u32*)s.key_sorted,
                      (const u32*)s.val_sorted, V, n, normals);
@@ -596,8 +566,7 @@ PINGS_API int pings_mesh_compact_vertices(const float* verts, int64_t V, const i
     hipLaunchKernelGGL(mark_used_kernel, dim3(blocks(3 * F)), dim3(kBlock), 0, st, faces, 3 * F, V, s.used, s.tot);
     PINGS_LAUNCH_CHECK();
   }
-  size_t tb = s.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(s.temp, tb, s.used, s.pos, (int)V, st));
+  if (int e = devprim::exclusive_sum_u32(s.temp, s.temp_bytes, s.used, s.pos, V, st)) return e;
   hipLaunchKernelGGL(gather_kept_kernel, dim3(blocks(V)), dim3(kBlock), 0, st, verts, (const u32*)nullptr,
                      (const u32*)s.used, (const u32*)s.pos, V, verts_out, remap, kept, s.tot);
   PINGS_LAUNCH_CHECK();

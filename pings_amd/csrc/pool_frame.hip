@@ -93,17 +93,15 @@ struct Scratch {
   size_t total;
 };
 Scratch carve(void* blob, i64 n) {
-  char* base = reinterpret_cast<char*>(blob);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* q = base ? base + off : nullptr; off = (off + bytes + 255) & ~(size_t)255; return q; };
+  pings::Carver c(blob);
   Scratch w;
   w.nchunks = n > 0 ? (n + kChunk - 1) / kChunk : 0;
   const size_t nc = (size_t)(w.nchunks > 0 ? w.nchunks : 1);
-  w.counts = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * nc));
-  w.tails = reinterpret_cast<uint32_t*>(take(sizeof(uint32_t) * nc));
-  w.offsets = reinterpret_cast<i64*>(take(sizeof(i64) * nc));
-  w.totals = reinterpret_cast<uint32_t*>(take(4 * sizeof(uint32_t)));
-  w.total = off;
+  w.counts = c.take<uint32_t>(nc);
+  w.tails = c.take<uint32_t>(nc);
+  w.offsets = c.take<i64>(nc);
+  w.totals = c.take<uint32_t>(4);
+  w.total = c.total();
   return w;
 }
 

@@ -362,8 +362,6 @@ __global__ __launch_bounds__(256) void qf_double_backward_kernel(
   }
 }
 
-size_t au(size_t v) { return (v + 255) / 256 * 256; }
-
 struct QfScratch {
   uint32_t *keys, *src_row;
   float* pair_w;
@@ -373,15 +371,13 @@ struct QfScratch {
 
 QfScratch carve_qf(void* base, int64_t B, int nnk, int64_t rows) {
   QfScratch s;
-  char* p = reinterpret_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off = au(off + bytes); return r; };
+  pings::Carver c(base);
   const size_t n = (size_t)(B > 0 ? B : 1) * nnk;
-  s.keys = (uint32_t*)take(n * 4);
-  s.src_row = (uint32_t*)take(n * 4);
-  s.pair_w = (float*)take(n * 4);
-  s.plan = take(pings_rows::carve(nullptr, (int64_t)n, rows).total);
-  s.total = off;
+  s.keys = c.take<uint32_t>(n);
+  s.src_row = c.take<uint32_t>(n);
+  s.pair_w = c.take<float>(n);
+  s.plan = c.take<char>(pings_rows::carve(nullptr, (int64_t)n, rows).total);
+  s.total = c.total();
   return s;
 }
 

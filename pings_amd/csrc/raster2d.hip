@@ -25,17 +25,14 @@
 // sqrt), so radii, tile squares and sort order match the fp32 restatement bit for bit.  The forward and backward
 // blend kernels evaluate a (pixel, splat) pair through the same inline function, so both take the same skip / stop /
 // branch decisions.
-#include <hipcub/hipcub.hpp>
-
 #include <algorithm>
 
+#include "devprim.hpp"
 #include "raster_common.hpp"
 
 namespace pings {
 namespace raster2d {
 
-using raster::Carver;
-using raster::align_up;
 using raster::wave_reduce_sum_dpp;
 
 constexpr int TILE = 16;
@@ -100,20 +97,6 @@ static int tile_bits(int nt) {
   return b;
 }
 
-static size_t scan_temp_bytes(int n) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, (uint32_t*)nullptr, (uint32_t*)nullptr, std::max(n, 1));
-  return b;
-}
-
-static size_t sort_temp_bytes(int64_t n) {
-  size_t a = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, a, (unsigned long long*)nullptr, (unsigned long long*)nullptr,
-                                           (uint32_t*)nullptr, (uint32_t*)nullptr, (int)std::max<int64_t>(n, 1), 0,
-                                           64);
-  return a;
-}
-
 static Geom carve_geom(void* blob, int P) {
   Carver c(blob);
   Geom g;
@@ -124,9 +107,9 @@ static Geom carve_geom(void* blob, int P) {
   g.offsets = c.take<uint32_t>(n);
   g.key = c.take<uint32_t>(n);
   g.count = c.take<unsigned long long>(1);
-  g.temp_bytes = scan_temp_bytes((int)n);
+  g.temp_bytes = devprim::inclusive_sum_u32_temp_bytes(P);
   g.temp = c.take<char>(g.temp_bytes);
-  g.total = c.off;
+  g.total = c.total();
   return g;
 }
 
@@ -140,9 +123,9 @@ static Bins carve_bins(void* blob, int64_t I, int nt) {
   b.point_list = c.take<uint32_t>(n);
   b.slot_g = c.take<uint32_t>(n);
   b.ranges = c.take<uint2>((size_t)nt);
-  b.temp_bytes = sort_temp_bytes((int64_t)n);
+  b.temp_bytes = devprim::sort_pairs_u64_u32_temp_bytes(I);
   b.temp = c.take<char>(b.temp_bytes);
-  b.total = c.off;
+  b.total = c.total();
   return b;
 }
 
@@ -155,8 +138,24 @@ static Img carve_img(void* blob, int W, int H) {
   im.median = c.take<int32_t>(n);
   im.M1 = c.take<float>(n);
   im.M2 = c.take<float>(n);
-  im.total = c.off;
+  im.total = c.total();
   return im;
+}
+
+struct Bwd {
+  float *parts, *rows, *gsum;   // gradient rows per (instance, wave), per instance, per Gaussian
+  size_t total;
+};
+
+static Bwd carve_bwd(void* blob, int P, int64_t I) {
+  Carver c(blob);
+  Bwd b;
+  const size_t n = (size_t)(I > 0 ? I : 1);
+  b.parts = c.take<float>(n * 4 * GROW);
+  b.rows = c.take<float>(n * GROW);
+  b.gsum = c.take<float>((size_t)(P > 0 ? P : 1) * GROW);
+  b.total = c.total();
+  return b;
 }
 
 // ---------------------------------------------------------------- preprocess
@@ -709,6 +708,7 @@ static int num_tiles(int H, int W) { return ceil_div(W, TILE) * ceil_div(H, TILE
 
 using namespace pings::raster2d;
 using pings::ceil_div;
+namespace devprim = pings::devprim;
 
 PINGS_API size_t pings_raster2d_geom_bytes(int P, int image_height, int image_width) {
   (void)image_height; (void)image_width;
@@ -747,8 +747,7 @@ PINGS_API int pings_raster2d_preprocess(const pings_raster_settings* s, int P, c
                          scales, rotations, gs.rec, gs.rect, gs.tiles, gs.key, radii);
       PINGS_LAUNCH_CHECK();
     }
-    size_t tb = gs.temp_bytes;
-    PINGS_HIP_CHECK(hipcub::DeviceScan::InclusiveSum(gs.temp, tb, gs.tiles, gs.offsets, P, st));
+    if (int e = devprim::inclusive_sum_u32(gs.temp, gs.temp_bytes, gs.tiles, gs.offsets, P, st)) return e;
     hipLaunchKernelGGL(total2d_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, P, gs.tiles, gs.count);
     PINGS_LAUNCH_CHECK();
   }
@@ -787,9 +786,9 @@ PINGS_API int pings_raster2d_render(const pings_raster_settings* s, int P, int64
     hipLaunchKernelGGL(duplicate2d_kernel, dim3(ceil_div(P, 256)), dim3(256), 0, st, P, kp.gx, gs.rect, gs.tiles,
                        gs.offsets, gs.key, bs.keys, bs.slots, bs.slot_g);
     PINGS_LAUNCH_CHECK();
-    size_t tb = bs.temp_bytes;
-    PINGS_HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(bs.temp, tb, bs.keys, bs.keys_sorted, bs.slots, bs.point_list,
-                                                       (int)I, 0, 32 + tile_bits(nt), st));
+    if (int e = devprim::sort_pairs_u64_u32(bs.temp, bs.temp_bytes, bs.keys, bs.keys_sorted, bs.slots, bs.point_list, I,
+                                            0, 32 + tile_bits(nt), st))
+      return e;
     hipLaunchKernelGGL(tile_ranges2d_kernel, dim3((unsigned)ceil_div<int64_t>(I, 256)), dim3(256), 0, st, I,
                        bs.keys_sorted, bs.ranges);
     PINGS_LAUNCH_CHECK();
@@ -804,12 +803,7 @@ PINGS_API int pings_raster2d_render(const pings_raster_settings* s, int P, int64
 }
 
 PINGS_API size_t pings_raster2d_backward_bytes(int P, int64_t I) {
-  Carver c(nullptr);
-  const size_t n = (size_t)(I > 0 ? I : 1);
-  c.take<float>(n * 4 * GROW);
-  c.take<float>(n * GROW);
-  c.take<float>((size_t)(P > 0 ? P : 1) * GROW);
-  return c.off;
+  return carve_bwd(nullptr, P, I).total;
 }
 
 PINGS_API int pings_raster2d_backward(const pings_raster_settings* s, int P, int64_t I, const float* scales,
@@ -830,11 +824,8 @@ PINGS_API int pings_raster2d_backward(const pings_raster_settings* s, int P, int
   Geom gs = carve_geom(const_cast<void*>(geom_blob), P);
   Bins bs = carve_bins(const_cast<void*>(binning_blob), I, nt);
   Img im = carve_img(const_cast<void*>(image_blob), kp.W, kp.H);
-  Carver c(bwd_blob);
-  const size_t n = (size_t)(I > 0 ? I : 1);
-  float* parts = c.take<float>(n * 4 * GROW);
-  float* rows = c.take<float>(n * GROW);
-  float* gsum = c.take<float>((size_t)P * GROW);
+  const Bwd bw = carve_bwd(bwd_blob, P, I);
+  float *parts = bw.parts, *rows = bw.rows, *gsum = bw.gsum;
   if (I > 0) {
     PINGS_HIP_CHECK(hipMemsetAsync(parts, 0, sizeof(float) * (size_t)I * 4 * GROW, st));
     {

@@ -59,20 +59,6 @@ enum GradSlot {
   G_ZLO = 14, G_ZHI = 15
 };
 
-inline size_t align_up(size_t v, size_t a = 256) { return (v + a - 1) / a * a; }
-
-struct Carver {
-  char* base;
-  size_t off = 0;
-  explicit Carver(void* p) : base(reinterpret_cast<char*>(p)) {}
-  template <typename T>
-  T* take(size_t count) {
-    T* p = base ? reinterpret_cast<T*>(base + off) : nullptr;
-    off = align_up(off + count * sizeof(T));
-    return p;
-  }
-};
-
 struct FrameSummary {   // the record of a frame's one host read-back (frame_summary_kernel)
   uint32_t overflow, pad0;
   unsigned long long stats[3];   // pairs before occlusion culling, visible Gaussians, kept pairs (= instances)

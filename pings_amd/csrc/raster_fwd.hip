@@ -1190,7 +1190,7 @@ PINGS_API int pings_raster_render(const pings_raster_settings* s, int P, int64_t
     const char* z1 = I > 0 ? (s->mode == PINGS_RASTER_3DGS ? reinterpret_cast<const char*>(bs.inst_cnt + I)
                                                              : reinterpret_cast<const char*>(bs.inst_qmask + I + 1))
                            : reinterpret_cast<const char*>(bs.ranges + num_tiles);
-    PINGS_HIP_CHECK(hipMemsetAsync(bs.ranges, 0, align_up((size_t)(z1 - z0)), st));
+    PINGS_HIP_CHECK(hipMemsetAsync(bs.ranges, 0, pings::align_up((size_t)(z1 - z0)), st));
   }
   if (I > 0) {
     // tile ids fit 16 bits for every image up to 4096x4096: a 2-byte key cuts the sort traffic by a quarter

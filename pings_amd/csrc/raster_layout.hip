@@ -76,7 +76,7 @@ GeomState carve_geom(void* blob, int P, int num_tiles) {
   g.summary = c.take<FrameSummary>(1);            // what the frame's one read-back fetches
   g.temp_bytes = sort_temp_bytes((int64_t)n);
   g.temp = c.take<char>(g.temp_bytes);
-  g.total = c.off;
+  g.total = c.total();
   return g;
 }
 
@@ -115,7 +115,7 @@ BinState carve_binning(void* blob, int64_t I, int num_tiles, uint32_t seg) {
   b.seg_nrel = c.take<uint32_t>((size_t)b.seg_max_units * 4);
   b.temp_bytes = sort_temp_bytes((int64_t)n);
   b.temp = c.take<char>(b.temp_bytes);
-  b.total = c.off;
+  b.total = c.total();
   return b;
 }
 
@@ -124,7 +124,7 @@ ImageState carve_image(void* blob, int W, int H) {
   ImageState im;
   im.final_T = c.take<float>((size_t)W * H);
   im.n_contrib = c.take<uint32_t>((size_t)W * H);
-  im.total = c.off;
+  im.total = c.total();
   return im;
 }
 
@@ -142,7 +142,7 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
   b.temp_bytes = std::max(raster_scan_bytes((int64_t)ni + 1), raster_scan_bytes((int64_t)np + 1));
   b.temp = c.take<char>(b.temp_bytes);
   b.rows = c.take<float>(n * GRAD_ROW);
-  b.total = c.off;
+  b.total = c.total();
   return b;
 }
 

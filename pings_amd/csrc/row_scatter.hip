@@ -1,12 +1,11 @@
 // Deterministic scatter-add of rows (see row_scatter.hpp): counting sort by destination row + one gather pass.
-#include <hipcub/hipcub.hpp>
-
 #include "row_scatter.hpp"
+
+#include "devprim.hpp"
 
 namespace pings_rows {
 namespace {
 
-size_t au(size_t v) { return (v + 255) / 256 * 256; }
 constexpr uint32_t NO_ROW = 0xFFFFFFFFu;
 
 __global__ __launch_bounds__(256) void hist_kernel(const uint32_t* __restrict__ keys, long long n, uint32_t rows,
@@ -127,21 +126,17 @@ __global__ __launch_bounds__(256) void gather_bucket_kernel(const uint32_t* __re
 
 Plan carve(void* base, int64_t n_pairs, int64_t rows) {
   Plan p;
-  char* b = reinterpret_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = b ? b + off : nullptr; off = au(off + bytes); return r; };
+  pings::Carver c(base);
   const size_t n = (size_t)(n_pairs > 0 ? n_pairs : 1), R = (size_t)(rows > 0 ? rows : 1);
-  p.count = (uint32_t*)take((R + 1) * 4);
-  p.offset = (uint32_t*)take((R + 2) * 4);
-  p.bucket = (uint32_t*)take(n * 4);
-  p.sorted = (uint32_t*)take(n * 4);
-  p.first = (uint32_t*)take(n * 4);
+  p.count = c.take<uint32_t>(R + 1);
+  p.offset = c.take<uint32_t>(R + 2);
+  p.bucket = c.take<uint32_t>(n);
+  p.sorted = c.take<uint32_t>(n);
+  p.first = c.take<uint32_t>(n);
   p.n = n_pairs > 0 ? n_pairs : 0;
-  size_t tb = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, tb, (uint32_t*)nullptr, (uint32_t*)nullptr, (int)(R + 1));
-  p.temp_bytes = au(tb) + 256;
-  p.temp = take(p.temp_bytes);
-  p.total = off;
+  p.temp_bytes = pings::devprim::exclusive_sum_u32_temp_bytes((int64_t)R + 1);
+  p.temp = c.take<char>(p.temp_bytes);
+  p.total = c.total();
   return p;
 }
 
@@ -153,8 +148,7 @@ int build(const Plan& p, const uint32_t* keys, int64_t n, int64_t rows, hipStrea
     hipLaunchKernelGGL(hist_kernel, dim3(grid), dim3(256), 0, st, keys, (long long)n, (uint32_t)rows, p.count);
     PINGS_LAUNCH_CHECK();
   }
-  size_t tb = p.temp_bytes;
-  PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(p.temp, tb, p.count, p.offset, (int)(rows + 1), st));
+  if (int e = pings::devprim::exclusive_sum_u32(p.temp, p.temp_bytes, p.count, p.offset, rows + 1, st)) return e;
   if (n > 0) {
     hipLaunchKernelGGL(place_kernel, dim3(grid), dim3(256), 0, st, keys, (long long)n, (uint32_t)rows, p.offset,
                        p.count, p.bucket);
@@ -203,12 +197,28 @@ __global__ __launch_bounds__(256) void u32_from_i64_kernel(const long long* __re
   const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   if (p < n) o[p] = (uint32_t)a[p];
 }
-size_t au2(size_t v) { return (v + 255) / 256 * 256; }
+
+// the blobs of the C entry points: the pairs' keys as 32-bit words (and their source rows), then the plan
+struct RowsScratch {
+  uint32_t *keys, *srow;
+  pings_rows::Plan plan;
+  size_t total;
+};
+RowsScratch carve_rows(void* base, int64_t n_pairs, int64_t rows, bool with_src_row) {
+  pings::Carver c(base);
+  RowsScratch s{};
+  const size_t n = (size_t)(n_pairs > 0 ? n_pairs : 1);
+  s.keys = c.take<uint32_t>(n);
+  if (with_src_row) s.srow = c.take<uint32_t>(n);
+  char* plan = c.take<char>(pings_rows::carve(nullptr, n_pairs, rows).total);
+  s.plan = pings_rows::carve(plan, n_pairs, rows);
+  s.total = c.total();
+  return s;
+}
 }  // namespace
 
 PINGS_API size_t pings_rows_scatter_add_scratch_bytes(int64_t n_pairs, int64_t rows) {
-  const size_t n = (size_t)(n_pairs > 0 ? n_pairs : 1);
-  return pings_rows::carve(nullptr, n_pairs, rows).total + 2 * au2(n * 4);
+  return carve_rows(nullptr, n_pairs, rows, true).total;
 }
 
 PINGS_API int pings_rows_scatter_add(const int64_t* dst_row, int64_t n_pairs, const float* src, int64_t ld,
@@ -218,11 +228,9 @@ PINGS_API int pings_rows_scatter_add(const int64_t* dst_row, int64_t n_pairs, co
   PINGS_ARG_CHECK(scratch && out && (n_pairs == 0 || (dst_row && src)), "null pointer");
   hipStream_t st = pings::as_stream(stream);
   pings::prof::Scope ps("rows_scatter_add", st);
-  const size_t n = (size_t)(n_pairs > 0 ? n_pairs : 1);
-  char* base = reinterpret_cast<char*>(scratch);
-  uint32_t* keys = reinterpret_cast<uint32_t*>(base);
-  uint32_t* srow = reinterpret_cast<uint32_t*>(base + au2(n * 4));
-  pings_rows::Plan plan = pings_rows::carve(base + 2 * au2(n * 4), n_pairs, rows);
+  const RowsScratch s = carve_rows(scratch, n_pairs, rows, true);
+  uint32_t *keys = s.keys, *srow = s.srow;
+  const pings_rows::Plan& plan = s.plan;
   const unsigned grid = (unsigned)((n_pairs + 255) / 256);
   if (n_pairs > 0) {
     hipLaunchKernelGGL(keys_from_i64_kernel, dim3(grid), dim3(256), 0, st, (const long long*)dst_row,
@@ -241,18 +249,16 @@ PINGS_API int pings_rows_scatter_add(const int64_t* dst_row, int64_t n_pairs, co
 // The same in two steps, for several tables that share one destination index (geo and colour features of one query
 // batch): build the plan once, apply it per table.  `plan` = pings_rows_plan_bytes(n_pairs, rows) bytes, caller-owned.
 PINGS_API size_t pings_rows_plan_bytes(int64_t n_pairs, int64_t rows) {
-  const size_t n = (size_t)(n_pairs > 0 ? n_pairs : 1);
-  return pings_rows::carve(nullptr, n_pairs, rows).total + au2(n * 4);
+  return carve_rows(nullptr, n_pairs, rows, false).total;
 }
 
 PINGS_API int pings_rows_plan_build(const int64_t* dst_row, int64_t n_pairs, int64_t rows, void* plan, void* stream) {
   PINGS_ARG_CHECK(rows > 0 && n_pairs >= 0 && plan && (n_pairs == 0 || dst_row), "bad arguments");
   hipStream_t st = pings::as_stream(stream);
   pings::prof::Scope ps("rows_plan_build", st);
-  const size_t n = (size_t)(n_pairs > 0 ? n_pairs : 1);
-  char* base = reinterpret_cast<char*>(plan);
-  uint32_t* keys = reinterpret_cast<uint32_t*>(base);
-  pings_rows::Plan pl = pings_rows::carve(base + au2(n * 4), n_pairs, rows);
+  const RowsScratch s = carve_rows(plan, n_pairs, rows, false);
+  uint32_t* keys = s.keys;
+  const pings_rows::Plan& pl = s.plan;
   if (n_pairs > 0) {
     hipLaunchKernelGGL(keys_from_i64_kernel, dim3((unsigned)((n_pairs + 255) / 256)), dim3(256), 0, st,
                        (const long long*)dst_row, (long long)n_pairs, (uint32_t)rows, keys);
@@ -267,8 +273,6 @@ PINGS_API int pings_rows_plan_apply(const void* plan, int64_t n_pairs, int64_t r
   PINGS_ARG_CHECK(n_pairs == 0 || src, "null source");
   hipStream_t st = pings::as_stream(stream);
   pings::prof::Scope ps("rows_plan_apply", st);
-  const size_t n = (size_t)(n_pairs > 0 ? n_pairs : 1);
-  char* base = reinterpret_cast<char*>(const_cast<void*>(plan));
-  pings_rows::Plan pl = pings_rows::carve(base + au2(n * 4), n_pairs, rows);
-  return pings_rows::gather_sum(pl, rows, F, src, ld, nullptr, w, out, st);
+  const RowsScratch s = carve_rows(const_cast<void*>(plan), n_pairs, rows, false);
+  return pings_rows::gather_sum(s.plan, rows, F, src, ld, nullptr, w, out, st);
 }

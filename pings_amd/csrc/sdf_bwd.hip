@@ -565,8 +565,6 @@ __global__ __launch_bounds__(256) void sdf_param_reduce_kernel(const float* __re
   else db2[0] = s;
 }
 
-size_t au(size_t v) { return (v + 255) / 256 * 256; }
-
 int grad_blocks(int64_t B) {
   const long long want = (B + WPB - 1) / WPB;
   return (int)(want < 1024 ? (want > 0 ? want : 1) : 1024);
@@ -582,16 +580,14 @@ struct Scratch {
 Scratch carve(void* base, int64_t B, int nnk, int F, int H, int64_t table_rows) {
   Scratch s;
   const size_t n = (size_t)(B > 0 ? B : 1) * nnk;
-  char* p = reinterpret_cast<char*>(base);
-  size_t off = 0;
-  auto take = [&](size_t bytes) { char* r = p ? p + off : nullptr; off = au(off + bytes); return r; };
-  s.rows = (float*)take(n * F * sizeof(float));
-  s.pair_w = (float*)take(n * 4);
-  s.keys = (uint32_t*)take(n * 4);
-  s.src_row = (uint32_t*)take(n * 4);
-  s.partials = (float*)take((size_t)grad_blocks(B) * ((size_t)H * (F + 5) + 1) * sizeof(float));
-  s.plan = take(pings_rows::carve(nullptr, (int64_t)n, table_rows).total);
-  s.total = off;
+  pings::Carver c(base);
+  s.rows = c.take<float>(n * F);
+  s.pair_w = c.take<float>(n);
+  s.keys = c.take<uint32_t>(n);
+  s.src_row = c.take<uint32_t>(n);
+  s.partials = c.take<float>((size_t)grad_blocks(B) * ((size_t)H * (F + 5) + 1));
+  s.plan = c.take<char>(pings_rows::carve(nullptr, (int64_t)n, table_rows).total);
+  s.total = c.total();
   return s;
 }
 

@@ -17,9 +17,9 @@
 //
 // Raw MLP outputs are [n, d*k] row-major, which the reference reinterprets as [n*k, d] (:632,645,665,687,716):
 // Gaussian g = i*k + j of neural point i owns columns j*d .. j*d+d-1, i.e. floats g*d .. g*d+d-1.
-#include <hipcub/hipcub.hpp>
 
 #include "common.hpp"
+#include "devprim.hpp"
 
 namespace {
 
@@ -357,10 +357,19 @@ int check_params(const pings_spawn_params* p) {
   return PINGS_OK;
 }
 
-size_t scan_temp_bytes(int64_t nk) {
-  size_t b = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, b, (int32_t*)nullptr, (int32_t*)nullptr, (int)nk);
-  return (b + 255) & ~(size_t)255;
+struct PlanScratch {
+  int32_t* flag;   // [n * k] 1 where the candidate is kept
+  void* temp;
+  size_t temp_bytes, total;
+};
+PlanScratch carve_plan(void* base, int64_t nk) {
+  pings::Carver c(base);
+  PlanScratch s;
+  s.flag = c.take<int32_t>((size_t)(nk > 0 ? nk : 1));
+  s.temp_bytes = pings::devprim::exclusive_sum_i32_temp_bytes(nk);
+  s.temp = c.take<char>(s.temp_bytes);
+  s.total = c.total();
+  return s;
 }
 
 int grid_rows16(int n) {  // one 16-lane group per row, 16 rows per 256-thread workgroup
@@ -431,8 +440,7 @@ PINGS_API int pings_spawn_gather_backward(int n, const int64_t* sel, const float
 }
 
 PINGS_API size_t pings_spawn_plan_scratch_bytes(int64_t num_gaussians) {
-  const int64_t nk = num_gaussians > 0 ? num_gaussians : 1;
-  return (size_t)nk * sizeof(int32_t) + 256 + scan_temp_bytes(nk);
+  return carve_plan(nullptr, num_gaussians).total;
 }
 
 PINGS_API int pings_spawn_plan(const pings_spawn_params* p, const float* alpha_raw, const float* scale_raw,
@@ -457,13 +465,12 @@ PINGS_API int pings_spawn_plan_dyn(const pings_spawn_params* p, const int32_t* n
   pings::prof::Scope sc("spawn_plan", st);
   SpawnArgs a{};
   a.p = *p; a.alpha_raw = alpha_raw; a.scale_raw = scale_raw; a.dist_ratio = dist_ratio; a.n_dev = n_rows_dev;
-  int32_t* flag = reinterpret_cast<int32_t*>(scratch);
-  void* temp = reinterpret_cast<char*>(scratch) + (((size_t)nk * sizeof(int32_t) + 255) & ~(size_t)255);
-  size_t tb = scan_temp_bytes(nk);
+  const PlanScratch s = carve_plan(scratch, nk);
+  int32_t* flag = s.flag;
   const int blocks = (int)pings::ceil_div<int64_t>(nk, 256);
   plan_kernel<<<blocks, 256, 0, st>>>(a, nk, flag);
   PINGS_LAUNCH_CHECK();
-  PINGS_HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(temp, tb, flag, dest, (int)nk, st));
+  if (int e = pings::devprim::exclusive_sum_i32(s.temp, s.temp_bytes, flag, dest, nk, st)) return e;
   plan_finish_kernel<<<blocks, 256, 0, st>>>(nk, flag, dest, count, nan_flag);
   PINGS_LAUNCH_CHECK();
   return PINGS_OK;

@@ -269,7 +269,7 @@ TileSortScratch carve_tile_sort(void* blob, int64_t n) {
   s.vals_tmp = c.take<uint32_t>(m);
   s.temp_bytes = align_up(tile_sort_library_bytes(n)) + 256;
   s.temp = c.take<char>(s.temp_bytes);
-  s.total = c.off;
+  s.total = c.total();
   return s;
 }
 }  // namespace

@@ -13,9 +13,9 @@
 //   update    one workgroup per touched block, one thread per voxel for the whole launch: project, gather, average
 //   densify   a box of grid points as dense arrays; vertices: marching-cubes keys -> positions from global integers
 // Integer atomics only; every float of the store is the same from run to run.
-#include <hipcub/hipcub.hpp>
 
 #include "common.hpp"
+#include "devprim.hpp"
 
 namespace {
 
@@ -328,12 +328,20 @@ bool table_ok(const void* tkeys, const void* tslots, i64 tsize) {
   return tkeys && tslots && tsize >= 64 && tsize < ((i64)1 << 31) && (tsize & (tsize - 1)) == 0;
 }
 
-size_t sort_bytes(i64 n) {
-  size_t tb = 0;
-  (void)hipcub::DeviceRadixSort::SortKeys(nullptr, tb, (const i64*)nullptr, (i64*)nullptr, (int)n);
-  return tb;
+struct AssignScratch {
+  i64* sorted;   // the new block keys in ascending order
+  void* temp;
+  size_t temp_bytes, total;
+};
+AssignScratch carve_assign(void* base, i64 n_new) {
+  pings::Carver c(base);
+  AssignScratch s;
+  s.sorted = c.take<i64>((size_t)n_new);
+  s.temp_bytes = pings::devprim::sort_keys_i64_temp_bytes(n_new);
+  s.temp = c.take<char>(s.temp_bytes);
+  s.total = c.total();
+  return s;
 }
-size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
 
 constexpr i64 kMaxBoxPoints = (i64)1 << 40;
 
@@ -392,7 +400,7 @@ PINGS_API int pings_tsdf_touch(const float* depth, int height, int width, const 
 
 PINGS_API size_t pings_tsdf_assign_scratch_bytes(int64_t n_new) {
   if (n_new <= 0 || n_new >= (i64)0x7FFFFFFF) return 0;
-  return align256(sizeof(i64) * (size_t)n_new) + align256(sort_bytes(n_new));
+  return carve_assign(nullptr, n_new).total;
 }
 
 PINGS_API int pings_tsdf_assign(const int64_t* new_keys, int64_t n_new, int64_t base_slot, int64_t capacity,
@@ -405,11 +413,9 @@ PINGS_API int pings_tsdf_assign(const int64_t* new_keys, int64_t n_new, int64_t 
   PINGS_ARG_CHECK(base_slot + n_new <= capacity && capacity < (i64)0x7FFFFFFF, "the store is too small for the new blocks");
   hipStream_t st = pings::as_stream(stream);
   pings::prof::Scope sc("tsdf_assign", st);
-  i64* sorted = static_cast<i64*>(scratch);
-  void* temp = static_cast<char*>(scratch) + align256(sizeof(i64) * (size_t)n_new);
-  size_t tb = sort_bytes(n_new);
-  PINGS_HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(temp, tb, new_keys, sorted, (int)n_new, 0, 63, st));
-  return pings::launch(tsdf_assign_kernel, dim3((unsigned)n_new), kBlock, 0, st, (const i64*)sorted, n_new, base_slot,
+  const AssignScratch s = carve_assign(scratch, n_new);
+  if (int e = pings::devprim::sort_keys_i64(s.temp, s.temp_bytes, new_keys, s.sorted, n_new, 0, 63, st)) return e;
+  return pings::launch(tsdf_assign_kernel, dim3((unsigned)n_new), kBlock, 0, st, (const i64*)s.sorted, n_new, base_slot,
                        tkeys, tslots, tsize, block_keys, tsdf, weight, color);
 }
 
