@@ -209,6 +209,11 @@ PINGS_API int pings_raster_debug_image(const void* image_blob, int image_height,
 PINGS_API int pings_raster_debug_occlusion(const void* geom_blob, int P, int image_height, int image_width,
                                            uint32_t* occ_bucket, uint16_t* occ_bsat, int32_t* occ_nb,
                                            void* stream);
+/* The rank bucket of the occlusion budget for each of `n` depth ranks, computed on the HOST by the function the
+ * kernels call (host pointers, no GPU work): buckets[i] = bucket of ranks[i] among `nvalid` surviving Gaussians with
+ * `occ_nb` buckets per tile.  Non-decreasing in the rank, 0 for rank 0, below occ_nb. */
+PINGS_API int pings_raster_rank_bucket(const int32_t* ranks, int64_t n, int occ_nb, uint32_t nvalid,
+                                       uint32_t* buckets);
 
 
 /* ------------------------------------------- 2D Gaussian splatting rasteriser

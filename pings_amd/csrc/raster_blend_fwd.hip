@@ -902,16 +902,17 @@ __global__ __launch_bounds__(256) void per_gaussian_sum_kernel(
     int P, const uint32_t* __restrict__ gidx_sorted, const uint32_t* __restrict__ nvalid,
     const uint32_t* __restrict__ offsets_sorted, const uint32_t* __restrict__ tiles_sorted,
     const T* __restrict__ inst, T* __restrict__ out) {
-  // one lane per DEPTH RANK, all P of them: gidx_sorted is a permutation of the Gaussians (the culled ones fill the
-  // ranks from nvalid on), so every entry of `out` is written exactly once and neither the rectangle nor the rank of
-  // a Gaussian is looked up.  The run of rank r is found with two coalesced words; the long runs sit at neighbouring
-  // ranks and are dealt to different waves (strided_rank).
+  // one lane per DEPTH RANK: neither the rectangle nor the rank of a Gaussian is looked up.  `out` is all zeros when
+  // this launch starts (duplicate_kernel of the same render call streams them out in Gaussian order), and only a rank
+  // that kept a tile — on the headline one survivor in a hundred — reads its offset and its Gaussian's index and
+  // stores a sum: no scattered store per Gaussian.  The run of such a rank is found with two coalesced words; the long
+  // runs sit at neighbouring ranks and are dealt to different waves (strided_rank).
   const int r = strided_rank(P);
   const int lane = threadIdx.x & 63;
   uint32_t n = 0, base = 0;
   if (r >= 0 && (uint32_t)r < *nvalid) {
     n = tiles_sorted[r];
-    base = offsets_sorted[r] - n;
+    if (n != 0u) base = offsets_sorted[r] - n;
   }
   T sum = (T)0;
   if (n <= (uint32_t)SMALL_RUN)
@@ -939,7 +940,7 @@ __global__ __launch_bounds__(256) void per_gaussian_sum_kernel(
     }
     if (lane == src) sum = acc;
   }
-  if (r >= 0) out[gidx_sorted[r]] = sum;
+  if (n != 0u) out[gidx_sorted[r]] = sum;
 }
 
 // ---------------------------------------------------------------- host: the forward kernels of a BlendPlan
@@ -993,6 +994,8 @@ static int launch_blend_fwd_wave(const KParams& kp, const BlendPlan& plan, int64
   return PINGS_OK;
 }
 
+// With I > 0 `per_gaussian` must be all zeros on `st` before this call: per_gaussian_sum_kernel stores only the sums of
+// the Gaussians that kept a tile.  pings_raster_render's duplicate_kernel launch, which runs whenever I > 0, writes them.
 int launch_blend_fwd(int mode, const KParams& kp, const BlendPlan& plan, int P, int64_t I, const GeomState& gs,
                      const BinState& bs, const ImageState& im, float* out_color, float* out_normal, float* out_depth,
                      float* out_alpha, void* per_gaussian, hipStream_t st) {

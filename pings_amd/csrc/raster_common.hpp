@@ -38,6 +38,15 @@ constexpr uint32_t DS_LIMIT = 4096u;  // bucket population beyond which the libr
 constexpr int DS_SHARDS = 64;  // single-address atomics serialise at ~12 ns each on this part: spread them
 // header words: [0, 64) max key shards, [64, 128) max ~key shards, 128 kmin, 129 shift, 130 overflow flag
 constexpr int DS_KMIN = 2 * DS_SHARDS, DS_SHIFT = DS_KMIN + 1, DS_FLAG = DS_KMIN + 2, DS_HEAD = DS_KMIN + 8;
+// The frame statistics (GeomState::stats), STAT_SHARDS words each so that thousands of waves do not add to one word:
+// [STAT_PAIRS + shard] (Gaussian, tile) pairs before occlusion culling and [STAT_VISIBLE + shard] Gaussians with a
+// tile, both from preprocess_kernel; [STAT_KEPT + shard] kept pairs from count_kept_kernel; word STAT_WORDS - 1 holds
+// occ_bmax.  The kept words come last, next to occ_bmax: a retry of the depth sort clears those two
+// (STAT_RETRY_WORDS from STAT_KEPT on) and keeps what the preprocess pass, which does not run again, left in the others.
+constexpr int STAT_SHARDS = 256;
+constexpr int STAT_PAIRS = 0, STAT_VISIBLE = STAT_SHARDS, STAT_KEPT = 2 * STAT_SHARDS;
+constexpr int STAT_BMAX = 3 * STAT_SHARDS, STAT_WORDS = STAT_BMAX + 1, STAT_RETRY_WORDS = STAT_WORDS - STAT_KEPT;
+static_assert((STAT_SHARDS & (STAT_SHARDS - 1)) == 0, "the shard of a wave is its number modulo a power of two");
 // occlusion culling of instances (see occl_budget_kernel)
 constexpr float OCC_THR = 9.5f;     // > -ln(T_EPS) = 9.21: transmittance bound that guarantees every pixel has stopped
 constexpr float OCC_FIX = 4096.f;   // fixed-point scale of the budget (integer atomics: order independent)
@@ -84,7 +93,8 @@ struct GeomState {
   char* zero_begin; size_t zero_bytes;      // occ_bucket .. stats .. ds_head: the frame's one memset
   size_t ds_words;                          //   [DS_NB + blocks + 1] their exclusive scan; ds_words = memset extent
   uint32_t* ds_idx;                         //   [P] Gaussian ids in bucket order (keys go to depth_key_sorted)
-  unsigned long long* stats;                // [2] pairs before occlusion culling, visible Gaussians
+  unsigned long long* stats;                // [3][shards] pairs before occlusion culling, Gaussians with a tile (both from
+                                            //     preprocess_kernel), kept pairs (count_kept_kernel); then occ_bmax
   FrameSummary* summary;
   int occ_nb, occ_words;                    // rank buckets per tile; 64-bit words per bucket of occ_mask
   char* temp;
@@ -286,6 +296,47 @@ __device__ inline int strided_rank(int P) {
   const int wave = (int)(blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
   const int r = dealt_rank(num_waves, wave, (int)(threadIdx.x & 63));
   return r < P ? r : -1;
+}
+
+// ---------------------------------------------------------------- rank buckets of the occlusion bound
+// The occlusion budget is kept per (tile, rank bucket), and a tile keeps every rank up to the END of the bucket in
+// which its budget saturates: the width of that bucket is what it keeps for nothing.  Where tiles saturate at all they
+// do so within the first few hundred to few thousand depth ranks, whatever the number of survivors, so the buckets are
+// fine at the front and pay for it with wider ones behind — a log-linear map in integer arithmetic:
+//   * FRONT: ranks in units of w0 = 2^RB_LW; the first s = 2^RB_LS buckets hold one unit each, then every octave of
+//     the unit number q = r / w0 is cut into s buckets: q in [s 2^k, s 2^(k+1)) has buckets of w0 2^k ranks.  A bucket
+//     that starts at rank r is at most max(w0, r / s) ranks wide.  Section 0 is the s unit buckets, section j >= 1 the
+//     octave k = j - 1; the front is the first J sections, ranks [0, w0 s 2^(J-1)), buckets [0, s J);
+//   * J: as many sections as keep the bucket width at or below today's equal share eq = ceil(nvalid / nb) — a front
+//     bucket is never wider than an equal one was — and at most nb / 2 buckets;
+//   * BEHIND: the remaining ranks dealt equally to the remaining buckets, at least nb / 2 of them: no bucket is wider
+//     than 2 eq, so a tile that saturates deep in the order keeps at most one equal share more than it did.
+// Any monotone partition of the ranks is a valid bucket map (the bound only needs buckets in depth order); this one
+// is a function of (r, nb, nvalid) alone, so the three kernels that call it agree without a table.  A rank from
+// nvalid on (a culled Gaussian: no tiles) gets the last bucket.  pings_raster_rank_bucket exports it to the host tests.
+constexpr int RB_LW = 4, RB_LS = 4;
+__host__ __device__ inline uint32_t rank_bucket_log2(uint32_t x) { return 31u - (uint32_t)__builtin_clz(x); }   // x > 0
+__host__ __device__ inline uint32_t rank_bucket(int r, int nb, uint32_t nvalid) {
+  if (r < 0 || nvalid == 0u) return 0u;
+  const uint32_t ur = (uint32_t)r, unb = (uint32_t)nb;
+  if (ur >= nvalid) return unb - 1u;
+  const uint32_t eq = (nvalid - 1u) / unb + 1u;
+  uint32_t J = 0u;
+  if ((eq >> RB_LW) != 0u) {
+    J = rank_bucket_log2(eq >> RB_LW) + 2u;
+    if (J > (unb >> (RB_LS + 1))) J = unb >> (RB_LS + 1);
+  }
+  const uint32_t front_ranks = J ? 1u << (RB_LW + RB_LS + J - 1u) : 0u, front_buckets = J << RB_LS;
+  if (ur < front_ranks) {
+    const uint32_t q = ur >> RB_LW;
+    if ((q >> RB_LS) == 0u) return q;
+    const uint32_t k = rank_bucket_log2(q) - RB_LS;
+    return (k << RB_LS) + (q >> k);     // ((k + 1) s) + (q >> k) - s
+  }
+  // here front_ranks <= r < nvalid: at least one rank and nb / 2 buckets are left
+  const uint32_t b = front_buckets + (uint32_t)(((unsigned long long)(ur - front_ranks) * (unb - front_buckets)) /
+                                                (unsigned long long)(nvalid - front_ranks));
+  return b < unb ? b : unb - 1u;
 }
 
 // Two fp32 values in one VGPR pair: + - * on f2 compile to v_pk_add_f32 / v_pk_mul_f32, fma2 to v_pk_fma_f32.  Each

@@ -50,13 +50,14 @@ __global__ __launch_bounds__(256) void mark_visible_kernel(const float* __restri
   present[i] = (pz > NEAR_Z) && (depth_only || ((nx >= -1.3f) && (nx <= 1.3f) && (ny >= -1.3f) && (ny <= 1.3f)));
 }
 
-// One Gaussian of preprocess_kernel; returns its depth key (CULLED_KEY if it was culled).
+// One Gaussian of preprocess_kernel; returns its depth key (CULLED_KEY if it was culled) and the tiles of its rectangle.
 template <int MODE>
 __device__ inline uint32_t preprocess_gaussian(
     const KParams& p, int g, const float* __restrict__ means3D, const float* __restrict__ colors,
     const float* __restrict__ opacities, const float* __restrict__ scales,
     const float* __restrict__ rotations, float4* __restrict__ rec, uint4* __restrict__ rect,
-    uint32_t* __restrict__ depth_key, uint32_t* __restrict__ gidx, int32_t* __restrict__ radii) {
+    uint32_t* __restrict__ depth_key, uint32_t* __restrict__ gidx, int32_t* __restrict__ radii,
+    uint32_t& tiles_out) {   // tiles_out: tiles of its rectangle, 0 if it was culled
   const float* V = p.view;
   const float* Pm = p.proj_raw;
 
@@ -226,6 +227,7 @@ __device__ inline uint32_t preprocess_gaussian(
   depth_key[g] = key;
   rect[g] = rc;
   radii[g] = rad;
+  tiles_out = rc.w;
   if (key != CULLED_KEY) {  // nobody reads the record of a culled Gaussian (two thirds of Metric-1's cloud)
     rec[4 * g + 0] = make_float4(mx, my, opac, pz);
     rec[4 * g + 1] = make_float4(conic_x, conic_y, conic_z, rz);
@@ -235,21 +237,41 @@ __device__ inline uint32_t preprocess_gaussian(
   return key;
 }
 
+// the shard of the frame statistics (STAT_*: raster_common.hpp) this wave adds to
+__device__ inline int stat_shard() {
+  return (int)((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (STAT_SHARDS - 1));
+}
+
 // `ds_head` (bucket depth sort only, else null): the key range of the survivors, as the largest key and the largest
 // ~key of every workgroup, each into one of DS_SHARDS words — the keys are in registers here; a pass of its own would
 // read them back from HBM.  The header must have been cleared before this launch.
+// `stats`: the footprint statistic behind the blend kernels' pixels-per-lane choice, all (Gaussian, tile) pairs before
+// occlusion culling and the Gaussians that own one — the rectangle is in registers here, and the sums do not depend
+// on the depth order.  Cleared before this launch.
 template <int MODE>
 __global__ __launch_bounds__(256) void preprocess_kernel(
     KParams p, const float* __restrict__ means3D, const float* __restrict__ colors,
     const float* __restrict__ opacities, const float* __restrict__ scales,
     const float* __restrict__ rotations, float4* __restrict__ rec, uint4* __restrict__ rect,
     uint32_t* __restrict__ depth_key, uint32_t* __restrict__ gidx, int32_t* __restrict__ radii,
-    uint32_t* __restrict__ ds_head) {
+    uint32_t* __restrict__ ds_head, unsigned long long* __restrict__ stats) {
   __shared__ uint32_t sm[8];
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  uint32_t key = CULLED_KEY;
+  uint32_t key = CULLED_KEY, tiles = 0u;
   if (g < p.P)
-    key = preprocess_gaussian<MODE>(p, g, means3D, colors, opacities, scales, rotations, rec, rect, depth_key, gidx, radii);
+    key = preprocess_gaussian<MODE>(p, g, means3D, colors, opacities, scales, rotations, rec, rect, depth_key, gidx, radii,
+                                    tiles);
+  {
+    const unsigned long long vis = __ballot(tiles != 0u);
+    uint32_t tot = tiles;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) tot += (uint32_t)__shfl_xor((int)tot, o, 64);
+    if ((threadIdx.x & 63) == 0 && tot) {
+      const int shard = stat_shard();
+      atomicAdd(stats + STAT_PAIRS + shard, (unsigned long long)tot);
+      atomicAdd(stats + STAT_VISIBLE + shard, (unsigned long long)__popcll(vis));
+    }
+  }
   if (!ds_head) return;
   uint32_t mx = key != CULLED_KEY ? key : 0u, mn = key != CULLED_KEY ? ~key : 0u;  // max key, max ~key over valid entries
 #pragma unroll
@@ -271,7 +293,6 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
 }
 
 constexpr int SMALL_RECT = 8;
-constexpr int STAT_SHARDS = 256;
 
 // Walks the tile rectangles of the depth-ranked Gaussians: one lane per rank; rectangles of more than SMALL_RECT
 // tiles are walked by the whole wave, 64 tiles per step (`coop(src_lane, k, active)` runs in every lane with its
@@ -624,11 +645,7 @@ __global__ __launch_bounds__(64) void count_valid_kernel(int P, const uint32_t* 
   if (lane == 0) *nvalid = (uint32_t)lo;
 }
 
-__device__ inline uint32_t rank_bucket(int r, int nb, uint32_t nvalid) {
-  if (r < 0 || nvalid == 0u) return 0u;
-  const uint32_t b = (uint32_t)(((unsigned long long)r * (unsigned long long)nb) / (unsigned long long)nvalid);
-  return min(b, (uint32_t)nb - 1u);
-}
+// rank_bucket (the rank bucket of a depth rank): raster_common.hpp
 
 // The budget pass.  A lane owns one depth rank: its inner rectangle, the six record values tile_min_alpha reads and its
 // rank bucket.  DENSE (the product): the (rank, tile) pairs of the workgroup's 256 ranks are numbered through — one
@@ -801,7 +818,8 @@ __global__ __launch_bounds__(512) void occl_scan_kernel(int num_tiles, int nb, c
 // kept tiles per depth rank (the Gaussian's rank bucket must not exceed the tile's last needed bucket).  A rank whose
 // bucket lies behind the last one ANY tile needs (occl_scan_kernel's bmax) keeps nothing and walks nothing: where every
 // tile saturates (the headline, closed rooms) that is most of the visible Gaussians; where one tile sees sky bmax is
-// nb - 1 and nothing changes.  Its rectangle is still loaded: the footprint statistics count every pair.
+// nb - 1 and nothing changes.  Such a rank loads neither its Gaussian's index nor its rectangle: it stores its zero and
+// is done (the footprint statistics, which count every pair, are preprocess_kernel's).
 __global__ __launch_bounds__(256) void count_kept_kernel(int P, int gx, int nb, int words,
                                                          const uint32_t* __restrict__ gidx_sorted,
                                                          const uint4* __restrict__ rect,
@@ -809,13 +827,13 @@ __global__ __launch_bounds__(256) void count_kept_kernel(int P, int gx, int nb, 
                                                          const uint32_t* __restrict__ nvalid,
                                                          const uint32_t* __restrict__ bmax,
                                                          uint32_t* __restrict__ tiles_sorted,
-                                                         unsigned long long* __restrict__ pairs_full) {
+                                                         unsigned long long* __restrict__ stats) {
   const int r = strided_rank(P);
   const int lane = threadIdx.x & 63;
   const uint32_t nv = *nvalid;
-  const RectLane me = rect_lane(r, gidx_sorted, rect, nv);
   const uint32_t bk = rank_bucket(r, nb, nv);
-  const uint32_t items = bk <= *bmax ? rect_items(me) : 0u;
+  const RectLane me = rect_lane(bk <= *bmax ? r : -1, gidx_sorted, rect, nv);
+  const uint32_t items = rect_items(me);
   uint32_t kept = 0, acc = 0;
   if (items != 0u && items <= (uint32_t)SMALL_ITEMS)
     walk_items_serial(me, items, gx, mask + (size_t)bk * words,
@@ -833,22 +851,12 @@ __global__ __launch_bounds__(256) void count_kept_kernel(int P, int gx, int nb, 
       [&](int, unsigned long long bits) { acc += (uint32_t)__popcll(bits); });
   flush();
   if (r >= 0) tiles_sorted[r] = kept;
-  // footprint statistic for the blend kernels' pixels-per-lane choice: all (Gaussian, tile) pairs before culling
-  uint32_t tot = me.n;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) tot += (uint32_t)__shfl_xor((int)tot, off, 64);
-  const unsigned long long vis = __ballot(me.n != 0u);
   // the kept total once more in 64 bits: the instance offsets are a 32-bit scan, which a degenerate frame (huge
   // footprints with the occlusion bound off) could wrap without anyone noticing
   uint32_t kept_w = r >= 0 ? kept : 0u;
 #pragma unroll
   for (int off = 32; off > 0; off >>= 1) kept_w += (uint32_t)__shfl_xor((int)kept_w, off, 64);
-  if (lane == 0 && tot) {  // sharded: thousands of waves adding to one word serialise
-    const int shard = (int)((blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6)) & (STAT_SHARDS - 1));
-    atomicAdd(pairs_full + 3 * shard, (unsigned long long)tot);
-    atomicAdd(pairs_full + 3 * shard + 1, (unsigned long long)__popcll(vis));
-    atomicAdd(pairs_full + 3 * shard + 2, (unsigned long long)kept_w);
-  }
+  if (lane == 0 && kept_w) atomicAdd(stats + STAT_KEPT + stat_shard(), (unsigned long long)kept_w);
 }
 
 // Emits the kept (tile id, slot) instances in depth order; gval[slot] = Gaussian id.  A Gaussian that keeps nothing
@@ -864,15 +872,22 @@ __global__ __launch_bounds__(256) void duplicate_kernel(int P, int gx, int nb, i
                                                          const unsigned long long* __restrict__ mask,
                                                          const uint32_t* __restrict__ nvalid,
                                                          KeyT* __restrict__ tile_key,
-                                                         uint32_t* __restrict__ gval) {
+                                                         uint32_t* __restrict__ gval,
+                                                         uint32_t* __restrict__ per_gaussian) {
+  // the zeros of the per-Gaussian sums (per_gaussian_sum_kernel stores only where a Gaussian kept a tile): one
+  // coalesced word per thread, in Gaussian order — the launch has one thread per Gaussian anyway
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < P) per_gaussian[i] = 0u;
   const int r = strided_rank(P);
   const int lane = threadIdx.x & 63;
-  const uint32_t nv = *nvalid;
-  const RectLane me = rect_lane(r, gidx_sorted, rect, nv);
-  const uint32_t bk = rank_bucket(r, nb, nv);
+  // the kept count first (one coalesced word): the ranks that keep nothing — on the headline all but one in a
+  // hundred of the survivors — load neither index, rectangle nor offset
   const uint32_t kept = r >= 0 ? tiles_sorted[r] : 0u;
-  uint32_t o = r >= 0 ? offsets_sorted[r] - kept : 0u;  // first slot of this Gaussian
-  const uint32_t items = kept != 0u ? rect_items(me) : 0u;
+  const uint32_t nv = *nvalid;
+  const RectLane me = rect_lane(kept != 0u ? r : -1, gidx_sorted, rect, nv);
+  const uint32_t bk = kept != 0u ? rank_bucket(r, nb, nv) : 0u;
+  uint32_t o = kept != 0u ? offsets_sorted[r] - kept : 0u;  // first slot of this Gaussian
+  const uint32_t items = rect_items(me);
   const bool coop = items > (uint32_t)SMALL_ITEMS || kept > SMALL_KEPT;
   if (items != 0u && !coop)
     walk_items_serial(me, items, gx, mask + (size_t)bk * words, [&](int s, unsigned long long bits) {
@@ -948,7 +963,7 @@ __global__ __launch_bounds__(64) void frame_summary_kernel(const uint32_t* __res
   const int lane = threadIdx.x;
   unsigned long long a0 = 0, a1 = 0, a2 = 0;
   for (int i = lane; i < STAT_SHARDS; i += 64) {
-    a0 += shards[3 * i]; a1 += shards[3 * i + 1]; a2 += shards[3 * i + 2];
+    a0 += shards[STAT_PAIRS + i]; a1 += shards[STAT_VISIBLE + i]; a2 += shards[STAT_KEPT + i];
   }
   part[0][lane] = a0; part[1][lane] = a1; part[2][lane] = a2;
   __syncthreads();
@@ -999,6 +1014,13 @@ PINGS_API int pings_raster_mark_visible(const float* positions, int N,
   return PINGS_OK;
 }
 
+PINGS_API int pings_raster_rank_bucket(const int32_t* ranks, int64_t n, int occ_nb, uint32_t nvalid,
+                                       uint32_t* buckets) {
+  PINGS_ARG_CHECK(n >= 0 && occ_nb > 0 && (n == 0 || (ranks && buckets)), "null pointer / non-positive bucket count");
+  for (int64_t i = 0; i < n; ++i) buckets[i] = rank_bucket(ranks[i], occ_nb, nvalid);
+  return PINGS_OK;
+}
+
 PINGS_API int pings_raster_preprocess(const pings_raster_settings* s, int P, const float* means3D,
                                       const float* colors, const float* opacities,
                                       const float* scales, const float* rotations,
@@ -1043,7 +1065,7 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
     with_mode(s->mode, [&](auto m) {
       hipLaunchKernelGGL(preprocess_kernel<m()>, grid, block, 0, st, kp, means3D, colors,
                          opacities, scales, rotations, gs.rec, gs.rect, gs.depth_key, gs.gidx, radii,
-                         library_sort ? (uint32_t*)nullptr : gs.ds_head);
+                         library_sort ? (uint32_t*)nullptr : gs.ds_head, gs.stats);
     });
     PINGS_LAUNCH_CHECK();
   }
@@ -1105,8 +1127,10 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
       // with the bound off the budget is still all zero: every tile keeps every rank bucket (OCC_ALL, masks all ones);
       // nvalid stays: rect_lane skips the culled ranks with it
       pings::prof::Scope ps("occl_scan", st);
-      // a retry clears again what the first attempt left: the statistics and, behind them, occ_bmax
-      if (attempt > 0) PINGS_HIP_CHECK(hipMemsetAsync(gs.stats, 0, (3 * STAT_SHARDS + 1) * sizeof(unsigned long long), st));
+      // a retry clears again what the first attempt's count_kept_kernel and occl_scan_kernel left: the kept pairs and,
+      // behind them, occ_bmax.  The footprint statistics stay: preprocess_kernel does not run again.
+      if (attempt > 0)
+        PINGS_HIP_CHECK(hipMemsetAsync(gs.stats + STAT_KEPT, 0, STAT_RETRY_WORDS * sizeof(unsigned long long), st));
       hipLaunchKernelGGL(occl_scan_kernel, dim3(gs.occ_words), dim3(512), 0, st, num_tiles, gs.occ_nb, gs.occ_bucket,
                          gs.occ_bsat, gs.occ_mask, gs.occ_bmax);
       PINGS_LAUNCH_CHECK();
@@ -1200,7 +1224,7 @@ PINGS_API int pings_raster_render(const pings_raster_settings* s, int P, int64_t
         pings::prof::Scope ps("duplicate", st);
         hipLaunchKernelGGL(duplicate_kernel<KeyT>, dim3(pings::ceil_div(P, 256)), dim3(256), 0, st, P,
                            kp.gx, gs.occ_nb, gs.occ_words, gs.gidx_sorted, gs.offsets_sorted, gs.tiles_sorted,
-                           gs.rect, gs.occ_mask, gs.nvalid, key, bs.gval);
+                           gs.rect, gs.occ_mask, gs.nvalid, key, bs.gval, reinterpret_cast<uint32_t*>(per_gaussian));
         PINGS_LAUNCH_CHECK();
       }
       const int bits = tile_bits(num_tiles);

@@ -55,9 +55,9 @@ GeomState carve_geom(void* blob, int P, int num_tiles) {
   g.occ_nb = occlusion_buckets((int)nt);
   // occ_bucket, stats and ds_head start every frame at zero: adjacent, ONE memset (zero_begin .. zero_end)
   g.occ_bucket = c.take<uint32_t>(nt * (size_t)g.occ_nb);
-  // sharded {pairs before culling, visible Gaussians, kept pairs}, then one word: occ_bmax
-  g.stats = c.take<unsigned long long>(3 * 256 + 1);
-  g.occ_bmax = g.stats ? reinterpret_cast<uint32_t*>(g.stats + 3 * 256) : nullptr;
+  // sharded pairs before culling, visible Gaussians, kept pairs, then one word: occ_bmax (STAT_*: raster_common.hpp)
+  g.stats = c.take<unsigned long long>(STAT_WORDS);
+  g.occ_bmax = g.stats ? reinterpret_cast<uint32_t*>(g.stats + STAT_BMAX) : nullptr;
   const size_t nblk = (n + 255) / 256;                  // workgroups of the per-Gaussian kernels
   g.ds_words = DS_HEAD + (size_t)DS_NB + nblk;          // header, counts (+ per-block culled)
   g.ds_head = c.take<uint32_t>(g.ds_words);
