@@ -1520,6 +1520,85 @@ PINGS_API int pings_lidar_project(const float* points, int64_t n, int64_t stride
                                   void* stream);
 PINGS_API int pings_lidar_depth_pyramid(const pings_lidar_cam* cams, int32_t ncam, void* stream);
 
+/* ------------------------------------------------------------- camera frame front-end (csrc/camfront.hip)
+ * The image pyramids of CamImage.__init__ (gaussian_splatting/utils/cameras.py:39, :116-182) on caller-owned buffers.
+ * No entry allocates, copies or waits; every output is bitwise the same from run to run (plain stores only).
+ *
+ * pings_camfront_pyramid: up to PINGS_CAMFRONT_MAX_MAPS maps (8 cameras x RGB, depth, sky mask, normal) in ONE launch;
+ *   the table travels in the kernel arguments and launches_out (HOST, may be NULL) receives the number of launches made.
+ *   Level k = 0..3 of a map is a contiguous [C, H >> k, W >> k] buffer (a trailing odd row or column is dropped at each
+ *   level); each of l0..l3 is nullable, a NULL level is not written, and no level is read back: levels 1..3 are formed
+ *   from the level-0 tile in registers and cross-lane moves.  By kind:
+ *     PINGS_CAMFRONT_RGB_U8   src uint8 [H, W, 3] contiguous (strides ignored); level 0 = float(u) / 255.0f, IEEE division
+ *     PINGS_CAMFRONT_RGB_F32  src fp32 [3, H, W] with element strides stride_c / stride_y / stride_x (any view); level 0 =
+ *                             the value clamped to [0, 1] as torch.clamp does (a NaN stays a NaN)
+ *     PINGS_CAMFRONT_NORMAL   src fp32 [3, H, W] with strides; level 0 = the value (pass l0 = NULL to keep the input)
+ *       these three, levels 1..3: 0.5 (0.5 a + 0.5 b) + 0.5 (0.5 c + 0.5 d) of the 2 x 2 block of the level above
+ *       (a, b the upper pair), rounded to fp32 at every level: F.interpolate(scale_factor=0.5, mode='bilinear')
+ *     PINGS_CAMFRONT_DEPTH    src fp32 [1, H, W] with strides; level k takes level-0 pixel (2^k y + 2^k - 1,
+ *                             2^k x + 2^k - 1): chained mode='nearest-exact'.  l0 is not written.
+ *     PINGS_CAMFRONT_SKY      src bytes [1, H, W] with strides; level k takes level-0 pixel (2^k y, 2^k x): chained
+ *                             mode='nearest' of a bool image.  l0 is not written.
+ *   A workgroup takes a PINGS_CAMFRONT_TILE_W x PINGS_CAMFRONT_TILE_H tile of one map and checks bounds per level.  A map
+ *   with W % 16 == 0, unit stride_x, stride_y and stride_c multiples of 16 and 16-byte aligned pointers moves 8- and
+ *   16-byte words per lane, any other map single elements; the values are the same. */
+#define PINGS_CAMFRONT_MAX_MAPS 32
+#define PINGS_CAMFRONT_TILE_W 128
+#define PINGS_CAMFRONT_TILE_H 32
+#define PINGS_CAMFRONT_RGB_U8 0
+#define PINGS_CAMFRONT_RGB_F32 1
+#define PINGS_CAMFRONT_NORMAL 2
+#define PINGS_CAMFRONT_DEPTH 3
+#define PINGS_CAMFRONT_SKY 4
+typedef struct pings_camfront_map {
+  const void* src;
+  void *l0, *l1, *l2, *l3;     /* levels, each nullable */
+  int64_t stride_c, stride_y, stride_x;
+  int32_t H, W, kind, reserved;
+} pings_camfront_map;
+PINGS_API int pings_camfront_pyramid(const pings_camfront_map* maps, int32_t nmaps, int32_t* launches_out, void* stream);
+
+/* The mono-depth cloud of dataset/slam_dataset.py:366-477, per camera, with every count on the device.
+ *
+ * pings_camfront_align: pred, lidar_depth [n] fp32.  Over the pixels with lidar > min_range && pred > min_range &&
+ *   lidar < 0.8 max_range (strict; both thresholds rounded to fp32 once, as numpy rounds a Python scalar) the line
+ *   lidar = k pred + b by least squares, from fp64 sums.  record (DEVICE, PINGS_CAMFRONT_FIT_RECORD doubles) = count, k,
+ *   b, rmse before (sqrt of the mean of (pred - lidar)^2, NaN at count 0), rmse after.  count <= PINGS_CAMFRONT_MIN_FIT
+ *   gives k = 1, b = 0 and rmse after = NaN.  Two launches: per-workgroup partial sums into `scratch`
+ *   (pings_camfront_align_scratch_bytes()) in a fixed order, then one workgroup that adds them in index order.
+ * pings_camfront_mono_cloud: pred [H, W] fp32, image [H, W, 3] uint8.  Per pixel, in this order:
+ *   d = fp32(k pred + b) evaluated in fp64 (k, b = record[1], record[2]; record NULL: 1, 0);
+ *   sky = d > 1.2 max_range, and d = 0 there; with high_z: d > 0.8 max_range -> 0, then d < 2 min_range -> 0; without:
+ *   d < 0.2 max_range -> 0 (every threshold rounded to fp32 once, every comparison strict).  sky [H, W] bytes and gated
+ *   (nullable) [H, W] fp32 receive sky and d.  A pixel gives a row iff 0 < d < depth_trunc: rows[o] = xyz, rgb with
+ *   xyz = cam_to_lidar ((u - cx) d / fx, (v - cy) d / fy, d) in fp64 rounded once (intrinsic HOST = fx, fy, cx, cy;
+ *   cam_to_lidar HOST = the first three rows of T_c_l^-1, row-major) and rgb = byte / 255 in fp64 rounded once, in
+ *   row-major pixel order; rows holds H W rows of 6 floats, *count (DEVICE) receives how many were written.  Three
+ *   launches (flag, scan, scatter); scratch of pings_camfront_cloud_scratch_bytes(H W).
+ * pings_camfront_voxel_average: Open3D's voxel_down_sample over rows of 6 floats (position, colour), with the contract
+ *   of pings_eval_voxel_centroids: cells from the first three columns in fp64 on a grid anchored at min - voxel / 2,
+ *   output in ascending cell key, sums in fp64 in input order over all six columns, PINGS_EVAL_EXTENT in *status.  The
+ *   input has n rows of capacity and *n_dev (nullable) live rows.  The cells are appended to out [out_cap, 6] behind
+ *   *offset rows (DEVICE, nullable = 0) and *count (DEVICE, another word than offset) receives offset + cells, so that
+ *   cameras chain without the host; cells that find no room are dropped and PINGS_CAMFRONT_FULL is or-ed into *status.
+ *   scratch of pings_camfront_voxel_scratch_bytes(n). */
+#define PINGS_CAMFRONT_FIT_RECORD 5
+#define PINGS_CAMFRONT_MIN_FIT 100
+#define PINGS_CAMFRONT_FULL 2
+PINGS_API size_t pings_camfront_align_scratch_bytes(void);
+PINGS_API int pings_camfront_align(const float* pred, const float* lidar_depth, int64_t n, double min_range,
+                                   double max_range, void* scratch, double* record, void* stream);
+PINGS_API size_t pings_camfront_cloud_scratch_bytes(int64_t hw);
+PINGS_API int pings_camfront_mono_cloud(const float* pred, const uint8_t* image, int32_t H, int32_t W,
+                                        const double* record, const double* intrinsic, const double* cam_to_lidar,
+                                        double min_range, double max_range, double depth_trunc, int32_t high_z,
+                                        void* scratch, uint8_t* sky, float* gated, float* rows, int64_t* count,
+                                        void* stream);
+PINGS_API size_t pings_camfront_voxel_scratch_bytes(int64_t n);
+PINGS_API int pings_camfront_voxel_average(const float* rows, int64_t n, const int64_t* n_dev, double voxel,
+                                           void* scratch, float* out, int64_t out_cap, const int64_t* offset,
+                                           int64_t* count, int32_t* status, void* stream);
+
 /* ------------------------------------------------------ sparse TSDF fusion (csrc/tsdf.hip)
  * Depth views fused into blocks of PINGS_TSDF_BLOCK^3 voxels, the route of SLAMDataset.o3d_tsdf_fusion.  Grid point g
  * lies at origin + voxel_length * g, block b = floor(g / 8) has the key (bx + 2^20) << 42 | (by + 2^20) << 21 |

@@ -22,6 +22,10 @@ EVAL_EXTENT = 1                                                   # PINGS_EVAL_E
 LOOP_MAX_R, LOOP_MAX_S, LOOP_MAX_D = 32, 128, 16                  # PINGS_LOOP_MAX_*: limits of the pings_loop_* entries
 LOOP_MAX_Q, LOOP_MAX_C = 16, 65536                                # poses / queries per call, candidates per search
 LIDAR_MAX_CAMS, LIDAR_MAX_LIDARS = 8, 8                           # PINGS_LIDAR_MAX_*: cameras per launch, other LiDARs
+CAMFRONT_MAX_MAPS, CAMFRONT_TILE_W, CAMFRONT_TILE_H = 32, 128, 32    # PINGS_CAMFRONT_*: maps per launch, workgroup tile
+CAMFRONT_RGB_U8, CAMFRONT_RGB_F32, CAMFRONT_NORMAL, CAMFRONT_DEPTH, CAMFRONT_SKY = 0, 1, 2, 3, 4   # pings_camfront_map.kind
+CAMFRONT_FIT_RECORD, CAMFRONT_MIN_FIT = 5, 100                    # doubles per fit record; no fit at this many pixels or fewer
+CAMFRONT_FULL = 2                                                 # status bit of pings_camfront_voxel_average
 TSDF_BLOCK = 8                                                    # PINGS_TSDF_BLOCK: voxels per block edge
 TSDF_EXTENT, TSDF_TABLE_FULL = 1, 2                               # PINGS_TSDF_*: status bits of pings_tsdf_touch
 
@@ -175,6 +179,12 @@ class PoolSelectArgs(C.Structure):
 class LidarCam(C.Structure):
     _fields_ = [(n, vp) for n in ("image", "K", "T", "keys", "src", "l0", "l1", "l2", "l3")] + \
                [("H", C.c_int32), ("W", C.c_int32)]
+
+
+class CamfrontMap(C.Structure):
+    _fields_ = [(n, vp) for n in ("src", "l0", "l1", "l2", "l3")] + \
+               [(n, C.c_int64) for n in ("stride_c", "stride_y", "stride_x")] + \
+               [(n, C.c_int32) for n in ("H", "W", "kind", "reserved")]
 
 
 # ---------------------------------------------------------------- entry points: {name: (restype, argtypes)}
@@ -409,6 +419,15 @@ SIGNATURES = {
     "pings_lidar_slerp_pose": (i32, [vp, i32, f64, vp, i32, i32, vp, i32, vp]),
     "pings_lidar_project": (i32, [vp, i64, i64, C.POINTER(LidarCam), i32, f64, f64, vp, i64, vp, i64, vp, i32, vp]),
     "pings_lidar_depth_pyramid": (i32, [C.POINTER(LidarCam), i32, vp]),
+    # camera frame front-end
+    "pings_camfront_pyramid": (i32, [C.POINTER(CamfrontMap), i32, C.POINTER(i32), vp]),
+    "pings_camfront_align_scratch_bytes": (sz, []),
+    "pings_camfront_align": (i32, [vp, vp, i64, f64, f64, vp, vp, vp]),
+    "pings_camfront_cloud_scratch_bytes": (sz, [i64]),
+    "pings_camfront_mono_cloud": (i32, [vp, vp, i32, i32, vp, C.POINTER(f64), C.POINTER(f64), f64, f64, f64, i32, vp, vp,
+                                        vp, vp, vp, vp]),
+    "pings_camfront_voxel_scratch_bytes": (sz, [i64]),
+    "pings_camfront_voxel_average": (i32, [vp, i64, vp, f64, vp, vp, i64, vp, vp, vp, vp]),
     # sparse TSDF fusion
     "pings_tsdf_table_insert": (i32, [vp, i64, vp, vp, i64, vp, vp]),
     "pings_tsdf_touch": (i32, [vp, i32, i32, C.POINTER(f64), C.POINTER(f64), C.POINTER(f64), f64, f64, f32, f32, i32, i32,

@@ -36,6 +36,34 @@ struct Carver {
   size_t total() const { return off; }
 };
 
+#if defined(__HIPCC__)
+// Exclusive scan of one int per thread over a workgroup of Block threads (whole waves); *total = the workgroup's sum.
+// Every thread of the workgroup calls it.
+template <int Block>
+__device__ inline int block_exclusive_scan(int x, int* total) {
+  constexpr int kWaves = Block / kWave;
+  __shared__ int wsum[kWaves];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = x;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int y = __shfl_up(incl, off, 64);
+    if (lane >= off) incl += y;
+  }
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < kWaves; ++w) {
+    before += w < wave ? wsum[w] : 0;
+    all += wsum[w];
+  }
+  __syncthreads();
+  *total = all;
+  return before + incl - x;
+}
+#endif
+
 // Stream-ordered read of up to 8 device words (32 bit each) into host memory WITHOUT a blocking wait inside the HIP
 // runtime: one wave copies the words into pinned, device-mapped host memory behind everything already queued on `st` and
 // the host polls a sequence number (abi.hip).  A blocking hipStreamSynchronize wakes through an interrupt, which on one

@@ -55,26 +55,8 @@ __device__ __forceinline__ float wave_sum(float x) {
 }
 
 // Exclusive scan of one int per thread over a kBlock workgroup; *total = the workgroup's sum.
-__device__ int block_exclusive_scan(int x, int* total) {
-  __shared__ int wsum[kWaves];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int incl = x;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const int y = __shfl_up(incl, off, 64);
-    if (lane >= off) incl += y;
-  }
-  if (lane == 63) wsum[wave] = incl;
-  __syncthreads();
-  int before = 0, all = 0;
-#pragma unroll
-  for (int w = 0; w < kWaves; ++w) {
-    before += w < wave ? wsum[w] : 0;
-    all += wsum[w];
-  }
-  __syncthreads();
-  *total = all;
-  return before + incl - x;
+__device__ __forceinline__ int block_exclusive_scan(int x, int* total) {
+  return pings::block_exclusive_scan<kBlock>(x, total);
 }
 
 // ------------------------------------------------------------------ view metrics
@@ -226,6 +208,8 @@ struct GridInfo {
   i64 cnt;               // live points
 };
 
+// C: floats per row of the cloud (3: positions; 6: positions and colours).  Cells come from the first three.
+template <int C>
 __global__ __launch_bounds__(kBlock) void bounds_kernel(const float* __restrict__ pts, i64 cap,
                                                         const int64_t* __restrict__ n_dev, Part* __restrict__ partial) {
   __shared__ float red[6][kWaves];
@@ -234,7 +218,7 @@ __global__ __launch_bounds__(kBlock) void bounds_kernel(const float* __restrict_
   for (i64 i = (i64)blockIdx.x * kBlock + threadIdx.x; i < n; i += (i64)gridDim.x * kBlock) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      const float x = pts[3 * i + a];
+      const float x = pts[C * i + a];
       v[a] = fminf(v[a], x);
       v[3 + a] = fmaxf(v[3 + a], x);
     }
@@ -305,6 +289,7 @@ __device__ __forceinline__ int filed_cell(float x, double lo, double cell, int d
   return (int)fmin(fmax(t, 0.0), (double)(dim - 1));
 }
 
+template <int C>
 __global__ __launch_bounds__(kBlock) void key_kernel(const float* __restrict__ pts, i64 cap,
                                                      const GridInfo* __restrict__ info, double cell,
                                                      u64* __restrict__ key, uint32_t* __restrict__ val) {
@@ -312,9 +297,9 @@ __global__ __launch_bounds__(kBlock) void key_kernel(const float* __restrict__ p
   if (i >= cap) return;
   u64 k = kPadKey;
   if (i < info->cnt) {
-    const int x = filed_cell(pts[3 * i], info->lo[0], cell, info->dim[0]);
-    const int y = filed_cell(pts[3 * i + 1], info->lo[1], cell, info->dim[1]);
-    const int z = filed_cell(pts[3 * i + 2], info->lo[2], cell, info->dim[2]);
+    const int x = filed_cell(pts[C * i], info->lo[0], cell, info->dim[0]);
+    const int y = filed_cell(pts[C * i + 1], info->lo[1], cell, info->dim[1]);
+    const int z = filed_cell(pts[C * i + 2], info->lo[2], cell, info->dim[2]);
     k = make_key(x, y, z);
   }
   key[i] = k;
@@ -328,6 +313,7 @@ struct GridScratch {
   uint32_t *val, *val_sorted;
   float4* pts4;                 // search only
   int *flag, *rank, *start;     // centroids only
+  i64* cells;                   // centroids only: occupied cells
   void* temp;
   size_t temp_bytes, total;
 };
@@ -349,6 +335,7 @@ GridScratch carve_grid(void* base, i64 cap, bool search) {
     s.flag = c.take<int>(n);
     s.rank = c.take<int>(n);
     s.start = c.take<int>(n);
+    s.cells = c.take<i64>(1);
     s.temp_bytes = std::max(s.temp_bytes, devprim::inclusive_sum_i32_temp_bytes(cap));   // the scan follows the sort
   }
   s.temp_bytes = pings::align_up(s.temp_bytes);
@@ -358,14 +345,15 @@ GridScratch carve_grid(void* base, i64 cap, bool search) {
 }
 
 // bounds, grid, keys and the sort by key: the front of both pipelines
+template <int C = 3>
 int file_points(const float* pts, i64 cap, const int64_t* n_dev, double cell, double shift, const GridScratch& s,
                 int32_t* status, hipStream_t st) {
   const int nb = (int)std::min<i64>(kPartBlocks, (cap + kBlock - 1) / kBlock);
-  bounds_kernel<<<nb, kBlock, 0, st>>>(pts, cap, n_dev, s.partial);
+  bounds_kernel<C><<<nb, kBlock, 0, st>>>(pts, cap, n_dev, s.partial);
   PINGS_LAUNCH_CHECK();
   grid_info_kernel<<<1, 64, 0, st>>>(s.partial, nb, cap, n_dev, cell, shift, s.info, status);
   PINGS_LAUNCH_CHECK();
-  key_kernel<<<blocks_for(cap), kBlock, 0, st>>>(pts, cap, s.info, cell, s.key, s.val);
+  key_kernel<C><<<blocks_for(cap), kBlock, 0, st>>>(pts, cap, s.info, cell, s.key, s.val);
   PINGS_LAUNCH_CHECK();
   return devprim::sort_pairs_u64_u32(s.temp, s.temp_bytes, s.key, s.key_sorted, s.val, s.val_sorted, cap, 0, 64, st);
 }
@@ -378,36 +366,56 @@ __global__ __launch_bounds__(kBlock) void vc_heads_kernel(const u64* __restrict_
   flag[i] = (i < info->cnt && (i == 0 || ks[i] != ks[i - 1])) ? 1 : 0;
 }
 
+// rows already in `out` (0 without a device offset), clamped into [0, out_cap]
+__device__ __forceinline__ i64 rows_before(const int64_t* offset, i64 out_cap) {
+  return offset ? live_count(out_cap, offset) : 0;
+}
+
+// *count = rows in `out` after this call: the rows before it plus the occupied cells, at most out_cap (then `full`, when
+// it is not 0, is or-ed into *status: this thread is the only writer in this launch)
 __global__ __launch_bounds__(kBlock) void vc_starts_kernel(const int* __restrict__ flag, const int* __restrict__ rank,
                                                            i64 cap, const GridInfo* __restrict__ info,
-                                                           int* __restrict__ start, int64_t* __restrict__ count) {
+                                                           int* __restrict__ start, const int64_t* __restrict__ offset,
+                                                           i64 out_cap, i64* __restrict__ cells,
+                                                           int64_t* __restrict__ count, int32_t* __restrict__ status,
+                                                           int full) {
   const i64 i = (i64)blockIdx.x * kBlock + threadIdx.x;
   if (i >= cap) return;
   if (flag[i]) start[rank[i] - 1] = (int)i;          // rank = inclusive sum of the flags: 1 <= rank <= cap
-  if (i == cap - 1) *count = (int64_t)rank[i];       // occupied cells (0 when there is no live point)
+  if (i == cap - 1) {                                // rank[i]: occupied cells (0 when there is no live point)
+    *cells = (i64)rank[i];
+    const i64 total = rows_before(offset, out_cap) + (i64)rank[i];
+    if (total > out_cap && full) *status = *status | full;
+    *count = (int64_t)(total > out_cap ? out_cap : total);
+  }
 }
 
-// one thread per occupied cell: the mean of its points, summed in fp64 in sorted order (a stable sort: input order)
+// one thread per occupied cell: the mean of its points over all C columns, summed in fp64 in sorted order (a stable
+// sort: input order); cell r becomes row (rows before this call) + r of `out`
+template <int C>
 __global__ __launch_bounds__(kBlock) void vc_mean_kernel(const float* __restrict__ pts, const uint32_t* __restrict__ vs,
                                                          const int* __restrict__ start, i64 cap,
                                                          const GridInfo* __restrict__ info,
-                                                         const int64_t* __restrict__ count, float* __restrict__ out) {
+                                                         const i64* __restrict__ cells,
+                                                         const int64_t* __restrict__ offset, i64 out_cap,
+                                                         float* __restrict__ out) {
   const i64 r = (i64)blockIdx.x * kBlock + threadIdx.x;
-  const i64 runs = live_count(cap, count);
-  if (r >= runs) return;
+  const i64 base = rows_before(offset, out_cap);
+  const i64 runs = *cells;                                                  // <= cap
+  if (r >= runs || base + r >= out_cap) return;                             // a cell that finds no room is dropped
   const i64 cnt = info->cnt > cap ? cap : info->cnt;
   const i64 b = start[r], e = r + 1 < runs ? (i64)start[r + 1] : cnt;
-  double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+  double s[C];
+#pragma unroll
+  for (int c = 0; c < C; ++c) s[c] = 0.0;
   for (i64 j = b; j < e; ++j) {                      // e <= cnt <= cap
     const i64 p = (i64)vs[j];
-    s0 += (double)pts[3 * p];
-    s1 += (double)pts[3 * p + 1];
-    s2 += (double)pts[3 * p + 2];
+#pragma unroll
+    for (int c = 0; c < C; ++c) s[c] += (double)pts[C * p + c];
   }
   const double inv = 1.0 / (double)(e - b);
-  out[3 * r] = (float)(s0 * inv);
-  out[3 * r + 1] = (float)(s1 * inv);
-  out[3 * r + 2] = (float)(s2 * inv);
+#pragma unroll
+  for (int c = 0; c < C; ++c) out[C * (base + r) + c] = (float)(s[c] * inv);
 }
 
 // ------------------------------------------------------------------ nearest neighbour
@@ -573,6 +581,24 @@ __global__ __launch_bounds__(kReduceBlock) void pair_reduce_kernel(const float* 
 
 bool count_ok(int64_t n) { return n > 0 && n <= kMaxCount; }
 
+// the centroids of a cloud of C floats per row, appended to `out` behind *offset rows (0 without one)
+template <int C>
+int voxel_means(const float* points, int64_t n, const int64_t* n_dev, double voxel, void* scratch, float* out,
+                const int64_t* offset, int64_t out_cap, int64_t* count, int32_t* status, int full, hipStream_t st) {
+  const GridScratch s = carve_grid(scratch, n, false);
+  if (int e = file_points<C>(points, n, n_dev, voxel, 0.5, s, status, st)) return e;
+  vc_heads_kernel<<<blocks_for(n), kBlock, 0, st>>>(s.key_sorted, n, s.info, s.flag);
+  PINGS_LAUNCH_CHECK();
+  if (int e = devprim::inclusive_sum_i32(s.temp, s.temp_bytes, s.flag, s.rank, n, st)) return e;
+  vc_starts_kernel<<<blocks_for(n), kBlock, 0, st>>>(s.flag, s.rank, n, s.info, s.start, offset, out_cap, s.cells, count,
+                                                     status, full);
+  PINGS_LAUNCH_CHECK();
+  vc_mean_kernel<C><<<blocks_for(n), kBlock, 0, st>>>(points, s.val_sorted, s.start, n, s.info, s.cells, offset, out_cap,
+                                                      out);
+  PINGS_LAUNCH_CHECK();
+  return PINGS_OK;
+}
+
 struct BpScratch {
   int *cnt, *off;   // per block: points kept, their inclusive scan
   void* temp;
@@ -662,17 +688,23 @@ PINGS_API int pings_eval_voxel_centroids(const float* points, int64_t n, const i
   PINGS_ARG_CHECK(count_ok(n), "empty or oversized cloud");
   PINGS_ARG_CHECK(voxel > 0.0 && std::isfinite(voxel), "voxel size must be positive");
   hipStream_t st = pings::as_stream(stream);
-  const GridScratch s = carve_grid(scratch, n, false);
   pings::prof::Scope sc("eval_voxel_centroids", st);
-  if (int e = file_points(points, n, n_dev, voxel, 0.5, s, status, st)) return e;
-  vc_heads_kernel<<<blocks_for(n), kBlock, 0, st>>>(s.key_sorted, n, s.info, s.flag);
-  PINGS_LAUNCH_CHECK();
-  if (int e = devprim::inclusive_sum_i32(s.temp, s.temp_bytes, s.flag, s.rank, n, st)) return e;
-  vc_starts_kernel<<<blocks_for(n), kBlock, 0, st>>>(s.flag, s.rank, n, s.info, s.start, count);
-  PINGS_LAUNCH_CHECK();
-  vc_mean_kernel<<<blocks_for(n), kBlock, 0, st>>>(points, s.val_sorted, s.start, n, s.info, count, out);
-  PINGS_LAUNCH_CHECK();
-  return PINGS_OK;
+  return voxel_means<3>(points, n, n_dev, voxel, scratch, out, nullptr, n, count, status, 0, st);
+}
+
+// The coloured voxel average of the camera front-end lives here, with the kernels it instantiates.
+PINGS_API size_t pings_camfront_voxel_scratch_bytes(int64_t n) { return pings_eval_voxel_scratch_bytes(n); }
+
+PINGS_API int pings_camfront_voxel_average(const float* rows, int64_t n, const int64_t* n_dev, double voxel,
+                                           void* scratch, float* out, int64_t out_cap, const int64_t* offset,
+                                           int64_t* count, int32_t* status, void* stream) {
+  PINGS_ARG_CHECK(rows && scratch && out && count && status, "null pointer");
+  PINGS_ARG_CHECK(offset != count, "offset and count must be different words");
+  PINGS_ARG_CHECK(count_ok(n) && out_cap > 0 && out_cap <= kMaxCount, "empty or oversized cloud");
+  PINGS_ARG_CHECK(voxel > 0.0 && std::isfinite(voxel), "voxel size must be positive");
+  hipStream_t st = pings::as_stream(stream);
+  pings::prof::Scope sc("camfront_voxel_average", st);
+  return voxel_means<6>(rows, n, n_dev, voxel, scratch, out, offset, out_cap, count, status, PINGS_CAMFRONT_FULL, st);
 }
 
 PINGS_API size_t pings_eval_nn_scratch_bytes(int64_t m) {

@@ -615,6 +615,37 @@ def select_update(coord, sdf_label, color, normal, pose, thr=None):
     return points, o_color, o_normal
 
 
+# ---------------------------------------------------------------- process_frame: mono-depth points (:297-331)
+@torch.no_grad()
+def _mono_update(self, mono, update_points, cur_pose_torch, frame_id: int) -> None:
+    """The mono-depth branch of `Mapper.process_frame` (utils/mapper.py:297-331) without normals.  `mono`'s xyz columns
+    are moved by the pose in place, as the reference leaves the caller's tensor (`select_update`, one launch).  The
+    rows above the 0.98 quantile (`mono_depth_for_high_z`) or below the 0.2 quantile of the update points' z plus
+    `voxel_size_m` (a device scalar, one compare launch) become a row list with one host read; one gather, then
+    `neural_map.voxel_down_sample` at `monodepth_gaussian_res` and `neural_points.update(..., is_reliable=True)`,
+    which is skipped when no row is left."""
+    from . import neural_map
+
+    cfg, dev = self.config, mono.device
+    if int(mono.shape[0]) == 0:
+        return
+    mono[:, :3] = select_update(mono[:, :3].contiguous(), None, None, None, cur_pose_torch)[0]
+    z = update_points[:, 2]
+    if self.dataset.loader.mono_depth_for_high_z:
+        used = mono[:, 2] > torch.quantile(z, 0.98) + cfg.voxel_size_m
+    else:
+        used = mono[:, 2] < torch.quantile(z, 0.2) + cfg.voxel_size_m
+    with _guard(dev):
+        rows, k, _ = neural_map._mask_rows(_lib.lib(), used)
+        if k == 0:
+            return
+        kept = neural_map._gather_many(_lib.lib(), [(mono, k)], rows)[0]
+        idx = neural_map.voxel_down_sample(kept[:, :3], cfg.monodepth_gaussian_res)
+        kept = neural_map._gather_many(_lib.lib(), [(kept, int(idx.shape[0]))], idx)[0]
+    self.neural_points.update(kept[:, :3], kept[:, 3:], None, cur_pose_torch[:3, 3], cur_pose_torch[:3, :3], frame_id,
+                              is_reliable=True)
+
+
 # ---------------------------------------------------------------- Mapper.process_frame
 def _frame_on_device(self, point_cloud_torch, frame_label_torch, frame_normal_torch, cur_pose_torch) -> bool:
     pc = point_cloud_torch
@@ -651,11 +682,19 @@ def process_frame(self, point_cloud_torch, frame_label_torch, frame_normal_torch
     Departures: `local_sample_indices` is always 1-D (`window_rows`), and the window is tested in float32 against the
     pose's translation rounded to float32 (the reference promotes to the pose's dtype).
 
-    CPU or non-float32 tensors, a non-contiguous pool and the deprecated mono-depth branch take the class's original
-    method."""
+    With `config.monodepth_on` and a mono-depth cloud (a float32 [M, 3 + color_channel] device tensor, as
+    `camfront_ops.mono_frame` leaves it) the branch of :297-331 follows the main `update`: `_mono_update`.
+
+    CPU or non-float32 tensors, a non-contiguous pool, a mono-depth cloud on the CPU or of another dtype and mono-depth
+    normals take the class's original method."""
     cfg = self.config
-    if ((mono_depth_point_cloud_torch is not None and cfg.monodepth_on)
-            or not _frame_on_device(self, point_cloud_torch, frame_label_torch, frame_normal_torch, cur_pose_torch)):
+    mono = mono_depth_point_cloud_torch if (mono_depth_point_cloud_torch is not None and cfg.monodepth_on) else None
+    mono_ok = mono is None or (mono_depth_point_normals_torch is None and _f32_dev(mono) and mono.dim() == 2
+                               and int(mono.shape[1]) == 3 + int(cfg.color_channel)
+                               and isinstance(point_cloud_torch, torch.Tensor)
+                               and mono.device == point_cloud_torch.device)
+    if not mono_ok or not _frame_on_device(self, point_cloud_torch, frame_label_torch, frame_normal_torch,
+                                           cur_pose_torch):
         return _original(self, "process_frame")(self, point_cloud_torch, frame_label_torch, frame_normal_torch,
                                                 cur_pose_torch, frame_id, filter_dynamic,
                                                 mono_depth_point_cloud_torch, mono_depth_point_normals_torch)
@@ -716,6 +755,8 @@ def process_frame(self, point_cloud_torch, frame_label_torch, frame_normal_torch
             self.neural_points.recreate_hash(None, None, True, True, frame_id)
     self.neural_points.update(update_points, update_colors, update_normals, frame_origin_torch,
                               frame_orientation_torch, frame_id)
+    if mono is not None:
+        _mono_update(self, mono, update_points, cur_pose_torch, frame_id)
     self.neural_points.record_memory(verbose=(not self.silence), record_footprint=True)
 
     # the data pool (:340-426)
