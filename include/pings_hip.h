@@ -214,6 +214,14 @@ PINGS_API int pings_raster_debug_occlusion(const void* geom_blob, int P, int ima
  * `occ_nb` buckets per tile.  Non-decreasing in the rank, 0 for rank 0, below occ_nb. */
 PINGS_API int pings_raster_rank_bucket(const int32_t* ranks, int64_t n, int occ_nb, uint32_t nvalid,
                                        uint32_t* buckets);
+/* Which (surfel record, 16x16 tile) pairs the wave-per-tile blend backward treats as interior, computed on the HOST by
+ * the function the kernel calls (host pointers, no GPU work).  records [n][16]: the four float4 of a record as the
+ * geometry blob holds them ({mx, my, opacity, pz} {conic x, y, z, rz} {r, g, b, q} {nx, ny, nz, -}); tile_origins
+ * [n][2]: pixel coordinates of the tile's first pixel; cxp = prcp.x * width - 0.5 and cyp likewise, fx, fy: the
+ * camera terms of the per-pixel ray.  flags[i] = 1 only if, at all 256 pixel positions of the tile, the record passes
+ * the alpha tests unclamped and takes the unclamped ray hit of its depth (csrc/raster_common.hpp: blend_interior). */
+PINGS_API int pings_raster_debug_interior(const float* records, const float* tile_origins, int64_t n, float cxp,
+                                          float cyp, float fx, float fy, uint8_t* flags);
 
 
 /* ------------------------------------------- 2D Gaussian splatting rasteriser

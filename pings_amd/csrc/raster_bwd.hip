@@ -57,11 +57,12 @@ __device__ __forceinline__ void blend_bwd_tile_body(
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ out_depth, const float* __restrict__ dL_dcolor,
     const float* __restrict__ dL_dnormal, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha,
     const float* __restrict__ inst_w, const uint32_t* __restrict__ cidx, float* __restrict__ rows,
-    const uint32_t* __restrict__ tile_order) {
+    const uint32_t* __restrict__ tile_order, int interior_on) {
   __shared__ float4 sA[BATCH], sB[BATCH], sC[BATCH], sD[BATCH];
   __shared__ uint32_t sRow[BATCH];  // compact gradient-row index, DEAD_ROW for dead instances
   __shared__ float4 sG[BATCH][4];
   __shared__ uint8_t sList[BATCH];  // live records of the batch that may reach the tile (ascending)
+  __shared__ uint8_t sInt[BATCH];   // 1: the record is interior to the tile (raster_common.hpp: blend_interior)
 
   const int lane = threadIdx.x;
   const int tile = (int)tile_order[blockIdx.x];   // longest-processing-time-first dispatch (raster_fwd.hip)
@@ -74,12 +75,14 @@ __device__ __forceinline__ void blend_bwd_tile_body(
 
   f2 rx = {0.f, 0.f};
   float ry[2] = {0.f, 0.f};
+  TileRays rays = {0.f, 0.f, 0.f, 0.f};
   if (MODE == MODE_SURFEL) {
     const float cxp = (p.prcp ? p.prcp[0] : 0.5f) * (float)p.W - 0.5f;
     const float cyp = (p.prcp ? p.prcp[1] : 0.5f) * (float)p.H - 0.5f;
     rx = f2{(pixf_x.x - cxp) / p.fx, (pixf_x.y - cxp) / p.fx};
 #pragma unroll
     for (int r = 0; r < 2; ++r) ry[r] = (pixf_y[r] - cyp) / p.fy;
+    rays = tile_rays_uniform(tile_rays(tileX0, tileY0, cxp, cyp, p.fx, p.fy));
   }
 
   const uint2 range = ranges[tile];
@@ -159,11 +162,17 @@ __device__ __forceinline__ void blend_bwd_tile_body(
       const float4 rb = rec[4 * (size_t)g + 1];
       sA[lane] = ra;
       sB[lane] = rb;
-      sC[lane] = rec[4 * (size_t)g + 2];
-      if (MODE == MODE_SURFEL) sD[lane] = rec[4 * (size_t)g + 3];
+      const float4 rc = rec[4 * (size_t)g + 2];
+      sC[lane] = rc;
+      float4 rd = make_float4(0.f, 0.f, 0.f, 0.f);
+      if (MODE == MODE_SURFEL) sD[lane] = rd = rec[4 * (size_t)g + 3];
       const bool live = inst_w[slot] > 0.f;  // blended something in the forward pass
       sRow[lane] = live ? cidx[slot] : DEAD_ROW;
       if (live) hit = quadrant_mask(ra.x, ra.y, ra.z, rb.x, rb.y, rb.z, tileX0, tileY0) != 0u;
+      // records interior to the tile take the lean trip below; the flags become one scalar mask over the list
+      if (MODE == MODE_SURFEL)
+        sInt[lane] = hit && interior_on && blend_interior(ra.x, ra.y, ra.z, ra.w, rb.x, rb.y, rb.z, rb.w, rc.w, rd.x, rd.y,
+                                                          rd.z, tileX0, tileY0, rays) ? 1 : 0;
     }
     const unsigned long long bal = __ballot(hit);
     if (hit) sList[__builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = (uint8_t)lane;
@@ -174,6 +183,8 @@ __device__ __forceinline__ void blend_bwd_tile_body(
       for (int e = lane; e < BATCH * 4; e += 64) z[e] = zero;
     }
     __syncthreads();
+    unsigned long long int_bits = 0ull;   // bit jj: list entry jj is interior (wave-uniform)
+    if (MODE == MODE_SURFEL) int_bits = __ballot(lane < cnt && sInt[sList[lane < cnt ? lane : 0] & (BATCH - 1)] != 0);
 
     // Two-deep software pipeline over the list: the INDEX of record jj-2 and the RECORD jj-1 are fetched from LDS
     // while record jj is processed, so neither LDS latency sits in an iteration's dependency chain.
@@ -184,8 +195,13 @@ __device__ __forceinline__ void blend_bwd_tile_body(
     float4 a0 = sA[i0], b0 = sB[i0], c0 = sC[i0], n0 = make_float4(0.f, 0.f, 0.f, 0.f);
     float4 a1, b1, c1, n1 = n0;
     if (MODE == MODE_SURFEL) n0 = sD[i0];
-    auto trip = [&](const float4& ca, const float4& cb, const float4& cc, const float4& cn, const int j)
+    // INT: the trip of a record interior to the tile (blend_interior: every pixel passes the alpha tests unclamped and
+    // takes the unclamped ray hit).  It leaves out the decisions and the three rows that are exactly zero for such a
+    // record (G_ZLO, G_ZHI, G_PZ); everything it keeps is the general trip's, operation for operation, so both give the
+    // same bits wherever the classifier holds.
+    auto trip = [&](auto interior_c, const float4& ca, const float4& cb, const float4& cc, const float4& cn, const int j)
                     __attribute__((always_inline)) {
+      constexpr bool INT = MODE == MODE_SURFEL && decltype(interior_c)::value;
       const uint32_t idx = (uint32_t)(start + j);
       // the forward pass's alpha and validity, operation for operation (blend_fwd_tile_kernel)
       const f2 dx = f2s(ca.x) - pixf_x;
@@ -202,9 +218,9 @@ __device__ __forceinline__ void blend_bwd_tile_body(
         const f2 power = (p0 - f2s(0.5f * (cb.z * dy * dy))) - pxy * f2s(dy);
         Gs[r] = f2{__expf(power.x), __expf(power.y)};
         raw[r] = f2s(ca.z) * Gs[r];
-        alpha[r] = f2{fminf(ALPHA_MAX, raw[r].x), fminf(ALPHA_MAX, raw[r].y)};
-        valid[r][0] = idx < last[r][0] && (power.x <= 0.0f) && (alpha[r].x >= ALPHA_MIN);
-        valid[r][1] = idx < last[r][1] && (power.y <= 0.0f) && (alpha[r].y >= ALPHA_MIN);
+        alpha[r] = INT ? raw[r] : f2{fminf(ALPHA_MAX, raw[r].x), fminf(ALPHA_MAX, raw[r].y)};
+        valid[r][0] = idx < last[r][0] && (INT || ((power.x <= 0.0f) && (alpha[r].x >= ALPHA_MIN)));
+        valid[r][1] = idx < last[r][1] && (INT || ((power.y <= 0.0f) && (alpha[r].y >= ALPHA_MIN)));
         any_v = any_v || valid[r][0] || valid[r][1];
       }
       if (!__any(any_v)) return;
@@ -215,6 +231,7 @@ __device__ __forceinline__ void blend_bwd_tile_body(
 #pragma clang fp contract(fast)
       f2 v2[16];
       if (MODE != MODE_SURFEL) v2[G_NX] = v2[G_NY] = v2[G_NZ] = v2[G_Q] = v2[G_ZLO] = v2[G_ZHI] = f2{0.f, 0.f};
+      if (INT) v2[G_ZLO] = v2[G_ZHI] = v2[G_PZ] = f2{0.f, 0.f};
       const float zlo = ca.w - cb.w, zhi = ca.w + cb.w;
       const float zlo_m = fminf(zlo, zhi);   // med3(d, min(lo, hi), hi) == fminf(fmaxf(d, lo), hi) for non-NaN d
       const f2 cxdx = f2s(cb.x) * dx;        // q = conic . (dx, dy) as two adds per pixel
@@ -240,20 +257,27 @@ __device__ __forceinline__ void blend_bwd_tile_body(
           sdot += (f2s(cn.x) * gN0[r] + f2s(cn.y) * gN1[r]) + f2s(cn.z) * gN2[r];
           // per-pixel depth of this surfel
           const f2 den = fma2(f2s(cn.x), rx, f2s(fmaf(cn.y, ry[r], cn.z)));
-          const bool hit0 = den.x < -DEN_EPS, hit1 = den.y < -DEN_EPS;
           const f2 inv_den = {__builtin_amdgcn_rcpf(den.x), __builtin_amdgcn_rcpf(den.y)};
-          const f2 d0 = sel2(hit0, hit1, f2s(cc.w) * inv_den, f2s(ca.w));
-          const f2 d = {__builtin_amdgcn_fmed3f(d0.x, zlo_m, zhi), __builtin_amdgcn_fmed3f(d0.y, zlo_m, zhi)};
-          sdot = fma2(d, gD[r], sdot);
-          const f2 gd = gD[r] * w;
-          const bool lo0 = d0.x < zlo, lo1 = d0.y < zlo, hi0 = d0.x > zhi, hi1 = d0.y > zhi;
-          const bool mid0 = !lo0 && !hi0, mid1 = !lo1 && !hi1;
-          const f2 zero = {0.f, 0.f};
-          acc(G_ZLO, sel2(lo0, lo1, gd, zero));
-          acc(G_ZHI, sel2(hi0, hi1, gd, zero));
-          const f2 gq = sel2(mid0 && hit0, mid1 && hit1, gd * inv_den, zero);
+          f2 d0 = f2s(cc.w) * inv_den, gq;
+          if (INT) {
+            sdot = fma2(d0, gD[r], sdot);
+            // rounded on its own as in the general trip, where a select stands between the product and the sum
+            gq = mul_rounded(gD[r] * w, inv_den);
+          } else {
+            const bool hit0 = den.x < -DEN_EPS, hit1 = den.y < -DEN_EPS;
+            d0 = sel2(hit0, hit1, d0, f2s(ca.w));
+            const f2 d = {__builtin_amdgcn_fmed3f(d0.x, zlo_m, zhi), __builtin_amdgcn_fmed3f(d0.y, zlo_m, zhi)};
+            sdot = fma2(d, gD[r], sdot);
+            const f2 gd = gD[r] * w;
+            const bool lo0 = d0.x < zlo, lo1 = d0.y < zlo, hi0 = d0.x > zhi, hi1 = d0.y > zhi;
+            const bool mid0 = !lo0 && !hi0, mid1 = !lo1 && !hi1;
+            const f2 zero = {0.f, 0.f};
+            acc(G_ZLO, sel2(lo0, lo1, gd, zero));
+            acc(G_ZHI, sel2(hi0, hi1, gd, zero));
+            gq = sel2(mid0 && hit0, mid1 && hit1, gd * inv_den, zero);
+            acc(G_PZ, sel2(mid0 && !hit0, mid1 && !hit1, gd, zero));
+          }
           acc(G_Q, gq);
-          acc(G_PZ, sel2(mid0 && !hit0, mid1 && !hit1, gd, zero));
           const f2 gden = -gq * d0;  // = -gd * d0 / den on the unclamped ray hit, else 0
           v2[G_NX] = fma2(gden, rx, first ? gN0[r] * w : fma2(gN0[r], w, v2[G_NX]));
           v2[G_NY] = fma2(gden, f2s(ry[r]), first ? gN1[r] * w : fma2(gN1[r], w, v2[G_NY]));
@@ -266,7 +290,8 @@ __device__ __forceinline__ void blend_bwd_tile_body(
         Bs[r] = fma2(av, dLda, Bs[r]);
         dLda = dLda * Tn;
         // alpha = min(0.99, opacity * G): no gradient through the clamp when it is active
-        dLda = sel2(valid[r][0] && raw[r].x <= ALPHA_MAX, valid[r][1] && raw[r].y <= ALPHA_MAX, dLda, f2{0.f, 0.f});
+        dLda = sel2(valid[r][0] && (INT || raw[r].x <= ALPHA_MAX), valid[r][1] && (INT || raw[r].y <= ALPHA_MAX), dLda,
+                    f2{0.f, 0.f});
         acc(G_OPAC, Gs[r] * dLda);
         const f2 dLp = raw[r] * dLda;  // dL/dpower = G * (opacity * dL/dalpha)
         // q = conic . d.  d power / d mean = -q, and d power / d cov2D = 0.5 q q^T: accumulating the
@@ -283,7 +308,7 @@ __device__ __forceinline__ void blend_bwd_tile_body(
         acc(G_CONZ, uy * qy);
         T[r] = Tn;
       }
-      const float tot = wave_reduce16_swap<MODE != MODE_SURFEL>(v2, lane) * red_scale;
+      const float tot = wave_reduce16_swap<MODE != MODE_SURFEL ? RED_ZERO6 : INT ? RED_ZERO3 : RED_FULL>(v2, lane) * red_scale;
       if (red_store) reinterpret_cast<float*>(&sG[j][0])[red_slot] = tot;
       }
     };
@@ -293,7 +318,8 @@ __device__ __forceinline__ void blend_bwd_tile_body(
         a1 = sA[i1]; b1 = sB[i1]; c1 = sC[i1];
         if (MODE == MODE_SURFEL) n1 = sD[i1];
         i0 = (int)sList[jj > 1 ? jj - 2 : 0];
-        trip(a0, b0, c0, n0, j);
+        if ((int_bits >> jj) & 1ull) trip(std::true_type{}, a0, b0, c0, n0, j);
+        else trip(std::false_type{}, a0, b0, c0, n0, j);
       }
       if (jj == 0) break;
       {  // record i1 from set 1; set 0 takes record i0
@@ -301,7 +327,8 @@ __device__ __forceinline__ void blend_bwd_tile_body(
         a0 = sA[i0]; b0 = sB[i0]; c0 = sC[i0];
         if (MODE == MODE_SURFEL) n0 = sD[i0];
         i1 = (int)sList[jj > 2 ? jj - 3 : 0];
-        trip(a1, b1, c1, n1, j);
+        if ((int_bits >> (jj - 1)) & 1ull) trip(std::true_type{}, a1, b1, c1, n1, j);
+        else trip(std::false_type{}, a1, b1, c1, n1, j);
       }
     }
     __syncthreads();
@@ -354,13 +381,13 @@ __global__ __launch_bounds__(64, 3) void blend_bwd_tile_kernel(
     const uint32_t* __restrict__ n_contrib, const float* __restrict__ out_depth, const float* __restrict__ dL_dcolor,
     const float* __restrict__ dL_dnormal, const float* __restrict__ dL_ddepth, const float* __restrict__ dL_dalpha,
     const float* __restrict__ inst_w, const uint32_t* __restrict__ cidx, float* __restrict__ rows,
-    const uint32_t* __restrict__ tile_order, uint32_t num_tiles, GradFill fill) {
+    const uint32_t* __restrict__ tile_order, uint32_t num_tiles, GradFill fill, int interior_on) {
   if (blockIdx.x >= num_tiles) {
     grad_fill_part(fill, blockIdx.x - num_tiles, gridDim.x - num_tiles);
     return;
   }
   blend_bwd_tile_body<MODE>(p, ranges, point_list, rec, gval, final_T, n_contrib, out_depth, dL_dcolor, dL_dnormal,
-                            dL_ddepth, dL_dalpha, inst_w, cidx, rows, tile_order);
+                            dL_ddepth, dL_dalpha, inst_w, cidx, rows, tile_order, interior_on);
 }
 
 // ---------------------------------------------------------------- blend backward, Gaussian-per-lane ("wave64 scan")
@@ -1296,7 +1323,7 @@ PINGS_API int pings_raster_backward(const pings_raster_settings* s, int P, int64
         hipLaunchKernelGGL((blend_bwd_tile_kernel<M>), dim3((unsigned)num_tiles + fill_wgs), dim3(64), 0, st, bp,
                            bs.ranges, bs.point_list, gs.rec, bs.gval, im.final_T, im.n_contrib, out_depth, dL_dcolor,
                            dL_dnormal, dL_ddepth, dL_dalpha, bs.inst_w, bw.cidx, bw.rows, order, (uint32_t)num_tiles,
-                           fill);
+                           fill, (int)plan.interior_bwd);
       }
     });
     PINGS_LAUNCH_CHECK();

@@ -15,6 +15,7 @@
 // only, so the final order inside a tile is (depth, Gaussian index) — the same order a
 // 64-bit (tile<<32 | depth) key sort gives, at a quarter of the sort traffic.
 #pragma once
+#include <cmath>
 #include <cstdlib>
 #include <type_traits>
 
@@ -216,6 +217,7 @@ struct RasterKnobs {
   unsigned rowsum_wgs = 2048u;   // PINGS_ROWSUM_WGS
   unsigned grad_fill_wgs = 512u; // PINGS_GRAD_FILL: fill workgroups behind the blend backward's tiles (0 = own launch)
   bool chain_sum_lanes = false;  // PINGS_CHAIN_SUM
+  bool blend_interior = true;    // PINGS_BLEND_INTERIOR
 };
 RasterKnobs read_knobs();
 
@@ -228,6 +230,7 @@ struct BlendPlan {
   uint32_t seg;        // entries per segment of the segmented forward of long tile lists
   bool seg_on, seg_reuse;
   uint32_t long_thr;   // four-wave split threshold of the scan backward
+  bool interior_bwd;   // the wave-per-tile backward classifies its records (blend_interior) and runs the lean trip
 };
 BlendPlan blend_plan(const RasterKnobs& k, int footprint_class, int64_t I, int num_tiles);
 
@@ -345,6 +348,11 @@ __host__ __device__ inline uint32_t rank_bucket(int r, int nb, uint32_t nvalid) 
 typedef float f2 __attribute__((ext_vector_type(2)));
 __device__ inline f2 f2s(float x) { return f2{x, x}; }
 __device__ inline f2 fma2(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
+// a * b rounded per component even inside a block that lets multiply-adds fuse
+__device__ inline f2 mul_rounded(f2 a, f2 b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
 __device__ inline f2 sel2(bool c0, bool c1, f2 a, f2 b) { return f2{c0 ? a.x : b.x, c1 ? a.y : b.y}; }
 
 // ---------------------------------------------------------------- lane masks of the class-2 blend kernels
@@ -504,6 +512,11 @@ __device__ inline int red16_lane_slot(int lane) {
 #define PINGS_SWAP5(op, a0, b0, a1, b1, a2, b2, a3, b3, a4, b4)                     \
   asm volatile("s_nop 1\n\t" op " %0, %5\n\t" op " %1, %6\n\t" op " %2, %7\n\t" op " %3, %8\n\t" op " %4, %9" \
                : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4))
+#define PINGS_SWAP7(op, a0, b0, a1, b1, a2, b2, a3, b3, a4, b4, a5, b5, a6, b6)                                \
+  asm volatile("s_nop 1\n\t" op " %0, %7\n\t" op " %1, %8\n\t" op " %2, %9\n\t" op " %3, %10\n\t"              \
+               op " %4, %11\n\t" op " %5, %12\n\t" op " %6, %13"                                               \
+               : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3), "+v"(a4), "+v"(a5), "+v"(a6),                          \
+                 "+v"(b0), "+v"(b1), "+v"(b2), "+v"(b3), "+v"(b4), "+v"(b5), "+v"(b6))
 #define PINGS_SWAP8(op, a0, b0, a1, b1, a2, b2, a3, b3, a4, b4, a5, b5, a6, b6, a7, b7)                        \
   asm volatile("s_nop 1\n\t" op " %0, %8\n\t" op " %1, %9\n\t" op " %2, %10\n\t" op " %3, %11\n\t"             \
                op " %4, %12\n\t" op " %5, %13\n\t" op " %6, %14\n\t" op " %7, %15"                             \
@@ -517,12 +530,18 @@ __device__ inline void pair_add(float& r0, float& r1, float a0, float a1, float 
   r1 = r.y;
 }
 
-template <bool ZERO6>
+// ZEROS: which slots the caller knows to be +0 — RED_ZERO6 (3DGS, above) or RED_ZERO3 (a surfel record interior to its
+// tile, blend_interior: G_ZLO, G_ZHI at positions 6 and 14, which meet in the first stage, and G_PZ at 13): their
+// folds are left out, and the swap and the add where zero meets zero.  Where a zero meets a sum the add stays
+// (-0 + 0 = +0), so the result has the bits of the full reduction.
+enum { RED_FULL = 0, RED_ZERO6 = 1, RED_ZERO3 = 2 };
+template <int ZEROS>
 __device__ inline float wave_reduce16_swap(const f2 (&v2)[16], int lane) {
+  constexpr bool ZERO6 = ZEROS == RED_ZERO6, ZERO3 = ZEROS == RED_ZERO3;
   float s[16];
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
-    const bool zero = ZERO6 && ((q & 3) == 3 || (q & 7) == 6);
+    const bool zero = (ZERO6 && ((q & 3) == 3 || (q & 7) == 6)) || (ZERO3 && (q == 6 || q == 13 || q == 14));
     s[q] = zero ? 0.f : v2[red16_slot(q)].x + v2[red16_slot(q)].y;
   }
   float u[8], t[4];
@@ -537,6 +556,17 @@ __device__ inline float wave_reduce16_swap(const f2 (&v2)[16], int lane) {
     pair_add(t[0], t[1], u[0], u[1], u[4], u[5]);
     t[2] = u[2] + z;
     t[3] = 0.f;
+  } else if (ZERO3) {
+    PINGS_SWAP7("v_permlane32_swap_b32", s[0], s[8], s[1], s[9], s[2], s[10], s[3], s[11], s[4], s[12], s[5], s[13],
+                s[7], s[15]);
+    pair_add(u[0], u[1], s[0], s[1], s[8], s[9]);
+    pair_add(u[2], u[3], s[2], s[3], s[10], s[11]);
+    pair_add(u[4], u[5], s[4], s[5], s[12], s[13]);       // position 13 is a zero register: -0 + 0 = +0 as in the full form
+    u[7] = s[7] + s[15];
+    u[6] = 0.f;                                           // 6 and 14 are zero in both halves
+    PINGS_SWAP4("v_permlane16_swap_b32", u[0], u[4], u[1], u[5], u[2], u[6], u[3], u[7]);
+#pragma unroll
+    for (int k = 0; k < 4; k += 2) pair_add(t[k], t[k + 1], u[k], u[k + 1], u[k + 4], u[k + 5]);
   } else {
     PINGS_SWAP8("v_permlane32_swap_b32", s[0], s[8], s[1], s[9], s[2], s[10], s[3], s[11], s[4], s[12], s[5], s[13],
                 s[6], s[14], s[7], s[15]);
@@ -719,11 +749,28 @@ int raster_scan_chunks(const RowRanges& rr, uint32_t* pair_off, uint32_t* pair_o
 // `power` can have (the terms cancel for large anisotropic footprints, so the margin scales with their
 // magnitude): no pixel of the rectangle can pass the alpha test, and skipping the record for the wave that owns
 // the rectangle leaves every output bit unchanged.
-__device__ inline float edge_min_q(float a, float b, float c, float d_fixed, float lo, float hi) {
+// v_rcp_f32 / __expf on the device, 1 / x and expf on the host: the functions below that the host tests and tools call
+// through the library (pings_raster_debug_interior) carry margins that cover either.
+__host__ __device__ inline float fast_rcp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_rcpf(x);
+#else
+  return 1.0f / x;
+#endif
+}
+__host__ __device__ inline float fast_exp(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __expf(x);
+#else
+  return expf(x);
+#endif
+}
+
+__host__ __device__ inline float edge_min_q(float a, float b, float c, float d_fixed, float lo, float hi) {
   // q along the edge {fixed offset d_fixed on one axis, free offset t in [lo, hi] on the other}:
   //   q(t) = a d^2 + 2 b d t + c t^2, minimised at t* = -b d / c, clamped to the edge
   // (1-ulp reciprocal: an error dt in t raises q by c dt^2 ~ 1e-14 c t^2, far below the margin)
-  const float t = fminf(fmaxf(-(b * d_fixed) * __builtin_amdgcn_rcpf(c), lo), hi);
+  const float t = fminf(fmaxf(-(b * d_fixed) * fast_rcp(c), lo), hi);
   const float q0 = a * d_fixed * d_fixed, q1 = 2.f * b * d_fixed * t, q2 = c * t * t;
   return (q0 + q1 + q2) - 2e-5f * (q0 + fabsf(q1) + q2);
 }
@@ -750,6 +797,86 @@ __device__ inline uint32_t quadrant_mask(float mx, float my, float opacity, floa
     if (!footprint_misses_rect(mx, my, cx, cy, cz, thr, x0, x0 + 7.f, y0, y0 + 7.f)) m |= 1u << q;
   }
   return m;
+}
+
+// a_min = a lower bound of the alpha the blend kernels give ANY of the 256 pixel positions of the tile at (X0, Y0)
+// (largest q at the tile corners, fp32 error margins included); 0 if some pixel might be rejected by the
+// alpha >= 1/255 or power <= 0 tests, in particular for the tile that holds the centre.  The occlusion bound
+// (raster_fwd.hip) and blend_interior below rest on it.
+__host__ __device__ inline float tile_min_alpha(float mx, float my, float o, float cx, float cy, float cz, float X0, float Y0) {
+  const float x1 = X0 + 15.f, y1 = Y0 + 15.f;
+  if (mx >= X0 && mx <= x1 && my >= Y0 && my <= y1) return 0.f;
+  float qmax = 0.f;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const float dx = ((c & 1) ? x1 : X0) - mx, dy = ((c & 2) ? y1 : Y0) - my;
+    const float q0 = cx * dx * dx, q1 = 2.f * cy * dx * dy, q2 = cz * dy * dy;
+    qmax = fmaxf(qmax, (q0 + q1 + q2) + 2e-5f * (q0 + fabsf(q1) + q2));
+  }
+  const float a = fminf(ALPHA_MAX, o * fast_exp(-0.5f * (qmax + 1e-3f)) * (1.f - 1e-5f));
+  if (!(a >= ALPHA_MIN * 1.001f)) return 0.f;
+  // the smallest q over the tile must be safely positive, or the kernel's `power <= 0` test might drop a pixel
+  const float lx = X0 - mx, hx = x1 - mx, ly = Y0 - my, hy = y1 - my;
+  float m = edge_min_q(cx, cy, cz, lx, ly, hy);
+  m = fminf(m, edge_min_q(cx, cy, cz, hx, ly, hy));
+  m = fminf(m, edge_min_q(cz, cy, cx, ly, lx, hx));
+  m = fminf(m, edge_min_q(cz, cy, cx, hy, lx, hx));
+  if (!(m > 1e-6f)) return 0.f;
+  return a;
+}
+
+// ---------------------------------------------------------------- records interior to a tile (class-2 blend kernels)
+// For most (record, tile) pairs the per-pixel decisions of the blend come out the same at all 256 pixel positions.
+// blend_interior is true only if that is CERTAIN, for every position of the 16x16 tile (positions outside the image
+// included), in the kernels' own fp32 evaluation; blend_bwd_tile_kernel then runs a trip without those decisions (the
+// forward's such body was measured and is not kept: DESIGN §8 item 1, r18).  A wrong
+// `true` changes output bits, a wrong `false` only costs time, and every comparison is written so that a NaN gives false.
+//   (a) alpha: every pixel passes alpha >= ALPHA_MIN and power <= 0 (tile_min_alpha > 0: the smallest q over the tile
+//       exceeds 1e-6, so power < -4e-7), and opacity < ALPHA_MAX: exp(power) <= 1 there (a result above 1 would take
+//       an error of more than 4e-7, six ulp), rounding is monotone, so opacity * exp(power) <= ALPHA_MAX and
+//       min(ALPHA_MAX, .) is the identity, as is the backward's `raw <= ALPHA_MAX`.
+//   (b) surfel depth: den = nx rx + ny ry + nz < -DEN_EPS at every pixel and zlo < d0 = q / den < zhi, so that the
+//       ray hit is taken and med3(d0, zlo, zhi) = d0.  rx = (x - cxp) / fx is a correctly rounded quotient, monotone
+//       in x, so every pixel's (rx, ry) lies in the box of the tile's first and last column and row (TileRays: the
+//       kernels' own expressions at those pixels).  den is affine in (rx, ry): in exact arithmetic its extremes over
+//       the box are at the corners, and d0 is monotone in den while den keeps its sign, so its extremes are at the
+//       corners with the largest and the smallest den.
+//       Margins.  With u = 2^-24 and mag = |nx| max|rx| + |ny| max|ry| + |nz|: the forward's (nx rx + ny ry) + nz
+//       rounds two products and two sums, the backward's fma(nx, rx, fma(ny, ry, nz)) two fmas; every intermediate is
+//       at most mag (1 + 3u), so either is within 4 u mag = 2.4e-7 mag of the exact value, and so are the corner values
+//       computed here.  E_DEN = 1e-6 mag is more than twice the sum of both.  For d0 = q * rcp(den): the relative error
+//       of den is at most 2.4e-7 mag / |den|, v_rcp_f32 is good to one ulp (1.2e-7) and the product rounds once
+//       (0.6e-7); the corner values here carry the same (1 / x and a product on the host).  The relative margin
+//       1e-6 mag / |den|_min + 1e-6 is more than twice the sum of both again, taken of the larger |d0|.
+struct TileRays {
+  float rx0, rx1, ry0, ry1;   // (x - cxp) / fx at columns X0 and X0 + 15, (y - cyp) / fy at rows Y0 and Y0 + 15
+};
+__host__ __device__ inline TileRays tile_rays(float X0, float Y0, float cxp, float cyp, float fx, float fy) {
+  return TileRays{(X0 - cxp) / fx, ((X0 + 15.f) - cxp) / fx, (Y0 - cyp) / fy, ((Y0 + 15.f) - cyp) / fy};
+}
+// the four wave-uniform values in scalar registers: they live across the whole record loop
+__device__ inline TileRays tile_rays_uniform(const TileRays& t) {
+  auto u = [](float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v))); };
+  return TileRays{u(t.rx0), u(t.rx1), u(t.ry0), u(t.ry1)};
+}
+constexpr float INTERIOR_DEN_MARGIN = 1e-6f, INTERIOR_D0_MARGIN = 1e-6f;
+// a = {mx, my, opacity, pz}, b = {conic x, y, z, rz}, q and (nx, ny, nz) as in the record (see the top of the file)
+__host__ __device__ inline bool blend_interior(float mx, float my, float opacity, float pz, float cx, float cy, float cz,
+                                               float rz, float q, float nx, float ny, float nz, float X0, float Y0,
+                                               const TileRays& t) {
+  if (!(opacity < ALPHA_MAX)) return false;   // (0.99 itself would do; the strict test keeps the boundary out)
+  const float ax = fmaxf(fabsf(t.rx0), fabsf(t.rx1)), ay = fmaxf(fabsf(t.ry0), fabsf(t.ry1));
+  const float e_den = INTERIOR_DEN_MARGIN * (fabsf(nx) * ax + fabsf(ny) * ay + fabsf(nz));
+  const float y0 = ny * t.ry0, y1 = ny * t.ry1, x0 = nx * t.rx0, x1 = nx * t.rx1;
+  const float d00 = (x0 + y0) + nz, d10 = (x1 + y0) + nz, d01 = (x0 + y1) + nz, d11 = (x1 + y1) + nz;
+  const float den_max = fmaxf(fmaxf(d00, d10), fmaxf(d01, d11)), den_min = fminf(fminf(d00, d10), fminf(d01, d11));
+  if (!(den_max + e_den < -DEN_EPS)) return false;
+  const float inv_max = fast_rcp(den_max);   // the largest |1 / den|
+  const float da = q * inv_max, db = q * fast_rcp(den_min);
+  const float dlo = fminf(da, db), dhi = fmaxf(da, db);
+  const float m = fmaxf(fabsf(da), fabsf(db)) * (INTERIOR_D0_MARGIN - e_den * inv_max);   // inv_max < 0
+  if (!(dlo - m > pz - rz && dhi + m < pz + rz)) return false;
+  return tile_min_alpha(mx, my, opacity, cx, cy, cz, X0, Y0) > 0.f;
 }
 
 }  // namespace raster

@@ -450,27 +450,7 @@ __device__ inline void walk_items_coop(unsigned long long big, const RectLane& m
 // Instances of later buckets are never created: the sort, the per-instance arrays and the staging of the blend
 // kernels shrink to the lists that can matter (Metric-1: 16.9 M -> 1.8 M), and every output stays bit-identical,
 // because a culled instance would never have been blended.  The kept list of a tile is a prefix of its full list.
-__device__ inline float tile_min_alpha(float mx, float my, float o, float cx, float cy, float cz, float X0, float Y0) {
-  const float x1 = X0 + 15.f, y1 = Y0 + 15.f;
-  if (mx >= X0 && mx <= x1 && my >= Y0 && my <= y1) return 0.f;
-  float qmax = 0.f;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const float dx = ((c & 1) ? x1 : X0) - mx, dy = ((c & 2) ? y1 : Y0) - my;
-    const float q0 = cx * dx * dx, q1 = 2.f * cy * dx * dy, q2 = cz * dy * dy;
-    qmax = fmaxf(qmax, (q0 + q1 + q2) + 2e-5f * (q0 + fabsf(q1) + q2));
-  }
-  const float a = fminf(ALPHA_MAX, o * __expf(-0.5f * (qmax + 1e-3f)) * (1.f - 1e-5f));
-  if (!(a >= ALPHA_MIN * 1.001f)) return 0.f;
-  // the smallest q over the tile must be safely positive, or the kernel's `power <= 0` test might drop a pixel
-  const float lx = X0 - mx, hx = x1 - mx, ly = Y0 - my, hy = y1 - my;
-  float m = edge_min_q(cx, cy, cz, lx, ly, hy);
-  m = fminf(m, edge_min_q(cx, cy, cz, hx, ly, hy));
-  m = fminf(m, edge_min_q(cz, cy, cx, ly, lx, hx));
-  m = fminf(m, edge_min_q(cz, cy, cx, hy, lx, hx));
-  if (!(m > 1e-6f)) return 0.f;
-  return a;
-}
+// tile_min_alpha itself: raster_common.hpp (the blend kernels' interior test rests on it as well).
 
 // ---------------------------------------------------------------- depth order of the preprocessed Gaussians
 // A library radix / merge sort of P = 1M (key, index) pairs costs 20 launches and 150 us, more than the preprocess
@@ -1018,6 +998,19 @@ PINGS_API int pings_raster_rank_bucket(const int32_t* ranks, int64_t n, int occ_
                                        uint32_t* buckets) {
   PINGS_ARG_CHECK(n >= 0 && occ_nb > 0 && (n == 0 || (ranks && buckets)), "null pointer / non-positive bucket count");
   for (int64_t i = 0; i < n; ++i) buckets[i] = rank_bucket(ranks[i], occ_nb, nvalid);
+  return PINGS_OK;
+}
+
+PINGS_API int pings_raster_debug_interior(const float* records, const float* tile_origins, int64_t n, float cxp,
+                                          float cyp, float fx, float fy, uint8_t* flags) {
+  PINGS_ARG_CHECK(n >= 0 && (n == 0 || (records && tile_origins && flags)), "null pointer / negative count");
+  PINGS_ARG_CHECK(fx > 0.f && fy > 0.f, "non-positive focal length");
+  for (int64_t i = 0; i < n; ++i) {
+    const float* r = records + 16 * i;
+    const float X0 = tile_origins[2 * i], Y0 = tile_origins[2 * i + 1];
+    flags[i] = blend_interior(r[0], r[1], r[2], r[3], r[4], r[5], r[6], r[7], r[11], r[12], r[13], r[14], X0, Y0,
+                              tile_rays(X0, Y0, cxp, cyp, fx, fy)) ? 1 : 0;
+  }
   return PINGS_OK;
 }
 

@@ -177,6 +177,9 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
 //                                                                   grad_zero_kernel, a launch of its own (always when there is no instance)
 //   PINGS_CHAIN_SUM         group | l(anes)           tests, A/B    first letter l: gaussian_bwd_rank_kernel sums an owner's chunk partials
 //                                                                   in the owner's lane instead of by 16-lane groups; same bits
+//   PINGS_BLEND_INTERIOR    1 | 0                     tests, A/B    the lean trip of blend_bwd_tile_kernel for surfel records interior to
+//                                                                   their tile (blend_interior); 0 = every record through the general trip;
+//                                                                   same bits
 RasterKnobs read_knobs() {
   RasterKnobs k;   // the defaults: raster_common.hpp
   if (const char* e = getenv("PINGS_BLEND_PPL")) k.blend_ppl = atoi(e);
@@ -210,6 +213,7 @@ RasterKnobs read_knobs() {
   if (const char* e = getenv("PINGS_ROWSUM_WGS")) k.rowsum_wgs = (unsigned)std::min(std::max(atoi(e), 1), 65535);
   if (const char* e = getenv("PINGS_GRAD_FILL")) k.grad_fill_wgs = e[0] == 'l' ? 0u : (unsigned)std::min(std::max(atoi(e), 1), 65535);
   if (const char* e = getenv("PINGS_CHAIN_SUM")) k.chain_sum_lanes = e[0] == 'l';
+  if (const char* e = getenv("PINGS_BLEND_INTERIOR")) k.blend_interior = atoi(e) != 0;
   return k;
 }
 
@@ -236,6 +240,7 @@ BlendPlan blend_plan(const RasterKnobs& k, int footprint_class, int64_t I, int n
   p.seg_on = p.seg > 0 && I > (int64_t)num_tiles * (p.seg / 4) && I > 2 * (int64_t)p.seg;
   p.seg_reuse = p.seg <= 65535u && k.seg_reuse;
   p.long_thr = k.bwd_long;
+  p.interior_bwd = k.blend_interior;
   return p;
 }
 
