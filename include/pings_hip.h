@@ -1665,4 +1665,50 @@ PINGS_API int pings_tsdf_vertices(const int64_t* keys, int64_t nv, const float* 
                                   int64_t nx, int64_t ny, int64_t nz, const double* origin, double voxel_length,
                                   float* verts, float* colors, void* stream);
 
+/* ------------------------------------------------------ pose-graph optimisation (csrc/pgo.hip)
+ * Poses X [n_nodes, 4, 4] fp64 (T_world<-frame, row-major).  Factor f: fi[f], fj[f] (-1: a prior), Z [f, 4, 4],
+ * W [f, 6, 6] the square-root information, rotation first.  r = W Log(Z^-1 X_i^-1 X_j) (prior: W Log(Z^-1 X_i)),
+ * cost = 1/2 sum |r|^2, update X <- X Exp(delta).  The caller classifies the factors once per graph change:
+ *   kind[f]   PINGS_PGO_PRIOR, PINGS_PGO_CHAIN (|i - j| = 1) or PINGS_PGO_LOOP; lcol[f] the loop's number 0 .. n_loops-1
+ *   loop_f [n_loops]: the factor of every loop, the inverse of lcol
+ *   node_off [n_nodes + 1], node_ent [n_entries]: per node the list of 2 f + slot (slot 0: the node is fi, 1: fj),
+ *   in the order the contributions are summed.
+ * The normal matrix is block tridiagonal plus U U^T with 6 columns per loop.  pings_pgo_iteration queues ONE
+ * Levenberg-Marquardt trial: linearise, assemble, damp with lambda diag(H), block Cholesky, sweeps for 1 + 6 n_loops
+ * right-hand sides in chunks of `chunk` columns (a multiple of 64), the dense capacitance system, the last sweep, the
+ * retraction into a candidate, its cost, and the decision, all on the device.
+ *   state  [8] fp64 DEVICE: 0 lambda (set by the caller before the first trial), 1 cost before, 2 cost after, rest
+ *          workspace.   status [1] int32 DEVICE, sticky bits PINGS_PGO_ST_*; the caller clears it.
+ *   record [8] fp64 DEVICE: cost before, cost after, lambda of this trial, accepted, status, iteration, 0, 0.
+ * A trial is accepted iff cost after <= cost before (lambda / 10, X <- candidate), else lambda * 10.
+ * PINGS_PGO_ST_CONVERGED: accepted with before - after <= rel_tol * before; PINGS_PGO_ST_LAMBDA_MAX: lambda passed
+ * 1e5.  pings_pgo_read_record is the one host read of a trial.  pings_pgo_cost: out_cost[0] = the cost at `poses`
+ * (status bits OR-ed into args->status).  pings_pgo_pose_diff: out64 / out32 (each nullable) [n, 4, 4] =
+ * after[n] before[n]^-1, rigid inverse.  scratch: pings_pgo_scratch_bytes(n_nodes, n_factors, n_loops, chunk). */
+#define PINGS_PGO_PRIOR 0
+#define PINGS_PGO_CHAIN 1
+#define PINGS_PGO_LOOP 2
+#define PINGS_PGO_ST_NEAR_PI 1
+#define PINGS_PGO_ST_NOT_POSDEF 2
+#define PINGS_PGO_ST_NONFINITE 4
+#define PINGS_PGO_ST_CONVERGED 8
+#define PINGS_PGO_ST_LAMBDA_MAX 16
+#define PINGS_PGO_RECORD 8
+typedef struct {
+  int64_t n_nodes, n_factors, n_loops, n_entries;
+  int32_t chunk, iteration;
+  double rel_tol;
+  const int32_t *fi, *fj, *kind, *lcol, *loop_f, *node_off, *node_ent;
+  const double *Z, *W;
+  double *X, *state, *record;
+  int32_t* status;
+  void* scratch;
+} pings_pgo_args;
+PINGS_API size_t pings_pgo_scratch_bytes(int64_t n_nodes, int64_t n_factors, int64_t n_loops, int32_t chunk);
+PINGS_API int pings_pgo_cost(const pings_pgo_args* args, const double* poses, double* out_cost, void* stream);
+PINGS_API int pings_pgo_iteration(const pings_pgo_args* args, void* stream);
+PINGS_API int pings_pgo_read_record(const double* record_dev, double* record_host, void* stream);
+PINGS_API int pings_pgo_pose_diff(const double* after, const double* before, int64_t n, double* out64, float* out32,
+                                  void* stream);
+
 #endif /* PINGS_HIP_H_ */

@@ -28,6 +28,9 @@ CAMFRONT_FIT_RECORD, CAMFRONT_MIN_FIT = 5, 100                    # doubles per 
 CAMFRONT_FULL = 2                                                 # status bit of pings_camfront_voxel_average
 TSDF_BLOCK = 8                                                    # PINGS_TSDF_BLOCK: voxels per block edge
 TSDF_EXTENT, TSDF_TABLE_FULL = 1, 2                               # PINGS_TSDF_*: status bits of pings_tsdf_touch
+PGO_PRIOR, PGO_CHAIN, PGO_LOOP = 0, 1, 2                          # PINGS_PGO_*: pings_pgo_args.kind
+PGO_ST_NEAR_PI, PGO_ST_NOT_POSDEF, PGO_ST_NONFINITE, PGO_ST_CONVERGED, PGO_ST_LAMBDA_MAX = 1, 2, 4, 8, 16   # status bits
+PGO_RECORD = 8                                                    # PINGS_PGO_RECORD: doubles per trial record
 
 vp = C.c_void_p     # device pointers and the hipStream_t travel as integers (tensor.data_ptr())
 i32, i64, f32, f64, sz = C.c_int, C.c_int64, C.c_float, C.c_double, C.c_size_t
@@ -185,6 +188,13 @@ class CamfrontMap(C.Structure):
     _fields_ = [(n, vp) for n in ("src", "l0", "l1", "l2", "l3")] + \
                [(n, C.c_int64) for n in ("stride_c", "stride_y", "stride_x")] + \
                [(n, C.c_int32) for n in ("H", "W", "kind", "reserved")]
+
+
+class PgoArgs(C.Structure):
+    _fields_ = [(n, C.c_int64) for n in ("n_nodes", "n_factors", "n_loops", "n_entries")] + \
+               [("chunk", C.c_int32), ("iteration", C.c_int32), ("rel_tol", C.c_double)] + \
+               [(n, vp) for n in ("fi", "fj", "kind", "lcol", "loop_f", "node_off", "node_ent", "Z", "W", "X", "state", "record",
+                                  "status", "scratch")]
 
 
 # ---------------------------------------------------------------- entry points: {name: (restype, argtypes)}
@@ -439,4 +449,10 @@ SIGNATURES = {
                                 i64, vp, vp, i64, i64, vp, vp, vp, vp]),
     "pings_tsdf_densify": (i32, [vp, vp, i64, i64, vp, vp, vp, C.POINTER(i64), i64, i64, i64, f32, vp, vp, vp, vp]),
     "pings_tsdf_vertices": (i32, [vp, i64, vp, vp, C.POINTER(i64), i64, i64, i64, C.POINTER(f64), f64, vp, vp, vp]),
+    # pose-graph optimisation
+    "pings_pgo_scratch_bytes": (sz, [i64, i64, i64, i32]),
+    "pings_pgo_cost": (i32, [C.POINTER(PgoArgs), vp, vp, vp]),
+    "pings_pgo_iteration": (i32, [C.POINTER(PgoArgs), vp]),
+    "pings_pgo_read_record": (i32, [vp, vp, vp]),
+    "pings_pgo_pose_diff": (i32, [vp, vp, i64, vp, vp, vp]),
 }
