@@ -1665,6 +1665,46 @@ PINGS_API int pings_tsdf_vertices(const int64_t* keys, int64_t nv, const float* 
                                   int64_t nx, int64_t ny, int64_t nz, const double* origin, double voxel_length,
                                   float* verts, float* colors, void* stream);
 
+/* ------------------------------------------------------ LiDAR scans into the TSDF volume (csrc/tsdf_points.hip, §2.9b)
+ * points [n, 3] fp32 world frame, colors [n, 3] fp32 in [0, 1] or NULL, sensor [3] fp32 DEVICE; n <=
+ * PINGS_TSDF_POINTS_MAX.  Table, store, key and origin as above; tindex [tsize] int32 DEVICE workspace (the place of
+ * an entry in `touched`, valid for entries stamped with this `frame`).  A point is valid iff it is finite and
+ * min_range < r < max_range, r = |p - sensor|.  Grid point g owns the half-open cube of edge voxel_length around it;
+ * the ray sensor + s d, d = (p - sensor) / r, samples every cube it crosses with a positive chord for s in [s0, s1],
+ * s1 = r + sdf_trunc, s0 = max(0, r - sdf_trunc), or 0 with space_carving (which needs a finite max_range).
+ *   touch       files the blocks floor(g / 8) of the samples exactly as pings_tsdf_touch does (same lists, counters,
+ *               totals and status bits); list_cap >= 8 n without carving, else the caller's bound on the blocks of a
+ *               call.  totals[3] (HOST) is the call's one read.
+ *   (pings_tsdf_assign, unchanged, gives the new blocks their slots.)
+ *   accumulate  per sample with centre c: sdf = sign((c - o).(p - c)) |p - c| (PINGS_TSDF_SDF_POINT, sign(0) = +1) or
+ *               r - (c - o).d (PINGS_TSDF_SDF_RAY); it counts iff sdf > -sdf_trunc, with t = min(1, sdf / sdf_trunc)
+ *               quantised once, q = rint(t 2^PINGS_TSDF_POINTS_SCALE_BITS), colours likewise.  acc [n_touched, P, 512]
+ *               uint64, P = 4 with colors and 1 without, ZEROED by the caller: plane 0 receives
+ *               1 << PINGS_TSDF_POINTS_COUNT_SHIFT | (q + 2^PINGS_TSDF_POINTS_SCALE_BITS) per sample, planes 1..3 the
+ *               colour q, all by 64-bit integer atomic adds.
+ *   apply       per voxel with count n > 0 and exact sum S = sum q / 2^SCALE_BITS: tsdf <- fl32((tsdf w + S) / (w + n))
+ *               in fp64, colour likewise, w <- min(w + n, max_weight) (INFINITY: no cap); n = 0 leaves every bit. */
+#define PINGS_TSDF_POINTS_SCALE_BITS 22
+#define PINGS_TSDF_POINTS_COUNT_SHIFT 44
+#define PINGS_TSDF_POINTS_MAX 1048575
+#define PINGS_TSDF_SDF_POINT 0
+#define PINGS_TSDF_SDF_RAY 1
+PINGS_API int pings_tsdf_points_touch(const float* points, int64_t n, const float* sensor, const double* origin,
+                                      double voxel_length, double sdf_trunc, float min_range, float max_range,
+                                      int space_carving, int frame, int64_t* tkeys, const int32_t* tslots,
+                                      int32_t* tstamps, int32_t* tindex, int64_t tsize, int64_t list_cap,
+                                      int32_t* touched, int64_t* new_keys, int32_t* counters, int64_t* totals,
+                                      void* stream);
+PINGS_API int pings_tsdf_points_accumulate(const float* points, const float* colors, int64_t n, const float* sensor,
+                                           const double* origin, double voxel_length, double sdf_trunc,
+                                           float min_range, float max_range, int space_carving, int sdf_mode,
+                                           int frame, const int64_t* tkeys, const int32_t* tslots,
+                                           const int32_t* tstamps, const int32_t* tindex, int64_t tsize,
+                                           int64_t n_touched, uint64_t* acc, void* stream);
+PINGS_API int pings_tsdf_points_apply(const int32_t* touched, int64_t n_touched, const int32_t* tslots, int64_t tsize,
+                                      int64_t capacity, const uint64_t* acc, int with_color, float max_weight,
+                                      float* tsdf, float* weight, float* color, void* stream);
+
 /* ------------------------------------------------------ pose-graph optimisation (csrc/pgo.hip)
  * Poses X [n_nodes, 4, 4] fp64 (T_world<-frame, row-major).  Factor f: fi[f], fj[f] (-1: a prior), Z [f, 4, 4],
  * W [f, 6, 6] the square-root information, rotation first.  r = W Log(Z^-1 X_i^-1 X_j) (prior: W Log(Z^-1 X_i)),

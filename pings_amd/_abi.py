@@ -28,6 +28,9 @@ CAMFRONT_FIT_RECORD, CAMFRONT_MIN_FIT = 5, 100                    # doubles per 
 CAMFRONT_FULL = 2                                                 # status bit of pings_camfront_voxel_average
 TSDF_BLOCK = 8                                                    # PINGS_TSDF_BLOCK: voxels per block edge
 TSDF_EXTENT, TSDF_TABLE_FULL = 1, 2                               # PINGS_TSDF_*: status bits of pings_tsdf_touch
+TSDF_POINTS_SCALE_BITS, TSDF_POINTS_COUNT_SHIFT = 22, 44          # a scan's sample is rint(t * 2^22); count << 44 | sum
+TSDF_POINTS_MAX = 1048575                                         # points per scan: the count field holds 20 bits
+TSDF_SDF_POINT, TSDF_SDF_RAY = 0, 1                               # PINGS_TSDF_SDF_*: sdf_mode of pings_tsdf_points_*
 PGO_PRIOR, PGO_CHAIN, PGO_LOOP = 0, 1, 2                          # PINGS_PGO_*: pings_pgo_args.kind
 PGO_ST_NEAR_PI, PGO_ST_NOT_POSDEF, PGO_ST_NONFINITE, PGO_ST_CONVERGED, PGO_ST_LAMBDA_MAX = 1, 2, 4, 8, 16   # status bits
 PGO_RECORD = 8                                                    # PINGS_PGO_RECORD: doubles per trial record
@@ -449,6 +452,12 @@ SIGNATURES = {
                                 i64, vp, vp, i64, i64, vp, vp, vp, vp]),
     "pings_tsdf_densify": (i32, [vp, vp, i64, i64, vp, vp, vp, C.POINTER(i64), i64, i64, i64, f32, vp, vp, vp, vp]),
     "pings_tsdf_vertices": (i32, [vp, i64, vp, vp, C.POINTER(i64), i64, i64, i64, C.POINTER(f64), f64, vp, vp, vp]),
+    # LiDAR scans into the TSDF volume
+    "pings_tsdf_points_touch": (i32, [vp, i64, vp, C.POINTER(f64), f64, f64, f32, f32, i32, i32, vp, vp, vp, vp, i64, i64,
+                                      vp, vp, vp, C.POINTER(i64), vp]),
+    "pings_tsdf_points_accumulate": (i32, [vp, vp, i64, vp, C.POINTER(f64), f64, f64, f32, f32, i32, i32, i32, vp, vp, vp,
+                                           vp, i64, i64, vp, vp]),
+    "pings_tsdf_points_apply": (i32, [vp, i64, vp, i64, i64, vp, i32, f32, vp, vp, vp, vp]),
     # pose-graph optimisation
     "pings_pgo_scratch_bytes": (sz, [i64, i64, i64, i32]),
     "pings_pgo_cost": (i32, [C.POINTER(PgoArgs), vp, vp, vp]),

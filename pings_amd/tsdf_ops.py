@@ -3,13 +3,15 @@
 between `render(...)["surf_depth"]` and `mesh_ops.finish_mesh` / `eval_ops.eval_pair`.
 
   TSDFVolume.integrate     one depth (+ colour) view: touch -> (one host read) -> assign new blocks -> update
+  TSDFVolume.integrate_points  one LiDAR scan, optionally carving free space (csrc/tsdf_points.hip):
+                           ray touch -> (one host read) -> assign -> accumulate integer sums -> apply
   TSDFVolume.dense         a box of grid points as dense tsdf / weight / colour arrays
   TSDFVolume.extract_mesh  per chunk densify -> marching cubes (csrc/mc.hip, unchanged) -> vertices from global integers,
                            then `mesh_ops.finish_mesh`
-  install(module)          rebinds `SLAMDataset.o3d_tsdf_fusion`
+  install(module)          rebinds `SLAMDataset.o3d_tsdf_fusion`; with `lidar=True` adds `SLAMDataset.lidar_tsdf_fusion`
 
 Images are fp32 tensors on the HIP device and a CPU tensor raises `PingsHipError`: there is no CPU fallback.  The
-rules are restated in fp64 numpy by tests/tsdf_ref.py.  Every host read is recorded with `_lib.note_sync`."""
+rules are restated in fp64 numpy by tests/tsdf_ref.py and tests/tsdf_points_ref.py.  Every host read is recorded with `_lib.note_sync`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -94,7 +96,7 @@ class TSDFVolume:
         self.n_blocks, self.capacity, self._frame = 0, 0, 0
         self._keys = self._tsdf = self._weight = self._color = None
         self._tkeys = self._tslots = self._tstamps = None
-        self._lists = None
+        self._lists = self._tindex = None
         self._reserve(self._capacity0)
 
     def _reserve(self, blocks: int) -> None:
@@ -204,6 +206,106 @@ class TSDFVolume:
                        "pings_tsdf_update")
         if status & _abi.TSDF_EXTENT:
             raise _lib.PingsHipError("tsdf_ops: a pixel lies beyond 2**20 blocks from the origin and was left out; "
+                                     "use a larger voxel_length or an origin near the scene")
+
+    # ------------------------------------------------------------------ integrate a LiDAR scan
+    def _points_block_bound(self, n: int, space_carving: bool, max_range: float) -> int:
+        """A host-side bound on the blocks one scan can name, so that table and lists are sized without a read."""
+        if not space_carving:
+            return 8 * n                          # a segment of 2 sdf_trunc plus one cube: 2 blocks per axis
+        edge, reach = B * self.voxel_length, max_range + self.sdf_trunc
+        per_ray = 3 * (math.floor(reach / edge) + 2) - 2            # a line leaves a block through one face at a time
+        cube = (math.ceil(2.0 * reach / edge) + 2) ** 3             # every block within reach of the sensor
+        return min(n * per_ray, cube)
+
+    def integrate_points(self, points, origin, colors=None, *, space_carving=False, sdf_mode="point", min_range=0.0,
+                         max_range=math.inf, max_weight=None) -> None:
+        """Fuses one LiDAR scan.  points [N, 3] fp32 in the world frame, valid where finite and min_range < |p - o| <
+        max_range; origin the sensor position o, a host sequence of 3 or a device tensor [3] (taken without a host
+        copy); colors [N, 3] fp32 in [0, 1] (required with a colour volume).  Every valid point's ray samples the
+        voxels whose cubes it crosses between max(0, r - sdf_trunc) (0 with `space_carving`, which needs a finite
+        max_range) and r + sdf_trunc; `sdf_mode` is "point" (signed distance to the point, VDB-Fusion's) or "ray" (the
+        projective distance along the ray).  A voxel averages all its samples of the call at once from exact integer
+        sums, so the store does not depend on the order of the rows; `max_weight` caps the weight afterwards.  One host
+        read (touched and new block counts and the status); a scan without a valid point ends after it."""
+        if not isinstance(points, torch.Tensor) or points.dim() != 2 or points.shape[1] != 3:
+            raise ValueError("points must be a [N, 3] tensor")
+        n = int(points.shape[0])
+        pts = _image("points", points, [(n, 3)])
+        if self.color and colors is None:
+            raise ValueError("a colour volume needs the scan's colours")
+        col = _image("colors", colors, [(n, 3)]) if self.color else None
+        if pts.device != self.device or (col is not None and col.device != self.device):
+            raise _lib.PingsHipError(f"TSDFVolume on {self.device} got a scan on {pts.device}")
+        if sdf_mode not in ("point", "ray"):
+            raise ValueError(f"sdf_mode must be 'point' or 'ray', got {sdf_mode!r}")
+        min_range, max_range = float(min_range), float(max_range)
+        if not (0.0 <= min_range < max_range):
+            raise ValueError(f"0 <= min_range < max_range, got {min_range} and {max_range}")
+        if space_carving and not math.isfinite(max_range):
+            raise ValueError("space carving needs a finite max_range: it bounds the blocks a scan can name")
+        if n > _abi.TSDF_POINTS_MAX:
+            raise ValueError(f"a scan holds at most {_abi.TSDF_POINTS_MAX} points (the count field of the accumulators), "
+                             f"got {n}; split it")
+        cap = math.inf if max_weight is None else float(max_weight)
+        if not cap >= 1.0:
+            raise ValueError(f"max_weight must be at least 1, got {max_weight}")
+        dev, L = self.device, _lib.lib()
+        if isinstance(origin, torch.Tensor):
+            if origin.device != dev or origin.numel() != 3:
+                raise ValueError(f"origin must be a tensor of 3 on {dev} or a host sequence of 3")
+            sensor = origin.detach().reshape(3).to(torch.float32).contiguous()
+        else:
+            o = np.asarray(origin, dtype=np.float64).reshape(-1)
+            if o.shape != (3,):
+                raise ValueError("origin must have 3 components")
+            sensor = torch.tensor(o.tolist(), dtype=torch.float32, device=dev)
+        org, st = _f64x(self.origin), _lib.stream_ptr(dev)
+        mode = _abi.TSDF_SDF_RAY if sdf_mode == "ray" else _abi.TSDF_SDF_POINT
+        carve = int(bool(space_carving))
+
+        list_cap = max(1, self._points_block_bound(n, carve, max_range))
+        self._table(self.n_blocks + list_cap)
+        if self._lists is None or self._lists[0].shape[0] < list_cap:
+            self._lists = (torch.empty(list_cap, dtype=torch.int32, device=dev),
+                           torch.empty(list_cap, dtype=torch.int64, device=dev),
+                           torch.zeros(4, dtype=torch.int32, device=dev))
+        touched, new_keys, counters = self._lists
+        tsize = self._tkeys.shape[0]
+        if self._tindex is None or self._tindex.shape[0] != tsize:
+            self._tindex = torch.empty(tsize, dtype=torch.int32, device=dev)
+        self._frame += 1
+        tot = (C.c_int64 * 3)(0, 0, 0)
+        _lib.note_sync("tsdf_touch_points")
+        _lib.check(L.pings_tsdf_points_touch(_lib.ptr(pts), n, _lib.ptr(sensor), org, self.voxel_length, self.sdf_trunc,
+                                             min_range, max_range, carve, self._frame, _lib.ptr(self._tkeys),
+                                             _lib.ptr(self._tslots), _lib.ptr(self._tstamps), _lib.ptr(self._tindex),
+                                             tsize, touched.shape[0], _lib.ptr(touched), _lib.ptr(new_keys),
+                                             _lib.ptr(counters), tot, st), "pings_tsdf_points_touch")
+        n_touched, n_new, status = int(tot[0]), int(tot[1]), int(tot[2])
+        if status & _abi.TSDF_TABLE_FULL or n_touched > list_cap:
+            raise _lib.PingsHipError("tsdf_ops internal error: a scan named more blocks than its bound")
+        if n_new:
+            self._reserve(self.n_blocks + n_new)
+            scratch = torch.empty(L.pings_tsdf_assign_scratch_bytes(n_new), dtype=torch.uint8, device=dev)
+            _lib.check(L.pings_tsdf_assign(_lib.ptr(new_keys), n_new, self.n_blocks, self.capacity, _lib.ptr(scratch),
+                                           _lib.ptr(self._tkeys), _lib.ptr(self._tslots), tsize, _lib.ptr(self._keys),
+                                           _lib.ptr(self._tsdf), _lib.ptr(self._weight), _lib.ptr(self._color), st),
+                       "pings_tsdf_assign")
+            self.n_blocks += n_new
+        if n_touched:
+            acc = torch.zeros((n_touched, 4 if self.color else 1, VOX), dtype=torch.int64, device=dev)   # one fill
+            _lib.check(L.pings_tsdf_points_accumulate(_lib.ptr(pts), _lib.ptr(col), n, _lib.ptr(sensor), org,
+                                                      self.voxel_length, self.sdf_trunc, min_range, max_range, carve,
+                                                      mode, self._frame, _lib.ptr(self._tkeys), _lib.ptr(self._tslots),
+                                                      _lib.ptr(self._tstamps), _lib.ptr(self._tindex), tsize, n_touched,
+                                                      _lib.ptr(acc), st), "pings_tsdf_points_accumulate")
+            _lib.check(L.pings_tsdf_points_apply(_lib.ptr(touched), n_touched, _lib.ptr(self._tslots), tsize,
+                                                 self.capacity, _lib.ptr(acc), int(self.color), cap,
+                                                 _lib.ptr(self._tsdf), _lib.ptr(self._weight), _lib.ptr(self._color), st),
+                       "pings_tsdf_points_apply")
+        if status & _abi.TSDF_EXTENT:
+            raise _lib.PingsHipError("tsdf_ops: a ray lies beyond 2**20 blocks from the origin and was left out; "
                                      "use a larger voxel_length or an origin near the scene")
 
     # ------------------------------------------------------------------ dense boxes and the mesh
@@ -316,6 +418,76 @@ def o3d_tsdf_fusion(self, frame_step=1, output_path=None, vox_size=0.02, trunc_d
     return mesh_ops.to_open3d(mesh)
 
 
-def install(slam_dataset_module) -> None:
-    """`import dataset.slam_dataset as D; install(D)`: SLAMDataset.o3d_tsdf_fusion -> the fusion above."""
+# ---------------------------------------------------------------------- SLAMDataset.lidar_tsdf_fusion
+def lidar_tsdf_fusion(self, voxel_size, sdf_trunc=None, space_carving=False, sdf_mode="point", frame_step=1,
+                      down_vox_m=None, use_gt_pose=False, output_path=None, color=False):
+    """The replay loop of `SLAMDataset.write_merged_point_cloud` (dataset/slam_dataset.py:1021-1101) with its
+    commented-out VDB-Fusion baseline switched on: per frame the loader, `intrinsic_correct` when
+    `kitti_correction_on`, the dataset's own `deskew_at_frame`, voxel down-sampling, the range and height crop, the
+    pose (gt / pgo / odom in the reference's order), then `TSDFVolume.integrate_points(points, pose[:3, 3])`.
+    `sdf_trunc` defaults to 4 voxels (2 sdf_trunc is then exactly the block edge); carving reaches `config.max_range`.
+    `color` fuses columns 3:6 of a 3-channel cloud.  The mesh is written to `output_path` as PLY and returned as
+    `o3d_tsdf_fusion` returns it.  No Open3D call."""
+    from . import lidar_ops, neural_map
+
+    cfg = self.config
+    dev = getattr(self, "device", None)
+    dev = torch.device(dev) if dev is not None and torch.device(dev).type == "cuda" else None
+    sdf_trunc = 4.0 * float(voxel_size) if sdf_trunc is None else float(sdf_trunc)
+    volume = TSDFVolume(voxel_size, sdf_trunc, color=bool(color), device=dev)
+    down_vox_m = cfg.vox_down_m if down_vox_m is None else down_vox_m
+    # what the crop lets through, with room for the fp32 rounding of the transform: the carving bound of every scan
+    reach = float(cfg.max_range)
+    if cfg.range_filter_2d:
+        reach = math.hypot(reach, max(abs(float(cfg.min_z)), abs(float(cfg.max_z))))
+    reach *= 1.001
+    for frame_id in range(0, self.total_pc_count, frame_step):
+        self.init_temp_data()
+        self.read_frame_with_loader(frame_id, False, False)
+        if self.cur_point_cloud_torch is None:
+            continue
+        if cfg.kitti_correction_on:
+            correct = getattr(lidar_ops._module_of(self), "intrinsic_correct", None) \
+                or lidar_ops._kept_original("intrinsic_correct")
+            self.cur_point_cloud_torch = correct(self.cur_point_cloud_torch, cfg.correction_deg)
+        if cfg.deskew:
+            if frame_id == 0:
+                continue                            # as the reference: the first frame has no motion to deskew with
+            self.deskew_at_frame(self.get_tran_in_frame(frame_id, use_gt_pose))
+        cloud = self.cur_point_cloud_torch.to(volume.device, torch.float32)
+        idx = neural_map.voxel_down_sample(cloud[:, :3], down_vox_m)
+        cloud, = lidar_ops.select_rows(idx, cloud)
+        keep = lidar_ops.crop_rows(cloud, cfg.min_z, cfg.max_z, cfg.min_range, cfg.max_range, cfg.range_filter_2d)
+        cloud, = lidar_ops.select_rows(keep, cloud)
+        if use_gt_pose and self.gt_pose_provided:
+            pose = self.gt_poses[frame_id]
+        elif cfg.pgo_on:
+            pose = self.pgo_poses[frame_id]
+        elif cfg.track_on:
+            pose = self.odom_poses[frame_id]
+        elif self.gt_pose_provided:
+            pose = self.gt_poses[frame_id]
+        else:
+            raise _lib.PingsHipError("lidar_tsdf_fusion: the dataset has no pose for the frame")
+        pose = torch.as_tensor(np.asarray(pose, dtype=np.float64), device=volume.device)
+        world = (cloud[:, :3].double() @ pose[:3, :3].T + pose[:3, 3]).float().contiguous()
+        cols = cloud[:, 3:6].contiguous() if color else None
+        volume.integrate_points(world, pose[:3, 3], cols, space_carving=space_carving, sdf_mode=sdf_mode,
+                                max_range=reach if space_carving else math.inf)
+    mesh = volume.extract_mesh()
+    if output_path is not None:
+        mesh_ops.write_ply(str(output_path), mesh.verts, mesh.faces, mesh.normals, mesh.colors)
+        print(f"Save the mesh resulting from LiDAR TSDF fusion to {output_path}")
+    try:
+        import open3d  # noqa: F401
+    except ImportError:
+        return mesh
+    return mesh_ops.to_open3d(mesh)
+
+
+def install(slam_dataset_module, lidar=False) -> None:
+    """`import dataset.slam_dataset as D; install(D)`: SLAMDataset.o3d_tsdf_fusion -> the fusion above.  With
+    `lidar=True` the class also gets `lidar_tsdf_fusion`, a method the reference does not have."""
     slam_dataset_module.SLAMDataset.o3d_tsdf_fusion = o3d_tsdf_fusion
+    if lidar:
+        slam_dataset_module.SLAMDataset.lidar_tsdf_fusion = lidar_tsdf_fusion
