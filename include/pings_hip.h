@@ -1113,6 +1113,33 @@ PINGS_API int pings_mesh_compact_vertices(const float* verts, int64_t V, const i
                                           void* scratch, float* verts_out, int64_t* faces_out, int64_t* remap,
                                           int64_t* kept, int64_t* n_out, void* stream);
 
+/* ------------------------------------------------------ mesh surface sampling (csrc/mesh_sample.hip)
+ * N points on the surface of a mesh (verts [V, 3] fp32, faces [F, 3] int64), in proportion to triangle area, with an
+ * optional box crop fused in: the cloud eval/eval_mesh_utils.py:eval_mesh scores.  Restated by tests/mesh_sample_ref.py;
+ * bit-equal to it and the same from run to run.  The call only enqueues on `stream`: no allocation, copy or wait.
+ *   area   A_t = 0.5 |(v1 - v0) x (v2 - v0)| in fp64.  With box != NULL (DEVICE double[6]: lo xyz, hi xyz) A_t = 0
+ *          unless lo <= v <= hi holds for all three vertices on every axis, both ends inclusive, compared in fp64
+ *          (Open3D's crop).  A corner index outside [0, V) gives A_t = 0 and PINGS_MESH_SAMPLE_INDEX in *status, a
+ *          non-finite vertex A_t = 0 and PINGS_MESH_SAMPLE_NONFINITE.
+ *   q_t    = llrint(A_t * 2^PINGS_MESH_SAMPLE_UNIT_BITS), an int64 count of quanta of 2^-32 m^2; Q_t its inclusive sum.
+ *          A triangle with A_t * 2^32 > floor(2^PINGS_MESH_SAMPLE_SUM_BITS / F) gets q_t = 0 and
+ *          PINGS_MESH_SAMPLE_AREA_CAP, so Q cannot overflow (4 M faces: 256 m^2 per triangle).
+ *   owner  point i in [0, N) belongs to the first t with llrint((double)Q_t * (double)N / (double)Q_{F-1}) > i.
+ *   point  z = splitmix64(seed + (i + 1) * 0x9E3779B97F4A7C15), u1 = (z >> 32) * 2^-32, u2 = (z & 0xffffffff) * 2^-32,
+ *          s = sqrt(u1), p = ((1 - s) * v0 + s * (1 - u2) * v1) + s * u2 * v2 in fp64, rounded to fp32 once.
+ * points [N, 3]; tri [N] (the owner, may be NULL); *count (DEVICE int64) = N, or 0 with Q_{F-1} == 0 (then nothing else
+ * is written); *status (DEVICE int32, zeroed by the caller) is OR-ed into.  The status bits leave PINGS_EVAL_EXTENT and
+ * PINGS_CAMFRONT_FULL free, so one word serves a whole evaluation.  V, F and N lie in [1, 2^31 - 1]. */
+#define PINGS_MESH_SAMPLE_UNIT_BITS 32
+#define PINGS_MESH_SAMPLE_SUM_BITS 62
+#define PINGS_MESH_SAMPLE_INDEX 16
+#define PINGS_MESH_SAMPLE_NONFINITE 32
+#define PINGS_MESH_SAMPLE_AREA_CAP 64
+PINGS_API size_t pings_mesh_sample_scratch_bytes(int64_t F);
+PINGS_API int pings_mesh_sample(const float* verts, int64_t V, const int64_t* faces, int64_t F, const double* box,
+                                int64_t N, int64_t seed, void* scratch, float* points, int32_t* tri, int64_t* count,
+                                int32_t* status, void* stream);
+
 /* ------------------------------------------------------ fused AdamW (csrc/optim.hip)
  * One optimiser step of every tensor of every parameter group in ONE launch.  A job is one fp32
  * tensor; its scalars are computed by the host in double and rounded to fp32 once, as torch's single-tensor AdamW

@@ -19,6 +19,8 @@ MC_ALLOW_DEGENERATE, MC_ASCENT = 1, 2                             # PINGS_MC_*: 
 ADAMW_MAX_JOBS, ADAMW_CHUNK = 48, 4096                            # PINGS_ADAMW_*: tensors per launch, elements per item
 EVAL_VIEW_RECORD, EVAL_PAIR_RECORD = 9, 12                        # PINGS_EVAL_*_RECORD: doubles per record
 EVAL_EXTENT = 1                                                   # PINGS_EVAL_EXTENT: status bit of the eval grids
+MESH_SAMPLE_UNIT_BITS, MESH_SAMPLE_SUM_BITS = 32, 62              # area quantum 2^-32 m^2; F * cap <= 2^62 quanta
+MESH_SAMPLE_INDEX, MESH_SAMPLE_NONFINITE, MESH_SAMPLE_AREA_CAP = 16, 32, 64   # status bits of pings_mesh_sample
 LOOP_MAX_R, LOOP_MAX_S, LOOP_MAX_D = 32, 128, 16                  # PINGS_LOOP_MAX_*: limits of the pings_loop_* entries
 LOOP_MAX_Q, LOOP_MAX_C = 16, 65536                                # poses / queries per call, candidates per search
 LIDAR_MAX_CAMS, LIDAR_MAX_LIDARS = 8, 8                           # PINGS_LIDAR_MAX_*: cameras per launch, other LiDARs
@@ -376,6 +378,9 @@ SIGNATURES = {
     "pings_mesh_vertex_normals": (i32, [vp, i64, vp, i64, vp, vp, vp]),
     "pings_mesh_compact_vertices_scratch_bytes": (sz, [i64, i64]),
     "pings_mesh_compact_vertices": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64), vp]),
+    # mesh surface sampling
+    "pings_mesh_sample_scratch_bytes": (sz, [i64]),
+    "pings_mesh_sample": (i32, [vp, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp]),
     # fused AdamW
     "pings_adamw_step": (i32, [C.POINTER(AdamwJob), i32, C.POINTER(i32), vp]),
     # view evaluation

@@ -7,7 +7,9 @@ loop of one KD-tree query per point.
   voxel_centroids    Open3D `voxel_down_sample`: the mean of each occupied cell, grid anchored at min - voxel/2
   nn_distance        exact nearest neighbour below `max_dist` through a sorted cell grid
   eval_pair          the reference's eleven Chamfer / F-score figures; the whole call reads one record
-  install(module)    rebinds `eval_pair` and `nn_correspondance` of eval/eval_mesh_utils.py
+  eval_mesh          box crop + surface sample of a mesh (mesh_ops.sample_surface), then eval_pair's body
+  crop_intersection  the ground-truth points near every predicted mesh's sampled surface; one host read
+  install(module)    rebinds `eval_pair` and `nn_correspondance` of eval/eval_mesh_utils.py, and the two above on request
 
 The raw operators take fp32 tensors on the HIP device and raise for anything else: there is no CPU fallback.  Counts
 that only a later stage needs stay on the device; every host read goes through `_read`, which notes it in
@@ -15,6 +17,7 @@ that only a later stage needs stay on the device; every host read goes through `
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import NamedTuple
 
 import numpy as np
@@ -307,8 +310,16 @@ def eval_pair(pred_points, trgt_points, down_sample_res=0.02, threshold=0.05, tr
         return pair_metrics([0.0] * 8, down_sample_res, threshold, truncation_acc, truncation_com)
     pred = _on_device(pred, trgt)
     trgt = _on_device(trgt, pred)
+    rec = _read(_pair_record(pred, pred_count, trgt, trgt_count, res, thr, tacc, tcom, _status(pred.device)),
+                "pair").tolist()
+    _raise_on_status(int(rec[10]))
+    return pair_metrics(rec, down_sample_res, threshold, truncation_acc, truncation_com)
+
+
+def _pair_record(pred, pred_count, trgt, trgt_count, res, thr, tacc, tcom, status) -> torch.Tensor:
+    """The device work of `eval_pair` on two non-empty device clouds: the float64 [EVAL_PAIR_RECORD] record, not read.
+    `status` (device int32 [1]) travels in it as entry 10, with whatever bits earlier stages OR-ed into it."""
     dev = pred.device
-    status = _status(dev)
     P, np_dev = _voxel(pred, pred_count, res, status)
     T, nt_dev = _voxel(trgt, trgt_count, res, status)
     # queries arrive in cell order (the centroids' order), so neighbouring lanes walk the same rows
@@ -319,9 +330,7 @@ def eval_pair(pred_points, trgt_points, down_sample_res=0.02, threshold=0.05, tr
     _lib.check(L.pings_eval_pair_reduce(_lib.ptr(dist_p), P.shape[0], _lib.ptr(np_dev), _lib.ptr(dist_r), T.shape[0],
                                         _lib.ptr(nt_dev), thr, tcom, _lib.ptr(status), _lib.ptr(rec),
                                         _lib.stream_ptr(dev)), "pings_eval_pair_reduce")
-    rec = _read(rec, "pair").tolist()
-    _raise_on_status(int(rec[10]))
-    return pair_metrics(rec, down_sample_res, threshold, truncation_acc, truncation_com)
+    return rec
 
 
 def nn_correspondance(verts1, verts2, truncation_dist, ignore_outlier=True):
@@ -346,7 +355,140 @@ def nn_correspondance(verts1, verts2, truncation_dist, ignore_outlier=True):
     return i.tolist(), np.where(far, trunc, d).tolist()
 
 
-def install(eval_mesh_utils_module) -> None:
-    """`import eval.eval_mesh_utils as E; install(E)`: E.eval_pair and E.nn_correspondance -> the device versions."""
+# ------------------------------------------------------------------ eval_mesh, crop_intersection (:8-60, :221-257)
+def _as_mesh(x, name: str):
+    """(verts fp32 [V, 3], faces int64 [F, 3]) on the device from a PLY path, a `mesh_ops.Mesh` or a (verts, faces) pair
+    of device tensors or host arrays; float64 coordinates are rounded once, on upload."""
+    from . import mesh_ops
+
+    if isinstance(x, (str, os.PathLike)):
+        ply = mesh_ops.read_ply(x)
+        x = (ply["verts"], ply["faces"])
+    elif isinstance(x, mesh_ops.Mesh):
+        x = (x.verts, x.faces)
+    if not (isinstance(x, (tuple, list)) and len(x) == 2):
+        raise TypeError(f"{name} must be a PLY path, a mesh_ops.Mesh or a (verts, faces) pair, got {type(x).__name__}")
+    v = _as_cloud(x[0], name + " vertices")
+    f = x[1]
+    if isinstance(f, torch.Tensor):
+        if not f.is_cuda:
+            raise _lib.PingsHipError(f"{name}: pings_amd.eval_ops runs on the HIP device only (got CPU faces); pass a "
+                                     "device tensor or a numpy array")
+        f = f.detach().to(torch.int64)
+    else:
+        f = np.ascontiguousarray(np.asarray(f).reshape(-1, 3), dtype=np.int64)
+    if f.ndim != 2 or f.shape[1] != 3:
+        raise ValueError(f"{name} faces must have shape [F, 3], got {list(f.shape)}")
+    return v, f
+
+
+def _as_target(x, name: str):
+    if isinstance(x, (str, os.PathLike)):
+        from . import mesh_ops
+        x = mesh_ops.read_ply(x)["verts"]
+    return _as_cloud(x, name)
+
+
+def _raise_on_sample_status(status: int) -> None:
+    from . import mesh_ops
+    msg = mesh_ops.sample_status_error(status)
+    if msg:
+        raise _lib.PingsHipError(msg)
+
+
+def eval_mesh(pred, trgt, down_sample_res=0.02, threshold=0.05, truncation_acc=0.50, truncation_com=0.50,
+              gt_bbx_mask_on=True, mesh_sample_point=20000000, possion_sample_on=True, possion_sample_init_factor=5,
+              *, seed=0) -> dict:
+    """The reference's `eval_mesh` (same signature, spelling included): the predicted mesh cropped to the target's
+    bounding box (z widened by `down_sample_res` at both ends, with `gt_bbx_mask_on`), `mesh_sample_point` points
+    sampled on its surface in proportion to triangle area, then `eval_pair` of that cloud against the target.
+    `pred`: a PLY path, a `mesh_ops.Mesh` or a (verts, faces) pair; `trgt`: a PLY path or any cloud `eval_pair` takes.
+    The box is formed on the device and the crop is fused into the sampler (`mesh_ops.sample_surface`), so the whole call
+    makes one host read: the pair record, which carries the sampler's status.  A mesh that leaves no sample gives what
+    `eval_pair` gives for an empty `pred`.
+    Poisson-disk elimination (Open3D's sequential priority-queue pass) is not built.  `possion_sample_on` is accepted
+    as long as `down_sample_res > 0`: the area-stratified sample serves it, since the voxel down-sampling at
+    `down_sample_res` that follows is what makes the scored cloud uniform; `possion_sample_init_factor` has no effect.
+    With `possion_sample_on=True` and `down_sample_res <= 0` the call raises NotImplementedError."""
+    from . import mesh_ops
+
+    if possion_sample_on and not float(down_sample_res) > 0.0:
+        raise NotImplementedError("eval_mesh: Poisson-disk sample elimination is not built; it is only stood in for by "
+                                  "the voxel down-sampling of down_sample_res > 0")
+    res, thr = _positive("down_sample_res", down_sample_res), _positive("threshold", threshold)
+    tacc, tcom = _positive("truncation_acc", truncation_acc), _positive("truncation_com", truncation_com)
+    n = int(mesh_sample_point)
+    if not 0 < n <= 2**31 - 1:
+        raise ValueError(f"mesh_sample_point must lie in [1, 2**31 - 1], got {n}")
+    verts, faces = _as_mesh(pred, "pred")
+    target = _as_target(trgt, "trgt")
+    empty = pair_metrics([0.0] * 8, down_sample_res, threshold, truncation_acc, truncation_com)
+    if verts.shape[0] == 0 or faces.shape[0] == 0 or target.shape[0] == 0:
+        return empty
+    like = next((t for t in (verts, faces, target) if isinstance(t, torch.Tensor)), None)
+    target = _on_device(target, like)
+    verts, faces = _on_device(verts, target), _on_device(faces, target)
+    box = None
+    if gt_bbx_mask_on:
+        box = torch.stack([target.amin(0), target.amax(0)]).double()       # exact: fp32 -> fp64
+        box[0, 2] -= res
+        box[1, 2] += res
+    status = _status(target.device)
+    sample = mesh_ops.sample_surface(verts, faces, n, seed=seed, box=box, status=status)
+    rec = _read(_pair_record(sample.points, sample.count, target, None, res, thr, tacc, tcom, status), "pair").tolist()
+    _raise_on_sample_status(int(rec[10]))
+    _raise_on_status(int(rec[10]))
+    if rec[8] == 0.0:                                                      # no live sample: the empty-pred answer
+        return empty
+    return pair_metrics(rec, down_sample_res, threshold, truncation_acc, truncation_com)
+
+
+def crop_intersection(gt, preds, out_file_crop=None, dist_thre=0.1, mesh_sample_point=1000000, *, seed=0):
+    """The reference's `crop_intersection`: the ground-truth points that lie closer than `dist_thre` (strictly, the
+    search's own rule) to the sampled surface of every predicted mesh in `preds`.  `gt`: a PLY path or a cloud; each
+    entry of `preds` as `eval_mesh` takes it.  Survival is chained on the device as one flag per ground-truth point (a
+    point already dropped is still queried, which changes no result), the flags are compacted once at the end, and the
+    samplers' status words travel with the count: one host read.  -> the kept [K, 3] device tensor in the order of
+    `gt`, also written to `out_file_crop` as a PLY cloud when that is given."""
+    from . import lidar_ops, mesh_ops
+
+    thre = _positive("dist_thre", dist_thre)
+    n = int(mesh_sample_point)
+    if not 0 < n <= 2**31 - 1:
+        raise ValueError(f"mesh_sample_point must lie in [1, 2**31 - 1], got {n}")
+    cloud = _as_target(gt, "gt")
+    meshes = [_as_mesh(p, f"preds[{k}]") for k, p in enumerate(preds)]
+    cloud = _on_device(cloud, next((v for v, _ in meshes if isinstance(v, torch.Tensor)), None))
+    dev = cloud.device
+    G = cloud.shape[0]
+    alive = torch.ones(G, dtype=torch.bool, device=dev)
+    status = _status(dev)
+    for verts, faces in meshes:
+        if G == 0:
+            break
+        if verts.shape[0] == 0 or faces.shape[0] == 0:
+            alive.zero_()                                   # nothing to be near to
+            continue
+        sample = mesh_ops.sample_surface(_on_device(verts, cloud), _on_device(faces, cloud), n, seed=seed,
+                                         status=status)
+        dist, _ = _nn(cloud, None, sample.points, sample.count, default_cell(thre), thre, status)
+        alive &= torch.isfinite(dist)
+    # kept rows first and in order, by a stable sort of the flags: their number is the call's one read
+    rows = torch.argsort(~alive, stable=True)
+    k, st = _read(torch.cat([alive.sum().reshape(1), status.to(torch.int64)]), "crop_intersection").tolist()
+    _raise_on_sample_status(st)
+    _raise_on_status(st)
+    kept, = lidar_ops.select_rows(rows[:k].contiguous(), cloud)
+    if out_file_crop is not None:
+        mesh_ops.write_ply(out_file_crop, kept, np.zeros((0, 3), dtype=np.int64))
+    return kept
+
+
+def install(eval_mesh_utils_module, mesh=False) -> None:
+    """`import eval.eval_mesh_utils as E; install(E)`: E.eval_pair and E.nn_correspondance -> the device versions; with
+    `mesh=True` also E.eval_mesh and E.crop_intersection."""
     eval_mesh_utils_module.eval_pair = eval_pair
     eval_mesh_utils_module.nn_correspondance = nn_correspondance
+    if mesh:
+        eval_mesh_utils_module.eval_mesh = eval_mesh
+        eval_mesh_utils_module.crop_intersection = crop_intersection

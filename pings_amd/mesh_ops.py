@@ -13,7 +13,7 @@ from typing import NamedTuple, Optional
 import numpy as np
 import torch
 
-from . import _lib
+from . import _abi, _lib
 
 
 class Mesh(NamedTuple):
@@ -277,6 +277,205 @@ def write_ply(path, verts, faces, normals=None, colors=None) -> None:
         fh.write(("\n".join(head) + "\n").encode("ascii"))
         fh.write(rec.tobytes())
         fh.write(tri.tobytes())
+
+
+_PLY_TYPES = {"char": "i1", "int8": "i1", "uchar": "u1", "uint8": "u1", "short": "i2", "int16": "i2", "ushort": "u2",
+              "uint16": "u2", "int": "i4", "int32": "i4", "uint": "u4", "uint32": "u4", "float": "f4", "float32": "f4",
+              "double": "f8", "float64": "f8"}
+
+
+def read_ply(path) -> dict:
+    """The inverse of `write_ply`, and a reader of what Open3D writes: `verts` float64 [V, 3], `faces` int64 [F, 3] (an
+    empty [0, 3] for a file without a face element: a cloud), and `normals` / `colors` float64 [V, 3] when the vertex
+    element has nx ny nz / red green blue (uchar colours are divided by 255, as Open3D reads them).  Host numpy only.
+    Formats `binary_little_endian` and `ascii`; any scalar vertex property is skipped by its declared size; faces are
+    `list uchar int|uint vertex_indices` (or `vertex_index`) of three indices.  Everything else (big-endian, another
+    element, a list property on vertices, a non-triangle face) raises ValueError naming the line."""
+    data = open(path, "rb").read()
+    end = data.find(b"end_header")
+    stop = data.find(b"\n", end) if end >= 0 else -1
+    if not data.startswith(b"ply") or stop < 0:
+        raise ValueError(f"{path}: line 1: not a PLY file (no 'ply' ... 'end_header' header)")
+    lines = data[:stop].decode("ascii", errors="replace").split("\n")
+    body = data[stop + 1:]
+    fmt, elements = None, []                      # elements: [name, count, [(property name, numpy type)], header line]
+    for ln, raw in enumerate(lines, 1):
+        tok = raw.split()
+        bad = lambda why: ValueError(f"{path}: line {ln}: {why}: {raw.strip()!r}")
+        if not tok or tok[0] in ("ply", "comment", "obj_info", "end_header"):
+            continue
+        if tok[0] == "format":
+            if len(tok) < 2 or tok[1] not in ("binary_little_endian", "ascii"):
+                raise bad("only binary_little_endian and ascii are read")
+            fmt = tok[1]
+        elif tok[0] == "element":
+            if len(tok) != 3 or tok[1] not in ("vertex", "face") or not tok[2].isdigit():
+                raise bad("only vertex and face elements are read")
+            if tok[1] in [e[0] for e in elements] or (tok[1] == "vertex" and elements):
+                raise bad("vertex comes first and each element once")
+            elements.append([tok[1], int(tok[2]), [], ln])
+        elif tok[0] == "property":
+            if not elements:
+                raise bad("a property before any element")
+            el = elements[-1]
+            if len(tok) >= 2 and tok[1] == "list":
+                if el[0] == "vertex":
+                    raise bad("list properties on vertices are not read")
+                if (len(tok) != 5 or tok[2] not in ("uchar", "uint8") or _PLY_TYPES.get(tok[3]) not in ("i4", "u4")
+                        or tok[4] not in ("vertex_indices", "vertex_index") or el[2]):
+                    raise bad("a face is one 'list uchar int|uint vertex_indices'")
+                el[2].append((tok[4], _PLY_TYPES[tok[3]]))
+            else:
+                if len(tok) != 3 or tok[1] not in _PLY_TYPES:
+                    raise bad("unknown property type")
+                if el[0] == "face":
+                    raise bad("a face is one 'list uchar int|uint vertex_indices'")
+                el[2].append((tok[2], _PLY_TYPES[tok[1]]))
+        else:
+            raise bad("unknown header line")
+    if fmt is None or not elements or elements[0][0] != "vertex":
+        raise ValueError(f"{path}: line {len(lines)}: the header has no format line or no vertex element")
+    _, V, vprops, vline = elements[0]
+    names = [n for n, _ in vprops]
+    if len(set(names)) != len(names) or not {"x", "y", "z"} <= set(names):
+        raise ValueError(f"{path}: line {vline}: the vertex element needs x, y and z, each property once")
+    F, ftype, fline = 0, "u4", None
+    if len(elements) > 1:
+        _, F, fprops, fline = elements[1]
+        if not fprops:
+            raise ValueError(f"{path}: line {fline}: the face element has no vertex_indices list")
+        ftype = fprops[0][1]
+    if fmt == "ascii":
+        rows = [r.split() for r in body.decode("ascii", errors="replace").split("\n")]
+        rows = [(len(lines) + 1 + k, r) for k, r in enumerate(rows) if r]
+        if len(rows) < V + F:
+            raise ValueError(f"{path}: line {len(lines) + 1}: {V + F} data lines expected, {len(rows)} found")
+        for ln, r in rows[:V]:
+            if len(r) != len(vprops):
+                raise ValueError(f"{path}: line {ln}: {len(vprops)} vertex values expected, {len(r)} found")
+        cols = np.array([r for _, r in rows[:V]], dtype=np.float64).reshape(V, len(vprops))
+        vert = {n: cols[:, k] for k, n in enumerate(names)}
+        for ln, r in rows[V:V + F]:
+            if r[0] != "3" or len(r) != 4:
+                raise ValueError(f"{path}: line {ln}: only triangles are read, got a face of {r[0]} indices")
+        faces = np.array([r[1:] for _, r in rows[V:V + F]], dtype=np.int64).reshape(F, 3)
+    else:
+        vdt = np.dtype([(n, "<" + t) for n, t in vprops])
+        fdt = np.dtype([("n", "u1"), ("i", "<" + ftype, (3,))])
+        if len(body) < V * vdt.itemsize:
+            raise ValueError(f"{path}: line {vline}: {V} vertices declared, the data holds fewer")
+        vert = np.frombuffer(body, dtype=vdt, count=V)
+        rest = body[V * vdt.itemsize:]
+        counts = np.frombuffer(rest, dtype=np.uint8)[:F * fdt.itemsize:fdt.itemsize]
+        if len(counts) and (counts != 3).any():       # the first face that is no triangle is where the stride breaks
+            k = int(np.flatnonzero(counts != 3)[0])
+            raise ValueError(f"{path}: line {fline}: only triangles are read, face {k} has {int(counts[k])} indices")
+        if len(rest) < F * fdt.itemsize:
+            raise ValueError(f"{path}: line {fline}: {F} faces declared, the data holds fewer")
+        faces = np.frombuffer(rest, dtype=fdt, count=F)["i"].astype(np.int64).reshape(F, 3)
+    col = lambda *keys: np.stack([np.asarray(vert[k], dtype=np.float64) for k in keys], 1).reshape(V, 3)
+    out = {"verts": col("x", "y", "z"), "faces": faces}
+    if {"nx", "ny", "nz"} <= set(names):
+        out["normals"] = col("nx", "ny", "nz")
+    if {"red", "green", "blue"} <= set(names):
+        c = col("red", "green", "blue")
+        out["colors"] = c / 255.0 if dict(vprops)["red"] == "u1" else c
+    return out
+
+
+# ------------------------------------------------------------------ surface sampling and box crop (DESIGN §2.8b)
+class SurfaceSample(NamedTuple):
+    points: torch.Tensor                  # [n, 3] fp32; rows are written only when count == n
+    tri: Optional[torch.Tensor]           # [n] int32, the owning triangle, with return_tri
+    count: torch.Tensor                   # device int64 [1]: n, or 0 when no triangle has area (then nothing is written)
+    status: torch.Tensor                  # device int32 [1]: MESH_SAMPLE_* bits OR-ed into it
+
+
+def _box_device(box, dev) -> Optional[torch.Tensor]:
+    """(lo, hi) -> a device fp64 [2, 3] tensor; a device tensor is taken as it is (no read), a host pair is uploaded."""
+    if box is None:
+        return None
+    if isinstance(box, torch.Tensor):
+        if not box.is_cuda:
+            raise _lib.PingsHipError("sample_surface: box as a tensor lives on the HIP device; pass a host (lo, hi) pair "
+                                     "otherwise")
+        if box.dtype != torch.float64 or tuple(box.shape) != (2, 3):
+            raise ValueError(f"box must be a float64 [2, 3] tensor, got {box.dtype} {list(box.shape)}")
+        return box.detach().contiguous()
+    lo, hi = box
+    b = np.stack([np.asarray(lo, dtype=np.float64).reshape(3), np.asarray(hi, dtype=np.float64).reshape(3)])
+    return torch.from_numpy(b).to(dev)
+
+
+def sample_status_error(status: int) -> Optional[str]:
+    """The text a caller raises with once it has read a sampler status, or None.  A non-finite vertex is no error: its
+    triangles own no samples, as `vertex_normals` gives them no weight."""
+    if status & _abi.MESH_SAMPLE_AREA_CAP:
+        return ("sample_surface: a triangle is larger than the area cap (2**62 quanta of 2**-32 m^2 shared among the "
+                "faces: 256 m^2 per triangle at 4 M faces); subdivide it or scale the mesh")
+    if status & _abi.MESH_SAMPLE_INDEX:
+        return "sample_surface: a face names a vertex outside [0, V)"
+    return None
+
+
+def sample_surface(verts, faces, n, *, seed=0, box=None, return_tri=False, status=None) -> SurfaceSample:
+    """`n` points on the surface, `round(cdf_t * n) - round(cdf_{t-1} * n)` of them on triangle t (the allocation of
+    Open3D's `sample_points_uniformly` as far as it is known), uniform inside each triangle by a
+    counter-based generator keyed on (seed, point index): bit-equal to tests/mesh_sample_ref.py and the same from run to
+    run.  `box` = (lo, hi), a host pair or a device fp64 [2, 3] tensor, drops every triangle with a vertex outside the
+    inclusive box before the allocation (Open3D's `crop`), with no compaction.  -> SurfaceSample(points, tri, count,
+    status); `status` (device int32 [1]) may be passed in to collect the bits of several calls.  No host read: whoever
+    reads `status` raises with `sample_status_error`."""
+    verts, faces = _check(verts, faces, "sample_surface")
+    n, seed = int(n), int(seed)
+    if not 0 <= n <= 2**31 - 1:
+        raise ValueError(f"sample_surface: n must lie in [0, 2**31 - 1], got {n}")
+    if not -2**63 <= seed < 2**64:
+        raise ValueError("sample_surface: the seed is a 64-bit integer")
+    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    if max(V, F) > 2**31 - 1:
+        raise _lib.PingsHipError("sample_surface: the mesh is too large for 32-bit indices")
+    bx = _box_device(box, dev)
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    points = torch.empty(n, 3, device=dev)
+    tri = torch.empty(n, dtype=torch.int32, device=dev) if return_tri else None
+    count = torch.zeros(1, dtype=torch.int64, device=dev)
+    if n == 0 or F == 0 or V == 0:
+        return SurfaceSample(points, tri, count, status)
+    L = _lib.lib()
+    scratch = _scratch(L.pings_mesh_sample_scratch_bytes(F), dev, "sample_surface")
+    seed = seed - 2**64 if seed >= 2**63 else seed          # the same 64 bits, as the signed word the ABI carries
+    _lib.check(L.pings_mesh_sample(_lib.ptr(verts), V, _lib.ptr(faces), F, _lib.ptr(bx), n, seed, _lib.ptr(scratch),
+                                   _lib.ptr(points), _lib.ptr(tri), _lib.ptr(count), _lib.ptr(status),
+                                   _lib.stream_ptr(dev)), "pings_mesh_sample")
+    return SurfaceSample(points, tri, count, status)
+
+
+def crop_box(verts, faces, lo, hi):
+    """Open3D's `TriangleMesh.crop(AxisAlignedBoundingBox(lo, hi))`: the vertices with lo <= v <= hi on every axis (both
+    ends inclusive, compared in fp64) renumbered in order, and the triangles whose three vertices are kept, in order.
+    A vertex inside the box that no kept face names stays, as in Open3D (`compact_vertices` drops those).  Torch
+    operators for the masks and gathers; -> (verts, faces).  One host read (both counts).  `eval_mesh` does not use
+    it: its sampler crops in place."""
+    verts, faces = _check(verts, faces, "crop_box")
+    dev, V = verts.device, verts.shape[0]
+    if V == 0:
+        _no_vertices(faces, "crop_box")
+        return verts, faces
+    b = _box_device((lo, hi), dev)
+    v64 = verts.double()
+    inside = ((v64 >= b[0]) & (v64 <= b[1])).all(1)
+    named = ((faces >= 0) & (faces < V)).all(1)
+    keep = inside[faces.clamp(0, V - 1)].all(1) & named
+    # kept rows first and in order, by a stable sort of the mask: no read until both counts travel together
+    vrows, frows = torch.argsort(~inside, stable=True), torch.argsort(~keep, stable=True)
+    _lib.note_sync("mesh_crop_box")
+    nv, nf = torch.stack([inside.sum(), keep.sum()]).cpu().tolist()
+    vrows = vrows[:nv]
+    remap = torch.full((V,), -1, dtype=torch.int64, device=dev)
+    remap[vrows] = torch.arange(nv, dtype=torch.int64, device=dev)
+    return verts.index_select(0, vrows), remap[faces.index_select(0, frows[:nf])]
 
 
 def to_open3d(mesh: Mesh):

@@ -149,6 +149,20 @@ def _image_losses(dev):
     print("smoke: image losses ok", {k: round(float(out[k]), 5) for k in ref})
 
 
+def _eval_mesh(dev):
+    """A two-triangle unit square scored against a grid 1 cm above it: the sampled surface covers every target point."""
+    from pings_amd import eval_ops
+
+    verts = torch.tensor([[0.0, 0, 0], [1, 0, 0], [0, 1, 0], [1, 1, 0]], device=dev)
+    faces = torch.tensor([[0, 1, 2], [1, 3, 2]], device=dev)
+    g = torch.linspace(0.0, 1.0, 51, device=dev)
+    x, y = torch.meshgrid(g, g, indexing="ij")
+    target = torch.stack([x, y, torch.full_like(x, 0.01)], -1).reshape(-1, 3)
+    m = eval_ops.eval_mesh((verts, faces), target, mesh_sample_point=50000)
+    assert m["Recall[Completeness](%)"] == 100.0 and abs(m["Chamfer_L1(m)"] - 0.01) < 2e-3, m
+    print("smoke: eval_mesh ok, Chamfer-L1", round(m["Chamfer_L1(m)"], 5))
+
+
 def run() -> None:
     dev = torch.device("cuda:0")
     _ssim(dev)
@@ -157,3 +171,4 @@ def run() -> None:
     _mlp(dev)
     _map(dev)
     _image_losses(dev)
+    _eval_mesh(dev)
