@@ -214,6 +214,12 @@ PINGS_API int pings_raster_debug_occlusion(const void* geom_blob, int P, int ima
  * `occ_nb` buckets per tile.  Non-decreasing in the rank, 0 for rank 0, below occ_nb. */
 PINGS_API int pings_raster_rank_bucket(const int32_t* ranks, int64_t n, int occ_nb, uint32_t nvalid,
                                        uint32_t* buckets);
+/* How the calling thread's last pings_raster_render built its tile lists (host values, no GPU work): *plan = 1 if it
+ * gathered them from the front depth ranks, 0 if it duplicated and sorted (or had no instance); *front = the front
+ * depth (1 + the last depth rank that keeps a tile) the thread's last pings_raster_preprocess read back, 0xFFFFFFFF
+ * if that frame cannot gather (footprint class 1 under the default rule, or PINGS_BIN=s) and nobody looked for it.  The
+ * environment knob PINGS_BIN=s|g forces the sort, or the gather wherever its tables fit. */
+PINGS_API int pings_raster_debug_bin_plan(int32_t* plan, uint32_t* front);
 /* Which (surfel record, 16x16 tile) pairs the wave-per-tile blend backward treats as interior, computed on the HOST by
  * the function the kernel calls (host pointers, no GPU work).  records [n][16]: the four float4 of a record as the
  * geometry blob holds them ({mx, my, opacity, pz} {conic x, y, z, rz} {r, g, b, q} {nx, ny, nz, -}); tile_origins

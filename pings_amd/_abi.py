@@ -235,6 +235,7 @@ SIGNATURES = {
     "pings_raster_debug_image": (i32, [vp, i32, i32, vp, vp, vp]),
     "pings_raster_debug_occlusion": (i32, [vp, i32, i32, i32, vp, vp, C.POINTER(C.c_int32), vp]),
     "pings_raster_rank_bucket": (i32, [vp, i64, i32, C.c_uint32, vp]),
+    "pings_raster_debug_bin_plan": (i32, [C.POINTER(i32), C.POINTER(C.c_uint32)]),
     "pings_raster_debug_interior": (i32, [vp, vp, i64, f32, f32, f32, f32, vp]),
     # 2D Gaussian splatting rasteriser
     "pings_raster2d_geom_bytes": (sz, [i32, i32, i32]),

@@ -42,8 +42,9 @@ constexpr int DS_KMIN = 2 * DS_SHARDS, DS_SHIFT = DS_KMIN + 1, DS_FLAG = DS_KMIN
 // The frame statistics (GeomState::stats), STAT_SHARDS words each so that thousands of waves do not add to one word:
 // [STAT_PAIRS + shard] (Gaussian, tile) pairs before occlusion culling and [STAT_VISIBLE + shard] Gaussians with a
 // tile, both from preprocess_kernel; [STAT_KEPT + shard] kept pairs from count_kept_kernel; word STAT_WORDS - 1 holds
-// occ_bmax.  The kept words come last, next to occ_bmax: a retry of the depth sort clears those two
-// (STAT_RETRY_WORDS from STAT_KEPT on) and keeps what the preprocess pass, which does not run again, left in the others.
+// occ_bmax in its low half and occ_front (the front depth F of the frame) in its high half.  The kept words come last,
+// next to that word: a retry of the depth sort clears those (STAT_RETRY_WORDS from STAT_KEPT on) and keeps what the
+// preprocess pass, which does not run again, left in the others.
 constexpr int STAT_SHARDS = 256;
 constexpr int STAT_PAIRS = 0, STAT_VISIBLE = STAT_SHARDS, STAT_KEPT = 2 * STAT_SHARDS;
 constexpr int STAT_BMAX = 3 * STAT_SHARDS, STAT_WORDS = STAT_BMAX + 1, STAT_RETRY_WORDS = STAT_WORDS - STAT_KEPT;
@@ -70,7 +71,8 @@ enum GradSlot {
 };
 
 struct FrameSummary {   // the record of a frame's one host read-back (frame_summary_kernel)
-  uint32_t overflow, pad0;
+  uint32_t overflow, front;      // depth-sort overflow flag; front depth F = 1 + the last depth rank that keeps a tile
+                                 // (FRONT_UNKNOWN where the frame cannot gather and nobody looked for it)
   unsigned long long stats[3];   // pairs before occlusion culling, visible Gaussians, kept pairs (= instances)
   int32_t aux[8];
   uint32_t seq;   // written last (system-scope release): the host polls it instead of blocking in the runtime
@@ -89,6 +91,8 @@ struct GeomState {
   uint32_t* nvalid;                         // [1] Gaussians that survived culling (= ranks with a real depth key)
   uint32_t* occ_bmax;                       // [1] largest occ_bsat over the tiles, occ_nb - 1 if one never saturates;
                                             //     behind `stats`, cleared with them
+  uint32_t* occ_front;                      // [1] front depth F: 1 + the largest depth rank that keeps a tile, 0 if none
+                                            //     does (count_kept_kernel); the other half of occ_bmax's 8-byte word
   uint32_t* ds_head;                        // depth sort: header (key range shards, range, overflow flag), then
   uint32_t *ds_cnt, *ds_fill, *ds_off;      //   [DS_NB + blocks] bucket / per-block culled counts, [DS_NB] fill cursors,
   char* zero_begin; size_t zero_bytes;      // occ_bucket .. stats .. ds_head: the frame's one memset
@@ -218,6 +222,8 @@ struct RasterKnobs {
   unsigned grad_fill_wgs = 512u; // PINGS_GRAD_FILL: fill workgroups behind the blend backward's tiles (0 = own launch)
   bool chain_sum_lanes = false;  // PINGS_CHAIN_SUM
   bool blend_interior = true;    // PINGS_BLEND_INTERIOR
+  enum Bin { BIN_AUTO, BIN_SORT, BIN_GATHER };
+  Bin bin = BIN_AUTO;            // PINGS_BIN
 };
 RasterKnobs read_knobs();
 
@@ -268,6 +274,30 @@ size_t tile_sort_library_bytes(int64_t n);
 template <typename KeyT>
 int tile_sort_library(const KeyT* keys_in, int64_t n, int bits, KeyT* keys_out, uint32_t* vals_out, void* temp,
                       size_t temp_bytes, hipStream_t st);
+
+// raster_gather.hip: the tile lists of a frame whose kept instances all lie in the first `front` depth ranks, gathered
+// per tile from those ranks instead of sorted: writes gval, ranges, point_list and the forward tile order word for word
+// as duplicate_kernel, the tile sort, tile_ranges_kernel and tile_order_kernel<true> do, and the zeros of per_gaussian.
+// gather_fits: whether its tables fit into the arrays of the binning blob that only the sort path uses (front entries
+// in slot_val, the row table in tile_key .. tile_key_sorted).  FRONT_MAX, the deepest front the plan takes: four
+// staging chunks of tile_gather_kernel, 3.5 times the headline's 2,304; a front entry carries its rank in 24 bits, so
+// the staging design would allow far more, but every workgroup of both passes reads the whole front (8 B a rank: 64 KB
+// at FRONT_MAX, 33 MB out of L2 per pass at 1080p), and at 1080p a front of FRONT_MAX is a cost ratio of about 37,
+// beyond GATHER_COST already: deeper fronts belong to the sort.
+constexpr uint32_t FRONT_MAX = 8192u;
+constexpr int GATHER_CHUNK = 2048;       // front entries a workgroup of tile_gather_kernel stages in LDS at a time
+// The default plan gathers while front * tiles <= GATHER_COST * instances: half the ratio at which the two plans
+// cost the same (profiles/r19/plan_sweep.json: the gather saves 30 - 33 us at ratios of 12 - 15, 23.5 us at 21.6 and
+// 11.9 us at 35.5, the last frame below FRONT_MAX; the least-squares line through them meets zero at 49.5).
+constexpr uint64_t GATHER_COST = 25u;
+constexpr uint32_t FRONT_UNKNOWN = 0xFFFFFFFFu;   // frame_summary_kernel did not look for the front depth: no plan gathers
+// nb: rank buckets per tile (a front entry holds the bucket in 8 bits)
+inline bool gather_fits(uint32_t front, int gx, int gy, int nb, int64_t I) {
+  return front >= 1u && front <= FRONT_MAX && gx <= 256 && gy <= 256 && nb <= 256 && (int64_t)front * gy <= 2 * I &&
+         2 * (int64_t)front <= I;
+}
+int launch_tile_gather(const KParams& kp, int P, int64_t I, uint32_t front, const GeomState& gs, const BinState& bs,
+                       void* per_gaussian, hipStream_t st);
 
 // raster_blend_fwd.hip: the blend half of pings_raster_render — the forward kernels of `plan`, then the per-Gaussian sums
 int launch_blend_fwd(int mode, const KParams& kp, const BlendPlan& plan, int P, int64_t I, const GeomState& gs,
@@ -340,6 +370,16 @@ __host__ __device__ inline uint32_t rank_bucket(int r, int nb, uint32_t nvalid) 
   const uint32_t b = front_buckets + (uint32_t)(((unsigned long long)(ur - front_ranks) * (unb - front_buckets)) /
                                                 (unsigned long long)(nvalid - front_ranks));
   return b < unb ? b : unb - 1u;
+}
+
+// bit i = tile s + i of the bucket whose mask row is `m` is kept, 0 <= i < w, 1 <= w <= 64 (GeomState::occ_mask; the row
+// walks of raster_fwd.hip and raster_gather.hip).  The second word may belong to the next bucket's row, or be the one
+// spare word behind the table: only bits of tiles below s + w survive the cut.
+__device__ inline unsigned long long kept_bits(const unsigned long long* __restrict__ m, int s, int w) {
+  const int i = s >> 6, sh = s & 63;
+  const unsigned long long lo = m[i], hi = m[i + 1];
+  const unsigned long long v = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
+  return v & (~0ull >> (64 - w));
 }
 
 // Two fp32 values in one VGPR pair: + - * on f2 compile to v_pk_add_f32 / v_pk_mul_f32, fma2 to v_pk_fma_f32.  Each

@@ -9,6 +9,8 @@
 //   radix sort (I)      STABLE sort by tile id only (ceil(log2(tiles)) bits): tile_sort.hip  [the only
 //                       multi-pass traffic over the instance list; 16-bit keys instead of 64-bit]
 //   tile_ranges_kernel  [start,end) of every tile in the sorted list
+//   (a frame whose kept instances all lie in a short front of depth ranks skips the three steps above and gathers its
+//   tile lists from those ranks: plan_gather below, raster_gather.hip)
 //   blend + sums        raster_blend_fwd.hip (launch_blend_fwd); blob layout, environment knobs and the
 //                       choice of blend kernels: raster_layout.hip
 //
@@ -358,14 +360,7 @@ __device__ inline RectLane rect_lane(int r, const uint32_t* __restrict__ gidx_so
 constexpr int SMALL_ITEMS = 16;   // up to this many items a lane walks its rectangle itself, four loads in flight
 constexpr uint32_t SMALL_KEPT = 16u;  // duplicate_kernel: up to this many kept tiles the lane also emits them itself
 
-// bit i = tile s + i of the bucket whose mask row is `m` is kept, 0 <= i < w <= 64.  The second word may belong to the
-// next bucket's row, or be the one spare word behind the table: only bits of tiles below s + w survive the cut.
-__device__ inline unsigned long long kept_bits(const unsigned long long* __restrict__ m, int s, int w) {
-  const int i = s >> 6, sh = s & 63;
-  const unsigned long long lo = m[i], hi = m[i + 1];
-  const unsigned long long v = sh ? (lo >> sh) | (hi << (64 - sh)) : lo;
-  return v & (~0ull >> (64 - w));
-}
+// kept_bits (a bit range of a bucket's mask row): raster_common.hpp
 
 struct RowItems {
   int s0, gx, wdt, cpr;   // first tile id of the rectangle, tiles per image row, rectangle width, items per row
@@ -933,13 +928,20 @@ __global__ __launch_bounds__(256) void tile_ranges_kernel(int64_t I, const KeyT*
 // One wave folds everything the host reads at the frame's one synchronisation into a 64-byte record: depth-sort
 // overflow flag, the three sharded statistics and up to 8 caller words (counts other kernels of the frame
 // left on the device: pings_raster_preprocess_dyn).
+constexpr int FRONT_SCAN_STEPS = 16;   // frame_summary_kernel: steps of 256 ranks it looks back for the last keeper
+enum { FRONT_NEVER = 0, FRONT_CLASS2 = 1, FRONT_ALWAYS = 2 };   // when frame_summary_kernel looks for the front depth
 struct AuxPtrs {
   const int32_t* p[8];
 };
 __global__ __launch_bounds__(64) void frame_summary_kernel(const uint32_t* __restrict__ overflow,
                                                            const unsigned long long* __restrict__ shards, AuxPtrs aux,
-                                                           int aux_words, FrameSummary* __restrict__ out, uint32_t seq) {
+                                                           int aux_words, FrameSummary* __restrict__ out, uint32_t seq,
+                                                           int nb, const uint32_t* __restrict__ nvalid,
+                                                           const uint32_t* __restrict__ bmax,
+                                                           const uint32_t* __restrict__ tiles_sorted,
+                                                           uint32_t* __restrict__ front, int front_mode) {
   __shared__ unsigned long long part[3][64];
+  __shared__ unsigned long long tot[3];
   const int lane = threadIdx.x;
   unsigned long long a0 = 0, a1 = 0, a2 = 0;
   for (int i = lane; i < STAT_SHARDS; i += 64) {
@@ -951,8 +953,56 @@ __global__ __launch_bounds__(64) void frame_summary_kernel(const uint32_t* __res
     unsigned long long t = 0;
     for (int i = 0; i < 64; ++i) t += part[lane][i];
     out->stats[lane] = t;
+    tot[lane] = t;
   }
+  __syncthreads();
   if (lane == 4) out->overflow = overflow ? *overflow : 0u;
+  // Only for a frame whose render may gather (front_mode FRONT_NEVER: PINGS_BIN=s; FRONT_CLASS2: the default rule, which
+  // gathers footprint class 2 alone — the host's own test on the same two sums; FRONT_ALWAYS: PINGS_BIN=g).  Every
+  // other frame (C2, C3: class 1) stores FRONT_UNKNOWN, which no plan accepts, and this wave, which the host is waiting
+  // for, does what it did before there was a front depth.
+  const bool want_front = front_mode == FRONT_ALWAYS || (front_mode == FRONT_CLASS2 && tot[1] > 0ull && tot[0] > 16ull * tot[1]);
+  if (!want_front) {
+    if (lane == 5) { out->front = FRONT_UNKNOWN; *front = FRONT_UNKNOWN; }
+  } else {
+    // The front depth of the frame: 1 + the last depth rank that keeps a tile.  No rank in a bucket behind occ_bmax
+    // keeps one, so the ranks of the buckets up to it bound the front (the bucket map is monotone: a search);
+    // from there the kept counts are read backwards, 256 ranks a step, until one is non-zero — the first step where
+    // tiles saturate, since the last needed bucket is a few hundred ranks wide.  After FRONT_SCAN_STEPS empty steps the
+    // bound itself stands: every use of the front depth (raster_gather.hip) only needs no keeper at or behind it.
+    const uint32_t nv = *nvalid, bm = *bmax;
+    // smallest rank whose bucket lies behind bm (nv if there is none), by a 64-ary search as in count_valid_kernel:
+    // ranks below lo have a bucket up to bm, ranks from hi on one behind it
+    uint32_t lo = 0u, hi = nv;
+    if (bm + 1u >= (uint32_t)nb) lo = nv;   // a tile never saturates: every bucket is needed, nothing to search
+    while (lo < hi) {
+      const uint32_t step = (hi - lo + 63u) / 64u;
+      const uint32_t pos = lo + (uint32_t)lane * step;
+      const bool le = pos < hi && rank_bucket((int)pos, nb, nv) <= bm;
+      const int nle = __popcll(__ballot(le));   // probes ascend and the map is monotone: these form a prefix
+      if (nle == 0) { hi = lo; break; }
+      const uint32_t last_le = lo + (uint32_t)(nle - 1) * step;
+      lo = last_le + 1u;
+      hi = min(hi, last_le + step);
+    }
+    uint32_t fr = lo;
+    for (int step = 0; step < FRONT_SCAN_STEPS && fr > 0u; ++step) {
+      const uint32_t base = fr > 256u ? fr - 256u : 0u;
+      uint32_t last = 0u;   // 1 + the last keeper among this lane's ranks base + lane, + 64, ..
+#pragma unroll
+      for (uint32_t u = 0u; u < 4u; ++u) {
+        const uint32_t r = base + 64u * u + (uint32_t)lane;
+        if (r < fr && tiles_sorted[r] != 0u) last = r + 1u;
+      }
+#pragma unroll
+      for (int o = 32; o > 0; o >>= 1) last = max(last, (uint32_t)__shfl_xor((int)last, o, 64));
+      if (last != 0u) { fr = last; break; }
+      if (base == 0u) { fr = 0u; break; }
+      if (step + 1 < FRONT_SCAN_STEPS) fr = base;
+      else fr = lo;
+    }
+    if (lane == 5) { out->front = fr; *front = fr; }
+  }
   if (lane >= 8 && lane < 16) out->aux[lane - 8] = (lane - 8 < aux_words && aux.p[lane - 8]) ? *aux.p[lane - 8] : 0;
   // `out` is pinned HOST memory: every field first, then the sequence number with system-scope release semantics
   __threadfence_system();
@@ -967,6 +1017,34 @@ static int make_params(const pings_raster_settings* s, int P, const RasterKnobs&
   kp.live = nullptr;
   kp.dyn_rows = 0;
   return PINGS_OK;
+}
+
+// What the thread's last geometry call read back, for the binning plan of the render call that follows it: the blob it
+// filled, the frame's size and its front depth.  A render of anything else (another blob, an older frame, another
+// thread's frame) finds no match and sorts.  Like every other field of the geometry blob the record assumes what the
+// two-call interface assumes anyway: nobody refills this blob between the geometry call and its render (a frame of
+// another thread written into it in between would hand either plan that frame's ranks, rectangles and offsets under
+// this frame's instance count).
+struct FrontRecord {
+  const void* geom = nullptr;
+  int P = 0, num_tiles = 0;
+  int64_t I = 0;
+  uint32_t front = 0;
+};
+static thread_local FrontRecord t_front;
+static thread_local int t_bin_plan = 0;   // what the thread's last render took: 0 = sort (or no instance), 1 = gather
+
+// Gather the tile lists from the front ranks?  The host value of the front depth only chooses the plan and sizes
+// grids and tables; the kernels read the device word.
+static bool plan_gather(const RasterKnobs& knobs, const void* geom_blob, int P, int64_t I, int footprint_class,
+                        const KParams& kp) {
+  const FrontRecord& fr = t_front;
+  const int num_tiles = kp.gx * kp.gy;
+  if (knobs.bin == RasterKnobs::BIN_SORT || I <= 0) return false;
+  if (fr.geom != geom_blob || fr.P != P || fr.I != I || fr.num_tiles != num_tiles) return false;
+  if (!gather_fits(fr.front, kp.gx, kp.gy, occlusion_buckets(num_tiles), I)) return false;
+  if (knobs.bin == RasterKnobs::BIN_GATHER) return true;
+  return footprint_class == 2 && (uint64_t)fr.front * (uint64_t)num_tiles <= GATHER_COST * (uint64_t)I;
 }
 
 static int tile_bits(int num_tiles) {
@@ -998,6 +1076,13 @@ PINGS_API int pings_raster_rank_bucket(const int32_t* ranks, int64_t n, int occ_
                                        uint32_t* buckets) {
   PINGS_ARG_CHECK(n >= 0 && occ_nb > 0 && (n == 0 || (ranks && buckets)), "null pointer / non-positive bucket count");
   for (int64_t i = 0; i < n; ++i) buckets[i] = rank_bucket(ranks[i], occ_nb, nvalid);
+  return PINGS_OK;
+}
+
+PINGS_API int pings_raster_debug_bin_plan(int32_t* plan, uint32_t* front) {
+  PINGS_ARG_CHECK(plan && front, "null pointer");
+  *plan = t_bin_plan;
+  *front = t_front.front;
   return PINGS_OK;
 }
 
@@ -1035,6 +1120,7 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
   PINGS_ARG_CHECK(num_instances != nullptr && footprint_class != nullptr, "null output");
   *num_instances = 0;
   *footprint_class = 1;
+  t_front = FrontRecord{};
   PINGS_ARG_CHECK(aux_words >= 0 && aux_words <= 8 && (aux_words == 0 || (aux_dev && aux_host)), "0..8 aux words");
   PINGS_ARG_CHECK(!live_rows_dev || (dyn_rows >= 0 && dyn_rows <= P), "dyn_rows must lie in 0..P");
   PINGS_ARG_CHECK(P > 0 || aux_words == 0, "aux words need a non-empty frame");
@@ -1140,7 +1226,8 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
     const uint32_t seq = ++frame_seq ? frame_seq : ++frame_seq;   // never 0
     hipLaunchKernelGGL(frame_summary_kernel, dim3(1), dim3(64), 0, st,
                        library_sort ? (const uint32_t*)nullptr : gs.ds_head + DS_FLAG, gs.stats, aux, aux_words,
-                       host_sum_dev, seq);
+                       host_sum_dev, seq, gs.occ_nb, gs.nvalid, gs.occ_bmax, gs.tiles_sorted, gs.occ_front,
+                       knobs.bin == RasterKnobs::BIN_SORT ? FRONT_NEVER : knobs.bin == RasterKnobs::BIN_GATHER ? FRONT_ALWAYS : FRONT_CLASS2);
     PINGS_LAUNCH_CHECK();
     {
       pings::prof::Scope ps("tile_count_scan", st);
@@ -1173,6 +1260,11 @@ PINGS_API int pings_raster_preprocess_dyn(const pings_raster_settings* s, int P,
   // wrapped, and its last entry is this number
   PINGS_ARG_CHECK(stats[2] < 0x7FFFFFFFull, "more than 2^31 - 1 (Gaussian, tile) instances in this frame");
   *num_instances = (int64_t)stats[2];
+  t_front.geom = geom_blob;
+  t_front.P = P;
+  t_front.num_tiles = num_tiles;
+  t_front.I = (int64_t)stats[2];
+  t_front.front = host_sum->front;
   // Class 2 = more than 16 (Gaussian, tile) pairs per visible Gaussian.  Footprints of many tiles reach nearly every
   // pixel of a tile: blend_plan gives such a view one wave per tile with four pixels per lane, forward and backward
   // (blend_fwd_tile_kernel, blend_bwd_tile_kernel), which amortises the per-record work.  Small footprints (class 1)
@@ -1209,7 +1301,12 @@ PINGS_API int pings_raster_render(const pings_raster_settings* s, int P, int64_t
                            : reinterpret_cast<const char*>(bs.ranges + num_tiles);
     PINGS_HIP_CHECK(hipMemsetAsync(bs.ranges, 0, pings::align_up((size_t)(z1 - z0)), st));
   }
-  if (I > 0) {
+  const bool gather = plan_gather(knobs, geom_blob, P, I, footprint_class, kp);
+  t_bin_plan = gather ? 1 : 0;
+  if (gather) {
+    // every kept instance lies in the first t_front.front depth ranks: each tile reads its list off those ranks
+    if (int e = launch_tile_gather(kp, P, I, t_front.front, gs, bs, per_gaussian, st)) return e;
+  } else if (I > 0) {
     // tile ids fit 16 bits for every image up to 4096x4096: a 2-byte key cuts the sort traffic by a quarter
     auto bin = [&](auto* key, auto* key_sorted) -> int {
       using KeyT = std::remove_pointer_t<decltype(key)>;
@@ -1246,7 +1343,7 @@ PINGS_API int pings_raster_render(const pings_raster_settings* s, int P, int64_t
                                      : bin(bs.tile_key, bs.tile_key_sorted);
     if (e) return e;
   }
-  {
+  if (!gather) {
     // forward dispatch order: tiles by descending list length
     pings::prof::Scope ps_o("tile_order", st);
     hipLaunchKernelGGL(tile_order_kernel<true>, dim3(1), dim3(1024), 0, st, (const uint32_t*)nullptr, bs.ranges, num_tiles,

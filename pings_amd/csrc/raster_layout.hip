@@ -58,6 +58,7 @@ GeomState carve_geom(void* blob, int P, int num_tiles) {
   // sharded pairs before culling, visible Gaussians, kept pairs, then one word: occ_bmax (STAT_*: raster_common.hpp)
   g.stats = c.take<unsigned long long>(STAT_WORDS);
   g.occ_bmax = g.stats ? reinterpret_cast<uint32_t*>(g.stats + STAT_BMAX) : nullptr;
+  g.occ_front = g.occ_bmax ? g.occ_bmax + 1 : nullptr;   // the other half of that word
   const size_t nblk = (n + 255) / 256;                  // workgroups of the per-Gaussian kernels
   g.ds_words = DS_HEAD + (size_t)DS_NB + nblk;          // header, counts (+ per-block culled)
   g.ds_head = c.take<uint32_t>(g.ds_words);
@@ -180,6 +181,10 @@ BwdState carve_bwd(void* blob, int P, int64_t I) {
 //   PINGS_BLEND_INTERIOR    1 | 0                     tests, A/B    the lean trip of blend_bwd_tile_kernel for surfel records interior to
 //                                                                   their tile (blend_interior); 0 = every record through the general trip;
 //                                                                   same bits
+//   PINGS_BIN               auto | s(ort) | g(ather)  tests, A/B    how pings_raster_render builds the tile lists: s = always duplicate and
+//                                                                   sort; g = gather from the front ranks (raster_gather.hip) whenever its
+//                                                                   tables fit (gather_fits), else sort; auto = gather only a class-2 frame
+//                                                                   with front * tiles <= GATHER_COST * instances; same bits
 RasterKnobs read_knobs() {
   RasterKnobs k;   // the defaults: raster_common.hpp
   if (const char* e = getenv("PINGS_BLEND_PPL")) k.blend_ppl = atoi(e);
@@ -214,6 +219,7 @@ RasterKnobs read_knobs() {
   if (const char* e = getenv("PINGS_GRAD_FILL")) k.grad_fill_wgs = e[0] == 'l' ? 0u : (unsigned)std::min(std::max(atoi(e), 1), 65535);
   if (const char* e = getenv("PINGS_CHAIN_SUM")) k.chain_sum_lanes = e[0] == 'l';
   if (const char* e = getenv("PINGS_BLEND_INTERIOR")) k.blend_interior = atoi(e) != 0;
+  if (const char* e = getenv("PINGS_BIN")) k.bin = e[0] == 's' ? RasterKnobs::BIN_SORT : e[0] == 'g' ? RasterKnobs::BIN_GATHER : RasterKnobs::BIN_AUTO;
   return k;
 }
 

@@ -1,11 +1,14 @@
 """What the per-Gaussian passes of the raster step have to visit: python tools/frame_counts.py [m1|c2|c3] [--out FILE]
 prints, for one forward + backward of the workload (default m1, the headline frame), the Gaussians that survive
-culling (nvalid), the depth ranks that keep a tile behind the occlusion bound, the ranks with a live gradient row, the
+culling (nvalid), the depth ranks that keep a tile behind the occlusion bound, the front depth F (1 + the last of those
+ranks; null where the frame cannot gather and the library does not look for it: set PINGS_BIN=g to see it) with the
+binning plan the render took by it (PINGS_BIN forces either), the ranks with a live gradient row, the
 (Gaussian, chunk) pairs of the row sums and the longest loop over chunk partials one rank runs.
 
 The chunk scan is read out of the backward blob: carve_bwd (raster_layout.hip) puts cidx[I + 2] first and pair_off[P + 1]
 behind it, each field on a 256-byte boundary."""
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -39,6 +42,10 @@ def frame_counts(which, dev):
     with torch.no_grad():
         fs, radii, contrib = hr._forward(prep, *[t.detach() for t in cloud])
         P, I = fs.P, fs.I
+        plan, front = C.c_int32(0), C.c_uint32(0)
+        if hasattr(L, "pings_raster_debug_bin_plan"):      # an older PINGS_HIP_LIB build always sorts
+            _lib.check(L.pings_raster_debug_bin_plan(C.byref(plan), C.byref(front)), "pings_raster_debug_bin_plan")
+        num_tiles = ((W + 15) // 16) * ((H + 15) // 16)
         gg = torch.Generator(device=dev).manual_seed(7)
         ups = [torch.randn(c, H, W, generator=gg, device=dev) for c in (3, 3, 1, 1)]
         f32 = dict(dtype=torch.float32, device=dev)
@@ -63,6 +70,10 @@ def frame_counts(which, dev):
             "workload": which, "gaussians": P, "width": W, "height": H, "footprint_class": fs.fclass, "instances": int(I),
             "nvalid": nvalid,
             "ranks_with_kept_tiles": int(torch.unique(owners).numel()),
+            # 0xFFFFFFFF: the frame cannot gather (footprint class 1, or PINGS_BIN=s) and nobody looked for its front
+            "front_depth": int(front.value) if front.value != 0xFFFFFFFF else None,
+            "front_tiles_per_instance": round(front.value * num_tiles / max(int(I), 1), 3) if front.value != 0xFFFFFFFF else None,
+            "binning_plan": "gather" if plan.value == 1 else "sort",
             "ranks_with_live_rows": int((chunks > 0).sum()),
             "live_rows": int(cidx[I]),
             "gaussian_chunk_pairs": int(pair_off[P]),
