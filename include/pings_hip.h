@@ -1059,6 +1059,34 @@ PINGS_API int pings_sdf_loss_backward(const pings_sdf_loss_args* a, void* stream
 /* Number of per-block partials the reduce writes (part holds 4 doubles each). */
 PINGS_API int pings_sdf_loss_partials(int64_t B, int64_t cap);
 
+/* ------------------------------------------------------ semantic loss block (csrc/sem_loss.hip)
+ * The mapper's semantic term over one SDF sample batch (utils/mapper.py:863-866, 929-946) with the selection on the
+ * device (pings_amd/semantic_losses.py).  Row b is labelled iff label[b] > 0 (>= 0 with the free-space flag) and
+ * label[b] < S; a label >= S is counted in counts[1] and never indexes memory.  r_b is the number of labelled rows in
+ * front of b; the row is selected iff it is labelled and r_b % d == 0, so n = ceil(M / d) rows of M labelled ones.
+ *   forward    selected[B]; loss[0] = -(1/n) sum_selected sum_j w[b,j] log_softmax(raw[b,j,:])[label[b]] (NaN when
+ *              n = 0); counts[2] = n, labels >= S (float64, exact integers).  fp64 sums in a fixed order.
+ *   backward   d_raw = gl[0] / n * w[b,j] * (softmax(raw[b,j,:]) - onehot(label[b])) on selected rows and exactly 0
+ *              on every other row, with the selected[] and scratch of the forward call on the same inputs.
+ * Limits: 1 <= S <= 32, 1 <= k <= 16, d >= 1; anything else is status 1.  Launch sizes depend on B, k, S and d only.
+ * flags: 1 weighted_first (raw is [B,S], k = 1, w unused), 2 free-space labels are labelled, 4 labels are int64. */
+typedef struct pings_sem_loss_args {
+  int64_t B;                     /* batch rows                                                                    */
+  int32_t k, S, d, flags;        /* neighbours, classes, sem_label_decimation                                     */
+  const float* raw;              /* [B,k,S] semantic decoder output, [B,S] when weighted_first                    */
+  const float* w;                /* [B,k] IDW weights, or NULL when weighted_first                                */
+  const void* label;             /* [B] int32, or int64 with flag 4                                               */
+  uint8_t* selected;             /* [B] 1 on the selected rows                                                    */
+  void* scratch;                 /* pings_sem_loss_scratch_bytes(B) bytes, 8-byte aligned                         */
+  float* loss;                   /* [1]                                                                           */
+  double* counts;                /* [2]                                                                           */
+  const float* gl;               /* [1] upstream gradient of the loss                                             */
+  float* d_raw;                  /* shape of raw                                                                  */
+} pings_sem_loss_args;
+PINGS_API size_t pings_sem_loss_scratch_bytes(int64_t B);   /* 0 for a bad B */
+PINGS_API int pings_sem_loss_forward(const pings_sem_loss_args* a, void* stream);
+PINGS_API int pings_sem_loss_backward(const pings_sem_loss_args* a, void* stream);
+
 /* ------------------------------------------------------ marching cubes (csrc/mc.hip)
  * The surface `v = level` of a C-contiguous [nx, ny, nz] fp32 volume (point (i, j, k) at (i*ny + j)*nz + k), by the
  * rules of DESIGN §2.7: cell (i, j, k) is processed iff mask[i, j, k] != 0 (mask NULL: every cell) and its 8 corners
@@ -1118,6 +1146,25 @@ PINGS_API size_t pings_mesh_compact_vertices_scratch_bytes(int64_t V, int64_t F)
 PINGS_API int pings_mesh_compact_vertices(const float* verts, int64_t V, const int64_t* faces, int64_t F,
                                           void* scratch, float* verts_out, int64_t* faces_out, int64_t* remap,
                                           int64_t* kept, int64_t* n_out, void* stream);
+
+/* ------------------------------------------------------ labelled meshes (csrc/mesh_label.hip)
+ * What Mesher.estimate_vertices_sem (utils/mesher.py:393-412) does with its colour dict and Open3D.
+ *   label_colors     colors[v] = table[labels[v]] / 255 (fp32, table uint8 [T, 3]), drop[v] = labels[v] <= 0.  A label
+ *                    outside [0, T), or one with valid[label] == 0, gets colour 0, never indexes the table, and adds one
+ *                    to *bad (DEVICE int32, zeroed by the caller; an integer atomic).  No host read.
+ *   remove_vertices  remove_vertices_by_mask: the vertices with drop[v] != 0 go and every face naming one goes; kept
+ *                    vertices and kept faces keep their order, faces are remapped.  verts_out [V, 3], kept [V] (the old
+ *                    index of every new vertex) and faces_out [F, 3] are filled up to the counts; remap [V] is -1 for a
+ *                    dropped vertex.  totals[3] (HOST, the one read): kept vertices, kept faces, *bad (0 with bad NULL).
+ *                    A face corner outside [0, V) never indexes memory: status 1 after the read.
+ * V and 3F stay below 2^31; scratch of `_scratch_bytes` (0 for a bad shape); no output aliases an input. */
+PINGS_API int pings_mesh_label_colors(const int64_t* labels, int64_t V, const uint8_t* table, const uint8_t* valid,
+                                      int64_t T, float* colors, uint8_t* drop, int32_t* bad, void* stream);
+PINGS_API size_t pings_mesh_remove_vertices_scratch_bytes(int64_t V, int64_t F);
+PINGS_API int pings_mesh_remove_vertices(const float* verts, int64_t V, const int64_t* faces, int64_t F,
+                                         const uint8_t* drop, const int32_t* bad, void* scratch, float* verts_out,
+                                         int64_t* faces_out, int64_t* remap, int64_t* kept, int64_t* totals,
+                                         void* stream);
 
 /* ------------------------------------------------------ mesh surface sampling (csrc/mesh_sample.hip)
  * N points on the surface of a mesh (verts [V, 3] fp32, faces [F, 3] int64), in proportion to triangle area, with an

@@ -145,6 +145,11 @@ class SdfLossArgs(C.Structure):
                                   "part", "sdf_pred", "losses", "counts", "gl", "g_pred", "d_s", "d_g", "d_c")]
 
 
+class SemLossArgs(C.Structure):
+    _fields_ = [("B", C.c_int64), ("k", C.c_int32), ("S", C.c_int32), ("d", C.c_int32), ("flags", C.c_int32)] + \
+               [(n, vp) for n in ("raw", "w", "label", "selected", "scratch", "loss", "counts", "gl", "d_raw")]
+
+
 class AdamwJob(C.Structure):
     _fields_ = [("p", vp), ("g", vp), ("m", vp), ("v", vp), ("n", C.c_int64)] + \
                [(n, C.c_float) for n in ("decay", "beta1", "beta2", "one_minus_beta1", "one_minus_beta2", "step_size",
@@ -364,6 +369,10 @@ SIGNATURES = {
     "pings_sdf_loss_reduce": (i32, [C.POINTER(SdfLossArgs), vp]),
     "pings_sdf_loss_backward": (i32, [C.POINTER(SdfLossArgs), vp]),
     "pings_sdf_loss_partials": (i32, [i64, i64]),
+    # semantic loss block
+    "pings_sem_loss_scratch_bytes": (sz, [i64]),
+    "pings_sem_loss_forward": (i32, [C.POINTER(SemLossArgs), vp]),
+    "pings_sem_loss_backward": (i32, [C.POINTER(SemLossArgs), vp]),
     # marching cubes
     "pings_mc_scratch_bytes": (sz, [i64, i64, i64]),
     "pings_mc_count": (i32, [vp, vp, i64, i64, i64, f32, i32, vp, C.POINTER(i64), vp]),
@@ -379,6 +388,10 @@ SIGNATURES = {
     "pings_mesh_vertex_normals": (i32, [vp, i64, vp, i64, vp, vp, vp]),
     "pings_mesh_compact_vertices_scratch_bytes": (sz, [i64, i64]),
     "pings_mesh_compact_vertices": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, C.POINTER(i64), vp]),
+    # labelled meshes
+    "pings_mesh_label_colors": (i32, [vp, i64, vp, vp, i64, vp, vp, vp, vp]),
+    "pings_mesh_remove_vertices_scratch_bytes": (sz, [i64, i64]),
+    "pings_mesh_remove_vertices": (i32, [vp, i64, vp, i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(i64), vp]),
     # mesh surface sampling
     "pings_mesh_sample_scratch_bytes": (sz, [i64]),
     "pings_mesh_sample": (i32, [vp, i64, vp, i64, vp, i64, i64, vp, vp, vp, vp, vp, vp]),

@@ -1,7 +1,9 @@
 """Mesh finishing on the HIP device: what `Mesher.recon_aabb_collections_mesh` (utils/mesher.py:480-530, :583-636) does
 with Open3D after marching cubes — concatenate the chunks, `remove_duplicated_vertices`, drop the connected clusters
 below `config.min_cluster_vertices` triangles, `compute_vertex_normals`, `global_transform`, write the `.ply` — without
-Open3D.  Kernels: csrc/mesh.hip; rules: DESIGN §2.7b, restated in numpy by tests/mesh_ref.py.
+Open3D.  Kernels: csrc/mesh.hip; rules: DESIGN §2.7b, restated in numpy by tests/mesh_ref.py.  The semantic branch
+(`estimate_sem`: colours by label, free-space vertices removed) is `label_colors` / `remove_vertices`
+(csrc/mesh_label.hip).
 
 Every primitive takes and returns device tensors (verts fp32 [V, 3], faces int64 [F, 3]); a CPU tensor raises
 `PingsHipError`.  Empty inputs give empty outputs with no launch.  Host reads are recorded with `_lib.note_sync`."""
@@ -170,6 +172,79 @@ def compact_vertices(verts, faces, *attrs):
     return (vout[:n.value], fout, *(None if a is None else a.index_select(0, kept) for a in attrs))
 
 
+def label_colors(labels, table, valid, status=None):
+    """Vertex colours by label (mesher.py:402-409, csrc/mesh_label.hip): `labels` int64 [V], `table` uint8 [T, 3] and
+    `valid` bool [T] on the device -> (colors [V, 3] fp32 = table[label] / 255, drop [V] bool = label <= 0, the
+    reference's `non_freespace_idx`).  A label outside the table, or one whose `valid` is false, gets colour 0 and is
+    counted on the device: no host read here; `remove_vertices(..., drop)` reads the count with its own and raises
+    ValueError where the reference's dict lookup raises KeyError.  `status` (device int32 [1]) may be passed in to
+    collect the count of several calls."""
+    for t in (labels, table, valid):
+        if not t.is_cuda:
+            raise _lib.PingsHipError("label_colors runs on the HIP device only (got a CPU tensor); there is no CPU "
+                                     "fallback")
+    if labels.dim() != 1 or labels.dtype != torch.int64:
+        raise ValueError(f"label_colors: labels must be int64 [V], got {labels.dtype} {tuple(labels.shape)}")
+    if table.dim() != 2 or table.shape[1] != 3 or table.dtype != torch.uint8 or table.shape[0] == 0:
+        raise ValueError(f"label_colors: table must be uint8 [T, 3], got {table.dtype} {tuple(table.shape)}")
+    if valid.dtype != torch.bool or tuple(valid.shape) != (table.shape[0],):
+        raise ValueError(f"label_colors: valid must be bool [{table.shape[0]}], got {valid.dtype} {tuple(valid.shape)}")
+    dev, V = labels.device, labels.shape[0]
+    if status is None:
+        status = torch.zeros(1, dtype=torch.int32, device=dev)
+    colors = torch.empty(V, 3, device=dev)
+    drop = torch.empty(V, dtype=torch.bool, device=dev)
+    drop._pings_bad_labels = status            # travels to the host with the counts of remove_vertices
+    if V:
+        _lib.check(_lib.lib().pings_mesh_label_colors(_lib.ptr(labels.contiguous()), V, _lib.ptr(table.contiguous()),
+                                                      _lib.ptr(valid.contiguous()), table.shape[0], _lib.ptr(colors),
+                                                      _lib.ptr(drop), _lib.ptr(status), _lib.stream_ptr(dev)),
+                   "pings_mesh_label_colors")
+    return colors, drop
+
+
+_label_colors = label_colors        # recon_mesh has a keyword of the same name
+
+
+def _bad_labels_error(n) -> ValueError:
+    return ValueError(f"label_colors: {n} vertex label(s) have no entry in the colour table")
+
+
+def remove_vertices(verts, faces, drop, *attrs):
+    """Open3D's `remove_vertices_by_mask`: the vertices with `drop` (bool [V], device) go and every face naming one
+    goes; kept vertices and kept faces keep their order, indices are remapped, per-vertex `attrs` ([V, ...] device
+    tensors, None passed through) follow.  -> (verts, faces, *attrs).  One host read: both counts in one record, and
+    with them the bad-label count of the `label_colors` call that made `drop`, which raises ValueError."""
+    verts, faces = _check(verts, faces, "remove_vertices")
+    dev, V, F = verts.device, verts.shape[0], faces.shape[0]
+    if not torch.is_tensor(drop) or not drop.is_cuda or drop.dtype != torch.bool or tuple(drop.shape) != (V,):
+        raise ValueError(f"remove_vertices: drop must be a device bool [{V}] tensor")
+    for a in attrs:
+        if a is not None and (not a.is_cuda or a.shape[0] != V):
+            raise ValueError("remove_vertices: every attribute is a device tensor with one row per vertex")
+    if V == 0:
+        _no_vertices(faces, "remove_vertices")
+        return (verts, faces, *attrs)
+    bad = getattr(drop, "_pings_bad_labels", None)
+    L = _lib.lib()
+    scratch = _scratch(L.pings_mesh_remove_vertices_scratch_bytes(V, F), dev, "remove_vertices")
+    vout = torch.empty(V, 3, device=dev)
+    fout = torch.empty(F, 3, dtype=torch.int64, device=dev)
+    remap = torch.empty(V, dtype=torch.int64, device=dev)
+    kept = torch.empty(V, dtype=torch.int64, device=dev)
+    tot = (C.c_int64 * 3)(0, 0, 0)
+    _lib.note_sync("mesh_remove_vertices")
+    _lib.check(L.pings_mesh_remove_vertices(_lib.ptr(verts), V, _lib.ptr(faces) if F else None, F,
+                                            _lib.ptr(drop.contiguous()), _lib.ptr(bad), _lib.ptr(scratch),
+                                            _lib.ptr(vout), _lib.ptr(fout) if F else None, _lib.ptr(remap),
+                                            _lib.ptr(kept), tot, _lib.stream_ptr(dev)), "pings_mesh_remove_vertices")
+    if tot[2]:
+        raise _bad_labels_error(int(tot[2]))
+    kept = kept[:int(tot[0])]
+    return (vout[:int(tot[0])], fout[:int(tot[1])],
+            *(None if a is None else a.index_select(0, kept) for a in attrs))
+
+
 def finish_mesh(parts, min_tri=0, normals=True, colors=None, transform=None, compact=False) -> Mesh:
     """The reference's order (mesher.py:500-523): concatenate `parts` (a list of device (verts, faces) pairs) with face
     offsets, weld, drop the clusters below `min_tri` faces when `min_tri > 0`, (with `compact`, an extension, drop the
@@ -212,28 +287,54 @@ def finish_mesh(parts, min_tri=0, normals=True, colors=None, transform=None, com
 
 
 def recon_mesh(mesher, aabbs, voxel_size, query_locally=False, estimate_color=False, mesh_normal=True,
-               filter_isolated_mesh=False, mesh_min_nn=10, mesh_path=None):
+               filter_isolated_mesh=False, mesh_min_nn=10, mesh_path=None, estimate_sem=False,
+               filter_free_space_vertices=True, label_colors=None):
     """`Mesher.recon_aabb_collections_mesh` without Open3D: `mesher_ops.mesh_bbx` per box (chunks past the point cap
     are skipped), vertex colours per chunk before the weld with `estimate_color`, `finish_mesh` with
     config.min_cluster_vertices and the mesher's global_transform (skipped when it is the identity), `write_ply` when
-    `mesh_path` is given.  The semantic branch (`estimate_sem`) is not offered.  -> Mesh, or None without boxes."""
+    `mesh_path` is given.  With `estimate_sem` (mesher.py:599-603, `estimate_vertices_sem`) each chunk's vertices are
+    labelled by the semantic decoder and coloured by `label_colors` = (table uint8 [T, 3], valid bool [T]) on the
+    device, the vertices with a label <= 0 and their faces are removed when `filter_free_space_vertices`, and
+    `estimate_color` is ignored, as the reference's `else` does.  -> Mesh, or None without boxes."""
     from . import mesher_ops as MO
 
     if aabbs is None:
         return None
     cfg = mesher.config
+    status = None
+    if estimate_sem:
+        if label_colors is None:
+            raise ValueError("recon_mesh: estimate_sem needs label_colors = (table uint8 [T, 3], valid bool [T])")
+        if getattr(mesher, "sem_mlp", None) is None:
+            raise ValueError("recon_mesh: estimate_sem needs a semantic decoder (mesher.sem_mlp)")
+        table, valid = label_colors
+        estimate_color = False
     parts, cols = [], []
     for bbx in aabbs:
         bmin, bmax = (bbx.get_min_bound(), bbx.get_max_bound()) if hasattr(bbx, "get_min_bound") else bbx
         chunk = MO.mesh_bbx(mesher, bmin, bmax, voxel_size, query_locally, mesh_min_nn)
         if chunk is None:
             continue
+        if estimate_sem:
+            v, f = chunk
+            if status is None:
+                status = torch.zeros(1, dtype=torch.int32, device=v.device)
+            c, drop = _label_colors(MO.label_vertices(mesher, v, query_locally), table, valid, status)
+            if filter_free_space_vertices:
+                v, f, c = remove_vertices(v, f, drop, c)
+            chunk = (v, f)
+            cols.append(c)
         parts.append(chunk)
         if estimate_color:
             _, _, c, _ = MO._query_device(mesher, chunk[0], cfg.infer_bs, False, False, True, False, query_locally)
             if getattr(cfg, "color_channel", 3) == 1:
                 c = (c * 2.0).repeat(1, 3)       # mesher.py estimate_vertices_color: np.repeat(color_pred * 2.0, 3, axis=1)
             cols.append(c)
+    if status is not None and not filter_free_space_vertices:
+        _lib.note_sync("mesh_label_status")      # no remove_vertices call carried the count to the host
+        n_bad = int(status.cpu())
+        if n_bad:
+            raise _bad_labels_error(n_bad)
     T = np.asarray(getattr(mesher, "global_transform", np.eye(4)), dtype=np.float64)
     mesh = finish_mesh(parts, min_tri=cfg.min_cluster_vertices if filter_isolated_mesh else 0, normals=mesh_normal,
                        colors=torch.cat(cols) if cols else None,

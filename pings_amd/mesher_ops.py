@@ -216,42 +216,97 @@ def mesh_bbx(self, bbx_min, bbx_max, voxel_size, query_locally=False, mesh_min_n
     return torch.tensor(origin, dtype=torch.float32, device=coord.device) + verts * voxel_size, faces
 
 
+def label_vertices(self, verts, query_locally=False):
+    """Semantic labels of mesh vertices (`estimate_vertices_sem`, mesher.py:398-401): the batch loop of `query_points`
+    with `query_sem` alone, -> int64 [V] on the device."""
+    if getattr(self, "sem_mlp", None) is None:
+        raise ValueError("label_vertices: the mesher has no semantic decoder (sem_mlp)")
+    _, sem, _, _ = _query_device(self, verts, self.config.infer_bs, False, True, False, False, query_locally)
+    return sem.to(torch.int64)
+
+
+def color_table(color_map, device=None):
+    """(table uint8 [T, 3], valid bool [T]) of a {label: (r, g, b)} dict such as the reference's
+    `sem_kitti_color_map`, T = the largest label + 1: the `label_colors` argument of `mesh_ops.recon_mesh`."""
+    keys = [int(k) for k in color_map]
+    if not keys or min(keys) < 0:
+        raise ValueError("color_table: the colour map needs at least one entry and no negative label")
+    table = np.zeros((max(keys) + 1, 3), dtype=np.uint8)
+    valid = np.zeros(max(keys) + 1, dtype=bool)
+    for k, rgb in color_map.items():
+        rgb = np.asarray(rgb)
+        if rgb.shape != (3,) or (rgb < 0).any() or (rgb > 255).any() or (rgb != np.floor(rgb)).any():
+            raise ValueError(f"color_table: label {k} needs three integers in 0..255, got {rgb!r}")
+        table[int(k)], valid[int(k)] = rgb, True
+    return torch.from_numpy(table).to(device), torch.from_numpy(valid).to(device)
+
+
 def recon_mesh(self, aabbs, voxel_size, **kw):
-    """`Mesher.recon_mesh`: `mesh_ops.recon_mesh`, the finished mesh as device tensors."""
+    """`Mesher.recon_mesh`: `mesh_ops.recon_mesh`, the finished mesh as device tensors.  After
+    `install(..., semantic=True)` a call with `estimate_sem` gets the installed colour table unless it passes one."""
     from . import mesh_ops
 
+    if aabbs is None:
+        return None
+    if kw.get("estimate_sem") and kw.get("label_colors") is None:
+        kw["label_colors"] = _installed_table(self)
     return mesh_ops.recon_mesh(self, aabbs, voxel_size, **kw)
 
 
-def _finished(original):
+def _installed_table(self):
+    """The colour table `install(..., semantic=True)` read, on the mesher's device (uploaded once per device)."""
+    host = getattr(type(self), "_pings_label_colors", None)
+    if host is None:
+        raise ValueError("estimate_sem needs a colour table: install(mesher_module, finish=True, semantic=True), or "
+                         "pass label_colors")
+    dev = _device(self)
+    cache = type(self)._pings_label_colors_device
+    if dev not in cache:
+        cache[dev] = tuple(t.to(dev) for t in host)
+    return cache[dev]
+
+
+def _finished(original, semantic=False):
     def recon_aabb_collections_mesh(self, aabbs, voxel_size, mesh_path=None, query_locally=False, estimate_sem=False,
                                     estimate_color=False, mesh_normal=True, filter_isolated_mesh=False,
                                     filter_free_space_vertices=True, mesh_min_nn=10, use_torch_mc=False):
         from . import mesh_ops
 
-        if estimate_sem:         # colours by label and deletes free-space vertices: stays the reference's
+        if estimate_sem and not semantic:     # not asked for: the labelled mesh stays the reference's
             return original(self, aabbs, voxel_size, mesh_path, query_locally, estimate_sem, estimate_color, mesh_normal,
                             filter_isolated_mesh, filter_free_space_vertices, mesh_min_nn, use_torch_mc)
-        mesh = mesh_ops.recon_mesh(self, aabbs, voxel_size, query_locally=query_locally, estimate_color=estimate_color,
-                                   mesh_normal=mesh_normal, filter_isolated_mesh=filter_isolated_mesh,
-                                   mesh_min_nn=mesh_min_nn, mesh_path=mesh_path)
+        mesh = recon_mesh(self, aabbs, voxel_size, query_locally=query_locally, estimate_color=estimate_color,
+                          mesh_normal=mesh_normal, filter_isolated_mesh=filter_isolated_mesh, mesh_min_nn=mesh_min_nn,
+                          mesh_path=mesh_path, estimate_sem=estimate_sem,
+                          filter_free_space_vertices=filter_free_space_vertices)
         return None if mesh is None else mesh_ops.to_open3d(mesh)
 
     recon_aabb_collections_mesh._pings_original = original
     return recon_aabb_collections_mesh
 
 
-def install(mesher_module, mc: bool = False, finish: bool = False) -> None:
+def install(mesher_module, mc: bool = False, finish: bool = False, semantic: bool = False) -> None:
     """`import utils.mesher as M; install(M)`: Mesher.query_points -> one fused kernel launch per batch.  With mc=True
     also Mesher.mc_mesh and Mesher.mc_mesh_torch -> marching cubes on the device (csrc/mc.hip).  With finish=True also
     Mesher.recon_aabb_collections_mesh -> `mesh_ops.recon_mesh` (csrc/mesh.hip) returned through `mesh_ops.to_open3d`
-    (the saved original with `estimate_sem`), and a new Mesher.recon_mesh for callers that want the device tensors."""
+    (the saved original with `estimate_sem`), and a new Mesher.recon_mesh for callers that want the device tensors.
+    With finish=True and semantic=True a call with `estimate_sem` takes that route too (csrc/mesh_label.hip): the colour
+    table is built here, once, from `mesher_module.sem_kitti_color_map`, the dict the reference's module imports."""
+    if semantic and not finish:
+        raise ValueError("install: semantic=True routes recon_aabb_collections_mesh(estimate_sem=True) and needs "
+                         "finish=True")
     mesher_module.Mesher.query_points = query_points
     if mc:
         mesher_module.Mesher.mc_mesh = mc_mesh
         mesher_module.Mesher.mc_mesh_torch = mc_mesh_torch
     if finish:
+        if semantic:
+            color_map = getattr(mesher_module, "sem_kitti_color_map", None)
+            if not isinstance(color_map, dict):
+                raise ValueError("install: semantic=True needs the module's sem_kitti_color_map dict")
+            mesher_module.Mesher._pings_label_colors = color_table(color_map)
+            mesher_module.Mesher._pings_label_colors_device = {}
         current = getattr(mesher_module.Mesher, "recon_aabb_collections_mesh", None)
         original = getattr(current, "_pings_original", current)
-        mesher_module.Mesher.recon_aabb_collections_mesh = _finished(original)
+        mesher_module.Mesher.recon_aabb_collections_mesh = _finished(original, semantic)
         mesher_module.Mesher.recon_mesh = recon_mesh
